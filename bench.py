@@ -2,7 +2,7 @@
 """bench.py -- encoder samples/sec at B=256, N=197, C=768 (Base) on N MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode train|fwd] [--workload base|large512|large1568|mixed]
-                    [--batch B] [--no-cpu-baseline]
+                    [--batch B] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-fwd-leg]]
 
 --gpus N > 1 launches itself: when no torchrun environment is present the script re-executes under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`, one rank per GPU; started
@@ -12,13 +12,24 @@ One "step" (mode=train, the default; BASELINE config 2 "Meta-Transformer-Base fo
     forward of the 12-layer/768-d encoder on a per-GPU batch of synthetic bf16 tokens, backward (input + all weight
     gradients), one RCCL all-reduce per flat gradient bucket when N > 1 (through the C ABI: me_allreduce_bucket on the
     communicator's own stream, launched from gradient hooks while backward still runs), fused AdamW on the fp32 masters.
-The default run also times the encoder FORWARD alone (torch.no_grad) -- the configuration the north star's "40 % MFMA"
-target is quoted on -- and reports it in the same JSON line under "fwd".
 
 Prints ONE JSON line (rank 0).  `value` = whole-job samples/s with the tokens resident in HBM, timed with the library's
-launch-timing hooks OFF.  `roofline` is for the dominant kernel (the bf16 NT MFMA GEMM): algorithmic FLOPs of its launches
-/ their summed duration, from HIP events on the launch stream in a SEPARATE pass of the same steps right after the timed
-region.  `cpu_baseline` = the reference's CPU formulation on the host cores (rank 0, N=1), threads and batch swept.
+launch-timing hooks OFF; `ms_per_step` = wall time of one timed step.  A plain run sets up, warms up, times the K steps and
+prints that line, nothing more.
+
+--full adds everything that needs passes of its own, after the timed region:
+  * `fwd`: the encoder FORWARD alone (torch.no_grad) timed too -- the configuration the north star's "40 % MFMA" target is
+    quoted on (--no-fwd-leg leaves it out);
+  * `roofline` for the dominant kernel (the bf16 NT MFMA GEMM): algorithmic FLOPs of its launches / their summed duration,
+    from HIP events on the launch stream in a SEPARATE pass of the same steps; `other_kernels` from the same records;
+    `schedule` (a serial pass of the step, timed); `per_rank_gemm` (N > 1); `power` (socket power over the timed steps);
+  * `cpu_baseline` = the reference's CPU formulation on the host cores (rank 0, N=1), threads and batch swept
+    (--no-cpu-baseline leaves it out).
+
+--dump-outputs DIR writes what the last timed step computed, as float32 .npy files (rank 0): `y` (the encoder output) and,
+when training, `x_grad` (dL/dx), `param_grad` (the flat fp32 gradient) and `param` (the flat fp32 weights after AdamW).
+Arrays above DUMP_SAMPLE elements are a fixed, seeded sample of their flattened elements (same indices every run).
+Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -37,6 +48,7 @@ PEAK_BF16_TFLOPS = 2500.0      # MI355X dense bf16 MFMA (MI355X_MICROARCH.md: ~2
 PEAK_F32_TFLOPS = 157.3        # f32-input MFMA (v_mfma_f32_32x32x2_f32): the f32 vector rate, 1/16 of bf16 (same guide)
 PEAK_X3_TFLOPS = PEAK_BF16_TFLOPS / 3.0      # fp32-accurate mode: three bf16 MFMA products per fp32 product
 PEAK_HBM_TBPS = 8.0            # HBM3E (same guide)
+DUMP_SAMPLE = 1 << 21          # --dump-outputs: elements kept per array (4 arrays x 8 MiB of float32 at most)
 
 WORKLOADS = {       # name: (model, per-GPU batch, tokens)
     "base": ("base", 256, 197),          # BASELINE config 2 (the metric)
@@ -62,8 +74,12 @@ def parse():
     ap.add_argument("--fp32-mode", choices=["exact", "3xbf16"], default="exact",
                     help="with --dtype fp32: 3xbf16 = fp32-accurate arithmetic on the bf16 matrix pipe (ME_BF16X3: three bf16 products per "
                          "Linear on hi / lo split operands, ~1e-5 relative; attention as three-product bf16 MFMA too -- me_attention_fwd_x3 / _bwd_x3 -- for head_dim 64, N > 64); roofline against 2500 / 3 TF")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fwd-leg", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra passes: forward leg, per-kernel roofline / other_kernels, serial schedule, power, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; large arrays as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-fwd-leg", action="store_true", help="with --full: leave out the forward-only leg")
     ap.add_argument("--no-wgrad-overlap", action="store_true",
                     help="train: keep the weight-gradient GEMMs in program order on the one stream (me_block_bwd_overlap(0))")
     ap.add_argument("--opt-prefetch", action="store_true",
@@ -186,6 +202,7 @@ def main():
 
     train = args.mode == "train"
     flat = opt = reducer = None
+    last = {} if args.dump_outputs else None      # --dump-outputs: the output of the step that ran last (dropped when the next one starts)
     if train:
         enc.train()
         # 1-D parameters and biases carry no weight decay, as in the reference recipes (Video/optim_factory.py:67-73)
@@ -199,6 +216,8 @@ def main():
         x.requires_grad_(True)                   # the tokenizer in front of the encoder needs dL/dx
 
         def step():
+            if last is not None:
+                last.clear()
             flat.zero_grad()
             x.grad = None
             y = enc(x)
@@ -206,12 +225,18 @@ def main():
             if reducer is not None:
                 reducer.finish()
             opt.step(grad_scale=1.0 / world)
+            if last is not None:
+                last["y"] = y
     else:
         enc.eval()
 
         def step():
+            if last is not None:
+                last.clear()
             with torch.no_grad():
-                enc(x)
+                y = enc(x)
+            if last is not None:
+                last["y"] = y
 
     def fwd_step():
         with torch.no_grad():
@@ -306,22 +331,39 @@ def main():
     # overlapped ones (profiles/r04_train_serial_summary.txt / r04_train_summary.txt).
     overlap = bool(train and not args.no_wgrad_overlap and os.environ.get("ME_WGRAD_OVERLAP", "1") != "0")
     ops.block_bwd_overlap(overlap)
-    elapsed = timed(step, args.steps, args.warmup, power_key="step")
+    elapsed = timed(step, args.steps, args.warmup, power_key="step" if args.full else None)
+
+    def dump_outputs(d):
+        """the arrays the last timed step handed its caller, as float32; above DUMP_SAMPLE elements a seeded sample of them"""
+        import numpy as np
+        os.makedirs(d, exist_ok=True)
+        arrays = {"y": last["y"]}
+        if train:
+            arrays.update(x_grad=x.grad, param_grad=flat.flat_grad, param=flat.flat_param)
+        for i, (name, t) in enumerate(arrays.items()):
+            v = t.detach().reshape(-1)
+            if v.numel() > DUMP_SAMPLE:
+                idx = torch.randint(v.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(4242 + i)).sort().values
+                v = v[idx.to(v.device)]
+            np.save(os.path.join(d, f"{name}.npy"), v.float().cpu().numpy())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs)          # before any further pass changes the weights or the outputs
     psteps = max(1, min(args.steps, 5))
-    serial_el = None
-    if train:
-        ops.block_bwd_overlap(False)
-        if overlap:
-            serial_el = timed(step, psteps, 1) / psteps
-    prof = profiled(step, psteps)
-    ops.block_bwd_overlap(overlap)
-    fwd = None
-    if train and not args.no_fwd_leg:
-        enc.eval()
-        fwd_el = timed(fwd_step, args.steps, min(args.warmup, 2), power_key="fwd")
-        fwd_prof = profiled(fwd_step, psteps)
-        enc.train()
-        fwd = (fwd_el, fwd_prof)
+    serial_el = prof = fwd = None
+    if args.full:
+        if train:
+            ops.block_bwd_overlap(False)
+            if overlap:
+                serial_el = timed(step, psteps, 1) / psteps
+        prof = profiled(step, psteps)
+        ops.block_bwd_overlap(overlap)
+        if train and not args.no_fwd_leg:
+            enc.eval()
+            fwd_el = timed(fwd_step, args.steps, min(args.warmup, 2), power_key="fwd")
+            fwd_prof = profiled(fwd_step, psteps)
+            enc.train()
+            fwd = (fwd_el, fwd_prof)
 
     def pmc_traffic(mode):
         """HBM bytes per launch of the roofline kernel from the committed PMC passes of this same command (rocprofv3 --pmc
@@ -436,7 +478,7 @@ def main():
 
     comm_info = comm.info() if comm is not None else None
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         # per-rank averages of the two GEMM classes from the same event records: a communication kernel that holds CUs shows up
         # as slower NT / wgrad launches on that rank (the resident NT kernel claims its tiles, the wgrad kernel does not)
         def _avg(recs, code):
@@ -471,19 +513,19 @@ def main():
                    "parallelism": f"dp{world}" if world > 1 else "single",
                    "grad_allreduce": (f"me_allreduce_bucket (RCCL behind the C ABI, own stream, event hand-off): one all-reduce(sum) per "
                                       f"64 MiB flat fp32 bucket ({args.grad_wire} on the wire) launched from grad hooks, 1/world folded into AdamW; "
-                                      f"{comm_info['buckets_reduced'] // max(1, args.steps + args.warmup + psteps)} buckets/step, "
+                                      f"{comm_info['buckets_reduced'] // max(1, args.steps + args.warmup + (psteps if args.full else 0))} buckets/step, "
                                       f"RCCL world {comm_info['world']}") if (comm_info and train) else
                                      (f"{comm_fallback}: one all_reduce(sum) per 64 MiB flat fp32 bucket from grad hooks" if (comm_fallback and train) else None)},
         "model_tflops_per_s": round(value * model_flops / 1e12, 2),
         "mfma_frac_end_to_end": round(value * model_flops / 1e12 / ((PEAK_X3_TFLOPS if x3 else PEAK_F32_TFLOPS if f32 else PEAK_BF16_TFLOPS) * world), 4),
-        "per_rank_gemm": per_rank,
-        "roofline": gemm_roofline(prof, serial_el or step_s, psteps, train),
-        "other_kernels": other_kernels(prof, serial_el or step_s, psteps),
     }
+    if args.full:
+        out.update(per_rank_gemm=per_rank, roofline=gemm_roofline(prof, serial_el or step_s, psteps, train),
+                   other_kernels=other_kernels(prof, serial_el or step_s, psteps))
     if power_info.get("step"):
         # (measured, not modelled: the step runs at the socket's power cap -- T = J / P)
         out["power"] = dict(power_info["step"], pJ_per_model_flop=round(power_info["step"]["J_per_step"] / (B * model_flops) * 1e12, 3))      # (this GPU's joules over this GPU's samples)
-    if train:
+    if train and args.full:
         out["schedule"] = {"wgrad_side_stream": overlap,
                            "serial_ms_per_step": round(1e3 * serial_el, 3) if serial_el else None,
                            "note": ("timed steps: weight-gradient GEMMs on me_block_bwd's side stream beside the dY -> dX chain; roofline / "
@@ -501,7 +543,7 @@ def main():
                       "other_kernels": other_kernels(fwd_prof, fs, psteps)}
         if power_info.get("fwd"):
             out["fwd"]["power"] = power_info["fwd"]
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # the CPU leg runs in its own process (fresh OpenMP pool, hard timeout) so it can never stall the bench
         cmd = [sys.executable, "-m", "oracle.cpu_baseline", "--depth", str(L), "--dim", str(C), "--heads", str(H),
                "--tokens", str(N), "--budget-s", str(args.cpu_budget_s)] + ([] if train else ["--forward-only"])
@@ -513,7 +555,7 @@ def main():
         except Exception as e:          # noqa: BLE001 -- a baseline failure must not lose the GPU measurement
             out["cpu_baseline"] = {"value": None, "unit": "samples/s", "cores": None, "kind": "port",
                                    "sample": f"failed: {type(e).__name__}: {e}"[:300]}
-    else:
+    elif args.full:
         out["cpu_baseline"] = None
     print(json.dumps(out), flush=True)
     if world > 1:

@@ -83,7 +83,7 @@ def test_bench_forced_dist_on_one_gpu():
     """ME_BENCH_FORCE_DIST=1 python bench.py --gpus 1: the whole step with the RCCL-behind-the-C-ABI exchange in it."""
     env = dict(os.environ, ME_BENCH_FORCE_DIST="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--batch", "16", "--no-cpu-baseline", "--no-fwd-leg"], env=env, capture_output=True, text=True, timeout=600)
+                        "--batch", "16", "--full", "--no-cpu-baseline", "--no-fwd-leg"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and "me_allreduce_bucket" in line["config"]["grad_allreduce"]

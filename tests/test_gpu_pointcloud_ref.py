@@ -2,11 +2,11 @@
 
   * me_fps against the reference's OWN kernel -- PointCloud/openpoints/cpp/pointnet2_batch/src/sampling_gpu.cu:101-258,
     compiled unmodified for gfx950 by oracle/build_ref.py into oracle/_ref/libref_fps.so and run on the same clouds
-    (ties, lattices, the block sizes opt_n_threads picks, the S3DIS cloud size);
+    (ties, lattices, the block sizes opt_n_threads picks, the S3DIS cloud size); its indices are stored in
+    tests/golden/fps_reference.npz (oracle/make_fps_golden.py), and where the library is built the kernel is run again;
   * PointPatchEmbed and ClsHead against tests/golden/pointcloud.npz, written by oracle/make_golden.py from the reference's
     own classes (group_embed.py:60-172, cls_base.py:77-136), parameters loaded with load_state_dict(strict=True).
 """
-import ctypes
 import json
 import os
 
@@ -16,49 +16,37 @@ import torch
 
 from conftest import GOLDEN, ROOT, TOL_F32, check_close, rel_err
 from metatransformer_amd import heads
+from oracle import make_fps_golden as mfg
 
 pytestmark = pytest.mark.gpu
 
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_fps.so")
-LAUNCHER = "_Z39furthest_point_sampling_kernel_launcheriiiPKfPfPi"       # sampling_gpu.cu:212
 
 
 @pytest.fixture(scope="module")
 def ref_fps():
-    if not os.path.isfile(REF_SO):
-        pytest.skip("oracle/_ref/libref_fps.so is not built (python -m oracle.build_ref in the build container; it travels "
-                    "to the GPU box with the snapshot)")
-    lib = ctypes.CDLL(REF_SO)
-    fn = getattr(lib, LAUNCHER)
-    fn.restype = None
-    fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    """(n, m, seed, clouds) -> the reference kernel's indices on mfg.fps_clouds(n, seed)[:clouds], from tests/golden/fps_reference.npz
+    (written by oracle/make_fps_golden.py from that kernel).  Where oracle/_ref/libref_fps.so is built, the kernel also runs
+    and must still return the stored indices."""
+    z = np.load(os.path.join(GOLDEN, "fps_reference.npz"))
+    live = mfg.load_kernel() if os.path.isfile(REF_SO) else None
 
-    def run(p: torch.Tensor, m: int) -> torch.Tensor:
-        B, n, _ = p.shape
-        idx = torch.zeros(B, m, dtype=torch.int32, device=p.device)
-        temp = torch.full((B, n), 1e10, dtype=torch.float32, device=p.device)      # subsample.py:96 fill_(1e10)
-        torch.cuda.synchronize()
-        fn(B, n, m, p.data_ptr(), temp.data_ptr(), idx.data_ptr())                 # default stream, as the reference launches it
-        torch.cuda.synchronize()
+    def want(n, m, seed, keep, p):
+        k = mfg.case_key(n, m, seed)
+        assert float(p.double().sum()) == float(z[k + "/cloud_sum"]), f"{k}: the seeded cloud differs from the one the fixture was made on"
+        idx = torch.from_numpy(z[k + "/idx"])
+        if live is not None:
+            assert torch.equal(live(p.cuda().contiguous(), m).cpu(), idx), f"{k}: the reference kernel no longer returns the stored indices"
         return idx
-    return run
-
-
-def _clouds(n, seed):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.rand(4, n, 3, generator=g) * 2 - 1
-    p[1, n // 2:] = p[1, : n - n // 2].clone()                   # exact duplicates: ties in every round
-    p[2] = torch.round(p[2] * 4) / 4                             # a coarse lattice: many equal distances, exact arithmetic
-    p[3] = p[3] * 1e3                                            # large coordinates: rounding of the distance decides
-    return p
+    return want
 
 
 @pytest.mark.parametrize("n,m", [(2, 2), (5, 5), (33, 20), (64, 64), (100, 50), (777, 100), (1024, 256), (2048, 512), (3000, 64),
                                  (8192, 300), (24000, 1500)])
 def test_fps_indices_equal_the_reference_kernel(dev, ref_fps, n, m):
-    p = _clouds(n, 100 + n).to(dev).contiguous()
-    want = ref_fps(p, m)
-    got = heads.furthest_point_sample(p, m)
+    p = mfg.fps_clouds(n, 100 + n)
+    want = ref_fps(n, m, 100 + n, 4, p).to(dev)
+    got = heads.furthest_point_sample(p.to(dev).contiguous(), m)
     assert got.dtype == torch.int32 and bool((got[:, 0] == 0).all())
     same = torch.equal(got, want)
     if not same:
@@ -68,16 +56,16 @@ def test_fps_indices_equal_the_reference_kernel(dev, ref_fps, n, m):
 
 def test_fps_memory_resident_form_equals_the_reference_kernel(dev, ref_fps):
     """n beyond the register-resident form (24 576 points): the same rounds with points and temp in memory"""
-    p = _clouds(30000, 7)[:3].to(dev).contiguous()
-    assert torch.equal(heads.furthest_point_sample(p, 200), ref_fps(p, 200))
+    p = mfg.fps_clouds(30000, 7)[:3].contiguous()
+    assert torch.equal(heads.furthest_point_sample(p.to(dev), 200).cpu(), ref_fps(30000, 200, 7, 3, p))
 
 
 def test_literal_restatement_equals_the_reference_kernel(dev, ref_fps):
     """oracle.tokenizer_oracle.fps_reference (used on CPU to generate tests/golden/pointcloud.npz) follows the same kernel"""
     from oracle import tokenizer_oracle as to
     for n, m in ((100, 40), (777, 60), (1500, 48)):
-        p = _clouds(n, 300 + n)
-        assert np.array_equal(to.fps_reference(p.numpy(), m), ref_fps(p.to(dev).contiguous(), m).cpu().numpy()), (n, m)
+        p = mfg.fps_clouds(n, 300 + n)
+        assert np.array_equal(to.fps_reference(p.numpy(), m), ref_fps(n, m, 300 + n, 4, p).numpy()), (n, m)
 
 
 def _load(z, prefix):

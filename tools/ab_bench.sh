@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 REPS=${REPS:-2}
-ARGS=${ARGS:---steps 10 --warmup 3 --no-cpu-baseline}
+ARGS=${ARGS:---steps 10 --warmup 3 --full --no-cpu-baseline}
 cp metatransformer_amd/libmetaenc.so /tmp/cur.so
 for rep in $(seq $REPS); do
   for arm in "$@"; do

@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 REPS=${REPS:-3}
-ARGS=${ARGS:---steps 20 --warmup 5 --no-cpu-baseline --mode fwd}
+ARGS=${ARGS:---steps 20 --warmup 5 --full --no-cpu-baseline --mode fwd}
 cp metatransformer_amd/libmetaenc.so /tmp/cur.so
 for rep in $(seq $REPS); do
   for arm in "$@"; do
