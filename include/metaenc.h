@@ -525,13 +525,36 @@ int me_pool_tokens_bwd(const float* dy, const int32_t* argmax, void* dx, int dx_
  *   the points and running distances held in registers for all m rounds: points [B, n, 3] fp32 -> idx [B, m] int32
  *   (idx[:, 0] = 0).  temp = [B, n] fp32 scratch, touched only by the memory-resident form (n > 24 576).
  * me_knn: for every query [B, m, 3] the k nearest of support [B, n, 3] (squared distance, ascending, ties -> lower
- *   index): what KNN.forward's cdist + topk(largest=False) selects (openpoints/models/layers/group.py:12-28). n <= 10240.
+ *   index): what KNN.forward's cdist + topk(largest=False) selects (openpoints/models/layers/group.py:12-28).  n <= 10240 runs
+ *   the LDS-resident form; larger clouds run me_knn_stream.
  * me_group_relative: rows[(b, s, j), 0:3] = points[b, idx[b, s, j]] - centers[b, s] (grouping_operation + relative_xyz,
  *   group.py:310-313), columns 3..cols-1 zero (cols = the GEMM's padded reduction length). */
 int me_fps(const float* points, int32_t* idx, float* temp, int B, int n, int m, void* stream);
 int me_knn(const float* support, const float* query, int32_t* idx, int B, int n, int m, int k, void* stream);
 int me_group_relative(const float* points, const float* centers, const int32_t* idx, float* rows, int B, int n, int m,
                       int k, int cols, void* stream);
+
+/* ------------------------------------------------------------------ P3Embed grouping
+ * The progressive point patch embed (PointCloud/openpoints/models/layers/group_embed.py:176-286) at room scale.
+ * me_knn_stream: me_knn's contract (idx [B, m, k] int32, nearest first, the (squared distance, index) order with the distance
+ *   evaluated as me_knn does) for any n >= k and k <= 64 (ME_ERR_UNSUPPORTED above): support tiles streamed through LDS, one
+ *   running top-k per query held across the lanes of a wave.  me_knn dispatches here for n > 10240.
+ * me_group_features: the GEMM operand rows of the grouped features, rows [B * m * k, cols] fp32 (cols a multiple of 8):
+ *   row(b, s, j) = [ p[nbr] - p[ctr] (3) | part | 0 ... ], nbr = nbr_idx[b, s, j], ctr = ctr_idx[b, s] (the FPS output),
+ *   part by mode (get_aggregation_feautres, group.py:323-335): ME_GROUP_DP none, ME_GROUP_DP_FJ f[nbr] (C),
+ *   ME_GROUP_DP_DF f[nbr] - f[ctr] (C), ME_GROUP_DP_FJ_DF f[nbr] | f[nbr] - f[ctr] (2 C).  feats [B, n, C] token-major,
+ *   ME_F32 or ME_BF16 (may be NULL for ME_GROUP_DP).  An index outside [0, n) gives a NaN row.
+ * me_group_features_bwd: df [B, n, C] (ME_F32 / ME_BF16) = the gradient of the feature part of the rows; every element
+ *   written.  Deterministic: the index lists are inverted by a counting sort, each point's list ordered by row id and summed
+ *   in that order (no float atomics), so two runs are bit-identical.  The points carry no gradient.
+ *   workspace: me_group_features_bwd_workspace(B, n, m, k, C) bytes (none for ME_GROUP_DP). */
+enum { ME_GROUP_DP = 0, ME_GROUP_DP_FJ = 1, ME_GROUP_DP_DF = 2, ME_GROUP_DP_FJ_DF = 3 };
+int me_knn_stream(const float* support, const float* query, int32_t* idx, int B, int n, int m, int k, void* stream);
+int me_group_features(const float* points, const void* feats, int feats_dtype, const int32_t* ctr_idx, const int32_t* nbr_idx,
+                      float* rows, int B, int n, int m, int k, int C, int cols, int mode, void* stream);
+size_t me_group_features_bwd_workspace(int B, int n, int m, int k, int C);
+int me_group_features_bwd(const float* drows, const int32_t* ctr_idx, const int32_t* nbr_idx, void* df, int df_dtype, int B,
+                          int n, int m, int k, int C, int cols, int mode, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ position-embedding table resize
  * Replaces TIMMVisionTransformer.resize_pos_embed (Image/detection/mmdet_custom/models/backbones/base/vit.py:459-486,

@@ -28,6 +28,7 @@ ME_PROF_LN_FWD, ME_PROF_LN_BWD, ME_PROF_ATTN_FWD, ME_PROF_ATTN_BWD, ME_PROF_ROW_
 ME_COMM_ID_BYTES = 128
 ME_RESIZE_BILINEAR, ME_RESIZE_BICUBIC = 0, 1
 ME_POOL_MEAN, ME_POOL_MAX, ME_POOL_FIRST = 0, 1, 2
+ME_GROUP_DP, ME_GROUP_DP_FJ, ME_GROUP_DP_DF, ME_GROUP_DP_FJ_DF = 0, 1, 2, 3
 
 
 class MetaEncError(RuntimeError):
@@ -198,6 +199,12 @@ SIGNATURES = {
     "me_fps": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "me_knn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "me_group_relative": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "me_knn_stream": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "me_group_features": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_int, c_void_p]),
+    "me_group_features_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "me_group_features_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_void_p, c_size_t, c_void_p]),
     "me_pool_tokens": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "me_pool_tokens_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "me_resize_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),

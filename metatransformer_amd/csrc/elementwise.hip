@@ -1050,8 +1050,8 @@ extern "C" int me_fps(const float* points, int32_t* idx, float* temp, int B, int
 extern "C" int me_knn(const float* support, const float* query, int32_t* idx, int B, int n, int m, int k, void* stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     ME_CHECK_ARG(support && query && idx && B > 0 && n > 0 && m > 0 && k > 0 && k <= n, "me_knn: bad args");
+    if (n > 10240) return me_knn_stream(support, query, idx, B, n, m, k, stream_);      // beyond the LDS-resident form
     const size_t lds = (size_t)4 * n * sizeof(float);
-    ME_CHECK_ARG(lds <= 160 * 1024, "me_knn: %d support points exceed the LDS-resident form (max 10240)", n);
     static OncePerDevice once;
     if (once.need()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipLaunchKernelGGL(knn_kernel, dim3((unsigned)((m + 3) / 4), (unsigned)B), dim3(256), lds, stream, support, query, idx, n, m, k);

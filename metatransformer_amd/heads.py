@@ -15,6 +15,7 @@ whose slices ARE the parameters, its bf16 mirror for the forward GEMMs and the p
 """
 from __future__ import annotations
 
+import math
 import re
 from collections import OrderedDict
 from typing import Optional
@@ -362,3 +363,228 @@ class PointPatchEmbed(nn.Module):
     def forward(self, p: torch.Tensor, x: Optional[torch.Tensor] = None):
         out, center, _, _ = self.tokens(p)
         return [p, center], [x, out.transpose(1, 2)]
+
+
+# ----------------------------------------------------------------------------------------------------- P3Embed
+
+_GROUP_MODE = {"dp_fj": _capi.ME_GROUP_DP_FJ, "dp_df": _capi.ME_GROUP_DP_DF, "dp_fj_df": _capi.ME_GROUP_DP_FJ_DF}
+
+
+def _group_width(mode: int, C: int) -> int:
+    return 3 + {_capi.ME_GROUP_DP: 0, _capi.ME_GROUP_DP_FJ: C, _capi.ME_GROUP_DP_DF: C, _capi.ME_GROUP_DP_FJ_DF: 2 * C}[mode]
+
+
+class _GroupFeaturesFn(torch.autograd.Function):
+    """rows [B*m*k, cols] fp32 = me_group_features(p, f, ctr, nbr); backward: df by me_group_features_bwd (the points carry
+    no gradient)"""
+
+    @staticmethod
+    def forward(ctx, p, f, ctr, nbr, mode, cols):
+        B, n, _ = p.shape
+        m, k = nbr.shape[1], nbr.shape[2]
+        C = f.shape[2] if f is not None else 0
+        rows = torch.empty(B * m * k, cols, dtype=torch.float32, device=p.device)
+        check(_capi.load().me_group_features(ptr(p), ptr(f), dtype_code(f.dtype) if f is not None else _capi.ME_F32, ptr(ctr),
+                                             ptr(nbr), ptr(rows), B, n, m, k, C, cols, mode, stream_ptr()), "me_group_features")
+        ctx.save_for_backward(ctr, nbr)
+        ctx.meta = (B, n, m, k, C, cols, mode, f.dtype if f is not None else None)
+        return rows
+
+    @staticmethod
+    def backward(ctx, drows):
+        ctr, nbr = ctx.saved_tensors
+        B, n, m, k, C, cols, mode, fdt = ctx.meta
+        if fdt is None or not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None
+        lib = _capi.load()
+        df = torch.empty(B, n, C, dtype=fdt, device=drows.device)
+        ws = torch.empty(max(1, int(lib.me_group_features_bwd_workspace(B, n, m, k, C))), dtype=torch.uint8, device=drows.device)
+        d = drows.float().contiguous()
+        check(lib.me_group_features_bwd(ptr(d), ptr(ctr), ptr(nbr), ptr(df), dtype_code(fdt), B, n, m, k, C, cols, mode, ptr(ws),
+                                        ws.numel(), stream_ptr()), "me_group_features_bwd")
+        return None, df, None, None, None, None
+
+
+def group_features(p: torch.Tensor, f: Optional[torch.Tensor], ctr: torch.Tensor, nbr: torch.Tensor, feature_type: str = "dp_df",
+                   cols: Optional[int] = None) -> torch.Tensor:
+    """The grouped GEMM operand rows of P3Embed: points [B, n, 3], token-major features [B, n, C] (fp32 / bf16), centre
+    indices [B, m] and neighbour indices [B, m, k] (int32) -> rows [B*m*k, cols] fp32, row (b, s, j) =
+    [p[nbr] - p[ctr] | feature part | 0 ...] with the feature part of ``feature_type`` ('dp': none, 'dp_fj': f[nbr], 'dp_df':
+    f[nbr] - f[ctr], 'dp_fj_df': both); cols defaults to the width rounded up to a multiple of 8.  Differentiable in f."""
+    mode = _capi.ME_GROUP_DP if feature_type == "dp" else _GROUP_MODE.get(feature_type)
+    if mode is None:
+        raise MetaEncError(f"group_features: feature_type {feature_type!r} (dp / dp_fj / dp_df / dp_fj_df)")
+    if p.dim() != 3 or p.shape[2] != 3 or not p.is_cuda or nbr.dim() != 3 or ctr.shape != nbr.shape[:2]:
+        raise MetaEncError("group_features: CUDA points [B, n, 3], ctr [B, m], nbr [B, m, k] required (no CPU fallback)")
+    if mode == _capi.ME_GROUP_DP:
+        f = None
+    elif f is None or f.dim() != 3 or f.shape[:2] != p.shape[:2]:
+        raise MetaEncError(f"group_features: feature_type {feature_type!r} needs token-major features [B, n, C]")
+    else:
+        f = f.contiguous() if f.dtype in (torch.float32, torch.bfloat16) else f.float().contiguous()
+    width = _group_width(mode, f.shape[2] if f is not None else 0)
+    cols = cols if cols is not None else (width + 7) // 8 * 8
+    if cols % 8 or cols < width:
+        raise MetaEncError(f"group_features: cols {cols} (a multiple of 8 >= {width})")
+    return _GroupFeaturesFn.apply(p.float().contiguous(), f, ctr.to(torch.int32).contiguous(), nbr.to(torch.int32).contiguous(),
+                                  mode, cols)
+
+
+class LayerNorm2d(nn.LayerNorm):
+    """openpoints LayerNorm2d (layers/norm.py:12-20): a LayerNorm over the channels; it ignores norm_args (eps 1e-5)."""
+
+    def __init__(self, num_channels, **kwargs):
+        super().__init__(num_channels)
+
+
+def _norm_2d(norm_args, channels):
+    """create_norm(norm_args, channels, dimension='2d') (layers/norm.py:74-97) for the norms P3Embed runs: 'bn' / 'bn2d'
+    (BatchNorm2d) and 'ln2d'"""
+    if norm_args is None:
+        return None
+    if isinstance(norm_args, dict):
+        kw = dict(norm_args)
+        norm = kw.pop("norm", None)
+    else:
+        norm, kw = norm_args, {}
+    if norm is None:
+        return None
+    norm = str(norm).lower()
+    if "2d" not in norm:
+        norm += "2d"
+    if norm == "bn2d":
+        return nn.BatchNorm2d(channels, **kw)
+    if norm == "ln2d":
+        return LayerNorm2d(channels, **kw)
+    raise MetaEncError(f"P3Embed: norm_args {norm_args!r} (bn / bn2d / ln2d are implemented)")
+
+
+class P3Embed(nn.Module):
+    """openpoints P3Embed, the progressive point patch embed (group_embed.py:176-286) of the ScanObjectNN / ShapeNetPart /
+    S3DIS / ScanNet Meta-Transformer recipes: per stage FPS to N // 4 centres of the previous stage's points, KNN grouping,
+    the 'dp_df' (or 'dp_fj' / 'dp_fj_df') grouped features, conv1 (1x1 convolutions), max over the group, conv2 on
+    [pooled | conv1 output], max over the group.  Parameters ``convs.{stage}.{0|1}.{i}.{0|1}.*`` as create_convblock2d makes
+    them (no bias where a norm follows), so the reference's checkpoints load strict=True.
+
+    forward(p [B, N, 3], f [B, C, N]) returns the reference's (out_p, out_f) lists, out_f channel-first [B, C_s, S_s].  Inside,
+    features stay token-major [rows, C]: FPS / KNN / grouping, every 1x1 convolution (exact-fp32 GEMM), LayerNorm2d and the
+    max reductions run in libmetaenc.so; BatchNorm2d and ReLU are PyTorch glue.  conv2's first layer runs on cat(pool, fj) as
+    fj W_b^T + broadcast(pool W_a^T): the concatenation is never built and that GEMM is half as long."""
+
+    def __init__(self, sample_ratio=0.0625, scale=4, group_size=32, in_channels=3, layers=4, embed_dim=256, subsample="fps",
+                 group="ballquery", normalize_dp=False, radius=0.1, feature_type="dp_df", relative_xyz=True,
+                 norm_args={"norm": "bn1d"}, act_args={"act": "relu"}, conv_args={"order": "conv-norm-act"}, reduction="max",
+                 **kwargs):
+        super().__init__()
+        if subsample.lower() != "fps":
+            raise MetaEncError(f"P3Embed: subsample {subsample!r} (fps is implemented; random subsampling is not)")
+        if "knn" not in group.lower():
+            raise MetaEncError(f"P3Embed: group {group!r} (knn is implemented; ball query is not)")
+        if normalize_dp:
+            raise MetaEncError("P3Embed: normalize_dp=True is not implemented")
+        if not relative_xyz:
+            raise MetaEncError("P3Embed: relative_xyz=False is not implemented")
+        if feature_type not in _GROUP_MODE:
+            raise MetaEncError(f"P3Embed: feature_type {feature_type!r} (dp_df / dp_fj / dp_fj_df are implemented)")
+        act = act_args.get("act") if isinstance(act_args, dict) else act_args
+        if act is None or str(act).lower() != "relu":
+            raise MetaEncError(f"P3Embed: act_args {act_args!r} (relu is implemented)")
+        order = (conv_args or {}).get("order", "conv-norm-act")
+        if order != "conv-norm-act" or set(conv_args or {}) - {"order"}:
+            raise MetaEncError(f"P3Embed: conv_args {conv_args!r} (order conv-norm-act, no other options)")
+        if reduction in ("mean", "avg", "meanpool", "avgpool"):
+            self.reduction = "mean"
+        elif reduction == "max":
+            self.reduction = "max"
+        else:
+            raise MetaEncError(f"P3Embed: reduction {reduction!r} (max / mean)")
+        if layers < 2 or layers % 2:
+            raise MetaEncError(f"P3Embed: layers={layers} (an even number >= 2)")
+        self.sample_ratio, self.group_size, self.feature_type = sample_ratio, group_size, feature_type
+        self.mode = _GROUP_MODE[feature_type]
+        chmap = {"dp_fj": lambda x: 3 + x, "dp_df": lambda x: x + 3, "dp_fj_df": lambda x: 2 * x + 3}[feature_type]   # CHANNEL_MAP
+
+        def block(cin, cout, with_norm):
+            norm = _norm_2d(norm_args, cout) if with_norm else None
+            mods = [nn.Conv2d(cin, cout, 1, bias=norm is None)]
+            if norm is not None:
+                mods.append(norm)
+            if with_norm:
+                mods.append(nn.ReLU(inplace=True))
+            return nn.Sequential(*mods)
+
+        stages = int(math.log(1 / sample_ratio, scale))
+        embed_dim = int(embed_dim // 2 ** (stages - 1))
+        self.convs = nn.ModuleList()
+        self.channel_list = [in_channels]
+        half = layers // 2
+        for _ in range(stages):
+            channels = [chmap(in_channels)] + [embed_dim] * half + [embed_dim * 2] * (half - 1) + [embed_dim]
+            conv1 = nn.Sequential(*[block(channels[i], channels[i + 1], i != half - 1) for i in range(half)])
+            channels[half] *= 2
+            conv2 = nn.Sequential(*[block(channels[i], channels[i + 1], True) for i in range(half, layers)])
+            self.convs.append(nn.ModuleList([conv1, conv2]))
+            self.channel_list.append(embed_dim)
+            in_channels = embed_dim
+            embed_dim *= 2
+        self.out_channels = channels[-1]
+
+    @staticmethod
+    def _weight(conv: nn.Conv2d, K: int) -> torch.Tensor:
+        w = conv.weight.reshape(conv.out_channels, conv.in_channels)
+        return w if K == w.shape[1] else torch.cat([w, w.new_zeros(w.shape[0], K - w.shape[1])], dim=1)
+
+    @staticmethod
+    def _norm_act(blk: nn.Sequential, f: torch.Tensor) -> torch.Tensor:
+        if len(blk) == 1:
+            return f
+        norm = blk[1]
+        if isinstance(norm, LayerNorm2d):
+            f = _LayerNormFn.apply(f, norm.weight, norm.bias, norm.eps)
+        else:                                       # BatchNorm2d over (B, C, S, k) == batch_norm over the rows of [rows, C]
+            momentum = norm.momentum
+            if norm.training and norm.track_running_stats:
+                norm.num_batches_tracked.add_(1)
+                if momentum is None:
+                    momentum = 1.0 / float(norm.num_batches_tracked)
+            use_batch = norm.training or norm.running_mean is None
+            f = torch.nn.functional.batch_norm(f, norm.running_mean, norm.running_var, norm.weight, norm.bias, use_batch,
+                                               momentum if momentum is not None else 0.0, norm.eps)
+        return torch.relu(f)
+
+    def _stage(self, convs, cur_p: torch.Tensor, cur_f: torch.Tensor, S: int):
+        B = cur_p.shape[0]
+        k = self.group_size
+        idx = furthest_point_sample(cur_p, S)
+        center_p = torch.gather(cur_p, 1, idx.long().unsqueeze(-1).expand(-1, -1, 3)).contiguous()
+        nbr = knn_indices(cur_p, center_p, k)
+        f = group_features(cur_p, cur_f, idx, nbr, self.feature_type)                 # [B*S*k, cols]
+        conv1, conv2 = convs
+        for blk in conv1:
+            f = self._norm_act(blk, linear(f, self._weight(blk[0], f.shape[1]), blk[0].bias))
+        C1 = f.shape[1]
+        pooled = pool_tokens(f.reshape(B * S, k, C1), self.reduction)                 # [B*S, C1]
+        first = conv2[0]
+        w = first[0].weight.reshape(first[0].out_channels, 2 * C1)
+        # cat([pool.expand(k), fj]) @ W^T == fj @ W_b^T + broadcast(pool @ W_a^T)
+        g = linear(f, w[:, C1:].contiguous(), None).reshape(B * S, k, -1) + linear(pooled, w[:, :C1].contiguous(), first[0].bias).unsqueeze(1)
+        f = self._norm_act(first, g.reshape(B * S * k, -1))
+        for blk in list(conv2)[1:]:
+            f = self._norm_act(blk, linear(f, self._weight(blk[0], f.shape[1]), blk[0].bias))
+        out = pool_tokens(f.reshape(B * S, k, f.shape[1]), self.reduction).reshape(B, S, -1)
+        return center_p, out
+
+    def forward(self, p: torch.Tensor, f: Optional[torch.Tensor] = None):
+        if p.dim() != 3 or p.shape[2] != 3 or not p.is_cuda:
+            raise MetaEncError("P3Embed: [B, N, 3] CUDA points required (no CPU fallback)")
+        if f is None:
+            raise MetaEncError("P3Embed: features f [B, C, N] are required (the reference's grouping gathers them)")
+        N = p.shape[1]
+        out_p, out_f = [p], [f]
+        cur_p, cur_f = p.float().contiguous(), f.transpose(1, 2).float().contiguous()        # token-major [B, N, C]
+        for convs in self.convs:
+            N = N // 4
+            cur_p, cur_f = self._stage(convs, cur_p, cur_f, N)
+            out_p.append(cur_p)
+            out_f.append(cur_f.transpose(1, 2))
+        return out_p, out_f
