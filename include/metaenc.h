@@ -556,6 +556,30 @@ size_t me_group_features_bwd_workspace(int B, int n, int m, int k, int C);
 int me_group_features_bwd(const float* drows, const int32_t* ctr_idx, const int32_t* nbr_idx, void* df, int df_dtype, int B,
                           int n, int m, int k, int C, int cols, int mode, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ point segmentation decoder (feature propagation)
+ * PointNet++ feature propagation as the segmentation decoders run it (PointCloud/openpoints/models/layers/upsampling.py,
+ * backbone/pointnext.py FeaturePropogation, backbone/pointvit.py:177-393), on token-major features [rows, C].
+ * me_three_nn: for every unknown point [B, n, 3] its 3 nearest known points [B, m, 3] (m >= 1; m = 0 is ME_ERR_ARG):
+ *   idx [B, n, 3] int32 in the (squared distance, index) order of three_nn_kernel_fast (scan in index order, strict <, so ties
+ *   keep the lower index), the distance evaluated as me_knn does (fmaf(dz, dz, fmaf(dy, dy, dx * dx))), so for m >= 3 the
+ *   indices equal me_knn(k = 3).  weight [B, n, 3] fp32 = three_interpolation's r / sum(r), r = 1 / (dist + 1e-8), and, unless
+ *   NULL, dist [B, n, 3] = sqrt(dist2).  With m < 3 the unused slots keep index 0 and dist = +inf, so their weight is exactly 0.
+ * me_three_interpolate: out[b * n + q, col0 + c] (= or, with accumulate, +=) sum_j weight[b, q, j] *
+ *   feats[b * m + idx[b, q, j], c] for c < C; feats fp32 with leading dimension ldf, out fp32 with leading dimension ldo
+ *   (ldo >= col0 + C).  fp32 arithmetic; an index outside [0, m) gives a NaN row.
+ * me_three_interpolate_bwd: dfeats [B * m, C] (leading dimension ldf) = sum over the (q, j) with idx[b, q, j] = row of
+ *   weight[b, q, j] * dout[b * n + q, col0 + c] (dout leading dimension ldo); every element written, rows no query references
+ *   get exact zeros.  Deterministic: the index lists are inverted by a counting sort and summed in ascending (q, j) order (no
+ *   float atomics), so two runs are bit-identical.  Positions and weights carry no gradient.
+ *   workspace: me_three_interpolate_bwd_workspace(B, n, m) bytes. */
+int me_three_nn(const float* unknown, const float* known, int32_t* idx, float* weight, float* dist, int B, int n, int m,
+                void* stream);
+int me_three_interpolate(const float* feats, int ldf, const int32_t* idx, const float* weight, float* out, int ldo, int col0,
+                         int B, int n, int m, int C, int accumulate, void* stream);
+size_t me_three_interpolate_bwd_workspace(int B, int n, int m);
+int me_three_interpolate_bwd(const float* dout, int ldo, int col0, const int32_t* idx, const float* weight, float* dfeats,
+                             int ldf, int B, int n, int m, int C, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ position-embedding table resize
  * Replaces TIMMVisionTransformer.resize_pos_embed (Image/detection/mmdet_custom/models/backbones/base/vit.py:459-486,
  * also vit_adapter.py:73-78): the [h*w, cols] grid part of a pos-embed table resampled to [H*W, cols] with

@@ -1,7 +1,10 @@
-// point.hip -- the point-cloud grouping of P3Embed (openpoints group_embed.py:176-286) at room scale:
+// point.hip -- the point-cloud grouping of P3Embed (openpoints group_embed.py:176-286) at room scale, and the feature
+// propagation of the point segmentation decoders (PointNet++ three_nn + three_interpolate, layers/upsampling.py):
 //   * me_knn_stream: k nearest support points for clouds of any size (me_knn's LDS-resident form holds n <= 10 240);
 //   * me_group_features / me_group_features_bwd: the grouped GEMM operand rows [dp | f-part | 0 ...] and their
-//     deterministic backward onto the token-major features.
+//     deterministic backward onto the token-major features;
+//   * me_three_nn / me_three_interpolate / me_three_interpolate_bwd: inverse-distance interpolation from the 3 nearest known
+//     points onto token-major rows, and its deterministic backward.
 #include "common.h"
 
 namespace {
@@ -245,14 +248,14 @@ GroupWs group_ws(int B, int n, int m, int k, int C) {
 
 // inverts idx [B, L] (values in [0, n)) into ascending per-point lists of flat positions b * L + l: off [B n + 1], srt
 int invert_lists(const int32_t* idx, int B, int64_t L, int n, int32_t* off, int32_t* cur, int32_t* ent, int32_t* srt,
-                 hipStream_t stream) {
+                 hipStream_t stream, const char* what = "me_group_features_bwd (inverted lists)") {
     const int64_t N = (int64_t)B * n, total = (int64_t)B * L;
-    if (hipMemsetAsync(cur, 0, (size_t)N * 4, stream) != hipSuccess) { me_set_error("me_group_features_bwd: memset failed"); return ME_ERR_HIP; }
+    if (hipMemsetAsync(cur, 0, (size_t)N * 4, stream) != hipSuccess) { me_set_error("%s: memset failed", what); return ME_ERR_HIP; }
     hipLaunchKernelGGL(inv_count_kernel, dim3(pt_blocks(total)), dim3(PT_THREADS), 0, stream, idx, L, total, n, cur);
     hipLaunchKernelGGL(inv_scan_kernel, dim3(1), dim3(1024), 0, stream, cur, off, N);
     hipLaunchKernelGGL(inv_fill_kernel, dim3(pt_blocks(total)), dim3(PT_THREADS), 0, stream, idx, L, total, n, off, cur, ent);
     hipLaunchKernelGGL(inv_sort_kernel, dim3(pt_blocks(N * 64)), dim3(PT_THREADS), 0, stream, off, ent, srt, N);
-    ME_CHECK_LAUNCH("me_group_features_bwd (inverted lists)");
+    ME_CHECK_LAUNCH(what);
     return ME_OK;
 }
 
@@ -260,6 +263,194 @@ bool group_mode_ok(int mode) {
     return mode == ME_GROUP_DP || mode == ME_GROUP_DP_FJ || mode == ME_GROUP_DP_DF || mode == ME_GROUP_DP_FJ_DF;
 }
 int group_width(int mode, int C) { return 3 + (mode == ME_GROUP_DP ? 0 : mode == ME_GROUP_DP_FJ_DF ? 2 * C : C); }
+
+// ---------------------------------------------------------------------------------------------------- three-NN interpolation
+// One unknown point per lane.  A workgroup of TNN_THREADS queries of one cloud streams the known points through LDS in SoA
+// tiles; every lane reads the same tile entry (a broadcast), four points per float4 read of each coordinate array.  Each lane
+// keeps its 3 nearest in registers with three_nn_kernel_fast's strict-< insertion over the points in index order, so ties
+// keep the lower index: the (squared distance, index) order.  The distance is me_knn's expression.  A tile's tail is padded
+// with +inf coordinates, whose distance is never below a running best.  Unused slots (m < 3) keep index 0 and dist2 = +inf
+// (the reference's 1e40 stored as fp32), so their weight is exactly 0.
+constexpr int TNN_THREADS = 128;
+constexpr int TNN_TILE = 1024;       // known points per LDS tile (12 KB, SoA)
+
+// knn_stream_kernel's distance expression
+__device__ __forceinline__ float tnn_dist(float x, float y, float z, float qx, float qy, float qz) {
+    const float dx = x - qx, dy = y - qy, dz = z - qz;
+    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+}
+
+__device__ __forceinline__ void tnn_insert(float d, int k, float& b1, float& b2, float& b3, int& i1, int& i2, int& i3) {
+    if (d < b3) {                                            // rare once the list has filled; the shift itself is selects
+        const bool c1 = d < b1, c2 = d < b2;
+        b3 = c2 ? b2 : d;            i3 = c2 ? i2 : k;
+        b2 = c1 ? b1 : (c2 ? d : b2); i2 = c1 ? i1 : (c2 ? k : i2);
+        b1 = c1 ? d : b1;            i1 = c1 ? k : i1;
+    }
+}
+
+__global__ __launch_bounds__(TNN_THREADS) void three_nn_kernel(const float* __restrict__ unknown, const float* __restrict__ known,
+                                                               int32_t* __restrict__ idx, float* __restrict__ weight,
+                                                               float* __restrict__ dist, int n, int m) {
+    __shared__ __attribute__((aligned(16))) float sx[TNN_TILE];
+    __shared__ __attribute__((aligned(16))) float sy[TNN_TILE];
+    __shared__ __attribute__((aligned(16))) float sz[TNN_TILE];
+    const int b = blockIdx.y;
+    const int q = blockIdx.x * TNN_THREADS + threadIdx.x;
+    const int qc = q < n ? q : n - 1;                        // (a lane past the end still joins the barriers; it writes nothing)
+    const float* up = unknown + ((int64_t)b * n + qc) * 3;
+    const float qx = up[0], qy = up[1], qz = up[2];
+    known += (int64_t)b * m * 3;
+    float b1 = __builtin_inff(), b2 = __builtin_inff(), b3 = __builtin_inff();
+    int i1 = 0, i2 = 0, i3 = 0;
+    for (int t0 = 0; t0 < m; t0 += TNN_TILE) {
+        const int cnt = m - t0 < TNN_TILE ? m - t0 : TNN_TILE;
+        const int cnt4 = (cnt + 3) & ~3;
+        __syncthreads();                                     // the previous tile is consumed
+        for (int i = threadIdx.x; i < cnt4; i += TNN_THREADS) {
+            if (i < cnt) {
+                const float* kp = known + (int64_t)(t0 + i) * 3;
+                sx[i] = kp[0]; sy[i] = kp[1]; sz[i] = kp[2];
+            } else {
+                sx[i] = sy[i] = sz[i] = __builtin_inff();
+            }
+        }
+        __syncthreads();
+        const float4* X = reinterpret_cast<const float4*>(sx);
+        const float4* Y = reinterpret_cast<const float4*>(sy);
+        const float4* Z = reinterpret_cast<const float4*>(sz);
+        for (int j = 0; j < cnt4 / 4; ++j) {
+            const float4 x = X[j], y = Y[j], z = Z[j];
+            const int k = t0 + 4 * j;
+            tnn_insert(tnn_dist(x.x, y.x, z.x, qx, qy, qz), k, b1, b2, b3, i1, i2, i3);
+            tnn_insert(tnn_dist(x.y, y.y, z.y, qx, qy, qz), k + 1, b1, b2, b3, i1, i2, i3);
+            tnn_insert(tnn_dist(x.z, y.z, z.z, qx, qy, qz), k + 2, b1, b2, b3, i1, i2, i3);
+            tnn_insert(tnn_dist(x.w, y.w, z.w, qx, qy, qz), k + 3, b1, b2, b3, i1, i2, i3);
+        }
+    }
+    if (q >= n) return;
+    const int64_t o = ((int64_t)b * n + q) * 3;
+    const float d1 = __builtin_sqrtf(b1), d2 = __builtin_sqrtf(b2), d3 = __builtin_sqrtf(b3);
+    // three_interpolation's weights: r = 1 / (dist + 1e-8), w = r / sum(r), fp32
+    const float r1 = 1.f / (d1 + 1e-8f), r2 = 1.f / (d2 + 1e-8f), r3 = 1.f / (d3 + 1e-8f);
+    const float s = (r1 + r2) + r3;
+    idx[o] = i1; idx[o + 1] = i2; idx[o + 2] = i3;
+    weight[o] = r1 / s; weight[o + 1] = r2 / s; weight[o + 2] = r3 / s;
+    if (dist) { dist[o] = d1; dist[o + 1] = d2; dist[o + 2] = d3; }
+}
+
+// out[r, col0 + c] (= or +=) w0 f[i0, c] + w1 f[i1, c] + w2 f[i2, c] for the rows r = b * n + q, i_j = b * m + idx[r, j].  A wave
+// takes 64 / lpr rows at once (lpr = lanes per row, a power of two covering the row's VEC-wide chunks); consecutive lanes read
+// consecutive chunks of the gathered rows.  An index outside [0, m) gives a NaN row instead of a read out of bounds.
+template <int VEC>
+__global__ __launch_bounds__(PT_THREADS) void three_interp_kernel(const float* __restrict__ feats, int64_t ldf,
+                                                                  const int32_t* __restrict__ idx, const float* __restrict__ weight,
+                                                                  float* __restrict__ out, int64_t ldo, int col0, int n, int m,
+                                                                  int C, int accumulate, int lpr_log2, int64_t rows) {
+    const int lane = threadIdx.x & 63;
+    const int lpr = 1 << lpr_log2;
+    const int sub = lane >> lpr_log2, l = lane & (lpr - 1);
+    const int rpw = 64 >> lpr_log2;
+    const int64_t wave0 = ((int64_t)blockIdx.x * PT_THREADS + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * PT_THREADS) >> 6;
+    for (int64_t r = wave0 * rpw + sub; r < rows; r += nw * rpw) {
+        const int64_t base = (r / n) * m;
+        const int k0 = idx[r * 3], k1 = idx[r * 3 + 1], k2 = idx[r * 3 + 2];
+        const float w0 = weight[r * 3], w1 = weight[r * 3 + 1], w2 = weight[r * 3 + 2];
+        const bool bad = k0 < 0 || k0 >= m || k1 < 0 || k1 >= m || k2 < 0 || k2 >= m;
+        const float* f0 = feats + (base + (bad ? 0 : k0)) * ldf;
+        const float* f1 = feats + (base + (bad ? 0 : k1)) * ldf;
+        const float* f2 = feats + (base + (bad ? 0 : k2)) * ldf;
+        float* o = out + r * ldo + col0;
+        for (int c = l * VEC; c < C; c += lpr * VEC) {
+            if constexpr (VEC == 4) {
+                const float4 a = *reinterpret_cast<const float4*>(f0 + c), e = *reinterpret_cast<const float4*>(f1 + c),
+                             g = *reinterpret_cast<const float4*>(f2 + c);
+                float4 v;
+                v.x = __builtin_fmaf(w2, g.x, __builtin_fmaf(w1, e.x, w0 * a.x));
+                v.y = __builtin_fmaf(w2, g.y, __builtin_fmaf(w1, e.y, w0 * a.y));
+                v.z = __builtin_fmaf(w2, g.z, __builtin_fmaf(w1, e.z, w0 * a.z));
+                v.w = __builtin_fmaf(w2, g.w, __builtin_fmaf(w1, e.w, w0 * a.w));
+                if (bad) v.x = v.y = v.z = v.w = __builtin_nanf("");
+                float4* op = reinterpret_cast<float4*>(o + c);
+                if (accumulate) {
+                    const float4 p = *op;
+                    v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w;
+                }
+                *op = v;
+            } else {
+                float v = __builtin_fmaf(w2, f2[c], __builtin_fmaf(w1, f1[c], w0 * f0[c]));
+                if (bad) v = __builtin_nanf("");
+                o[c] = accumulate ? o[c] + v : v;
+            }
+        }
+    }
+}
+
+// dfeats[v, c] = sum over the (q, j) with idx[q, j] = v, in ascending order of q * 3 + j, of w[q, j] dout[q, col0 + c]; rows that
+// no query references get 0.  The lists come from invert_lists (flat positions (b * n + q) * 3 + j, ascending).
+template <int VEC>
+__global__ __launch_bounds__(PT_THREADS) void three_interp_bwd_kernel(const float* __restrict__ dout, int64_t ldo, int col0,
+                                                                      const float* __restrict__ weight, const int32_t* __restrict__ off,
+                                                                      const int32_t* __restrict__ srt, float* __restrict__ df,
+                                                                      int64_t ldf, int C, int lpr_log2, int64_t rows) {
+    const int lane = threadIdx.x & 63;
+    const int lpr = 1 << lpr_log2;
+    const int sub = lane >> lpr_log2, l = lane & (lpr - 1);
+    const int rpw = 64 >> lpr_log2;
+    const int64_t wave0 = ((int64_t)blockIdx.x * PT_THREADS + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * PT_THREADS) >> 6;
+    for (int64_t v = wave0 * rpw + sub; v < rows; v += nw * rpw) {
+        const int e0 = off[v], e1 = off[v + 1];
+        float* o = df + v * ldf;
+        for (int c = l * VEC; c < C; c += lpr * VEC) {
+            if constexpr (VEC == 4) {
+                float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+                for (int e = e0; e < e1; ++e) {
+                    const int fe = srt[e];
+                    const float w = weight[fe];
+                    const float4 d = *reinterpret_cast<const float4*>(dout + (int64_t)(fe / 3) * ldo + col0 + c);
+                    s.x = __builtin_fmaf(w, d.x, s.x); s.y = __builtin_fmaf(w, d.y, s.y);
+                    s.z = __builtin_fmaf(w, d.z, s.z); s.w = __builtin_fmaf(w, d.w, s.w);
+                }
+                *reinterpret_cast<float4*>(o + c) = s;
+            } else {
+                float s = 0.f;
+                for (int e = e0; e < e1; ++e) {
+                    const int fe = srt[e];
+                    s = __builtin_fmaf(weight[fe], dout[(int64_t)(fe / 3) * ldo + col0 + c], s);
+                }
+                o[c] = s;
+            }
+        }
+    }
+}
+
+// lanes per row (log2) for rows of C floats read VEC at a time: the smallest power of two covering the row, at most a wave
+int lanes_log2(int C, int vec) {
+    const int chunks = (C + vec - 1) / vec;
+    int lg = 0;
+    while ((1 << lg) < chunks && lg < 6) ++lg;
+    return lg;
+}
+unsigned row_blocks(int64_t rows, int lpr_log2) {
+    const int64_t waves = (rows + (64 >> lpr_log2) - 1) / (64 >> lpr_log2);
+    int64_t b = (waves + PT_THREADS / 64 - 1) / (PT_THREADS / 64);
+    const int64_t cap = 256 * 16;
+    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+struct InterpWs {
+    size_t off, cur, ent, srt, total;
+};
+InterpWs interp_ws(int B, int n, int m) {
+    InterpWs w;
+    const size_t N = (size_t)B * m, R = (size_t)B * n * 3;
+    size_t o = 0;
+    auto take = [&](size_t elems) { const size_t at = o; o += (elems * 4 + 255) / 256 * 256; return at; };
+    w.off = take(N + 1); w.cur = take(N); w.ent = take(R); w.srt = take(R);
+    w.total = o;
+    return w;
+}
 
 }  // namespace
 
@@ -339,5 +530,74 @@ extern "C" int me_group_features_bwd(const float* drows, const int32_t* ctr_idx,
     hipLaunchKernelGGL(group_features_bwd_kernel, dim3(pt_blocks(total)), dim3(PT_THREADS), 0, stream, drows, dcs, I(w.noff),
                        I(w.nsrt), I(w.coff), I(w.csrt), df, df_dtype, C, cols, fj_col, df_col, total);
     ME_CHECK_LAUNCH("me_group_features_bwd");
+    return ME_OK;
+}
+
+extern "C" int me_three_nn(const float* unknown, const float* known, int32_t* idx, float* weight, float* dist, int B, int n, int m,
+                           void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    ME_CHECK_ARG(unknown && known && idx && weight && B > 0 && n >= 0, "me_three_nn: bad args");
+    ME_CHECK_ARG(m > 0, "me_three_nn: m=%d known points (at least 1 required)", m);
+    ME_CHECK_ARG(B <= 65535, "me_three_nn: B=%d exceeds the grid's y dimension", B);
+    ME_CHECK_ARG((int64_t)B * n * 3 < (1ll << 31), "me_three_nn: B * n * 3 exceeds int32 row indexing");
+    if (n == 0) return ME_OK;
+    hipLaunchKernelGGL(three_nn_kernel, dim3((unsigned)((n + TNN_THREADS - 1) / TNN_THREADS), (unsigned)B), dim3(TNN_THREADS), 0, stream,
+                       unknown, known, idx, weight, dist, n, m);
+    ME_CHECK_LAUNCH("me_three_nn");
+    return ME_OK;
+}
+
+extern "C" int me_three_interpolate(const float* feats, int ldf, const int32_t* idx, const float* weight, float* out, int ldo,
+                                    int col0, int B, int n, int m, int C, int accumulate, void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    ME_CHECK_ARG(feats && idx && weight && out && B > 0 && n >= 0 && m > 0 && C > 0, "me_three_interpolate: bad args");
+    ME_CHECK_ARG(ldf >= C && col0 >= 0 && ldo >= col0 + C, "me_three_interpolate: ldf %d / ldo %d / col0 %d for C %d", ldf, ldo,
+                 col0, C);
+    const int64_t rows = (int64_t)B * n;
+    if (rows == 0) return ME_OK;
+    const bool vec = C % 4 == 0 && ldf % 4 == 0 && ldo % 4 == 0 && col0 % 4 == 0 && aligned16(feats) && aligned16(out);
+    const int lg = lanes_log2(C, vec ? 4 : 1);
+    if (vec)
+        hipLaunchKernelGGL(three_interp_kernel<4>, dim3(row_blocks(rows, lg)), dim3(PT_THREADS), 0, stream, feats, (int64_t)ldf, idx,
+                           weight, out, (int64_t)ldo, col0, n, m, C, accumulate, lg, rows);
+    else
+        hipLaunchKernelGGL(three_interp_kernel<1>, dim3(row_blocks(rows, lg)), dim3(PT_THREADS), 0, stream, feats, (int64_t)ldf, idx,
+                           weight, out, (int64_t)ldo, col0, n, m, C, accumulate, lg, rows);
+    ME_CHECK_LAUNCH("me_three_interpolate");
+    return ME_OK;
+}
+
+extern "C" size_t me_three_interpolate_bwd_workspace(int B, int n, int m) {
+    if (B <= 0 || n < 0 || m <= 0) return 0;
+    return interp_ws(B, n, m).total;
+}
+
+extern "C" int me_three_interpolate_bwd(const float* dout, int ldo, int col0, const int32_t* idx, const float* weight, float* dfeats,
+                                        int ldf, int B, int n, int m, int C, void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    ME_CHECK_ARG(dfeats && B > 0 && n >= 0 && m > 0 && C > 0 && (n == 0 || (dout && idx && weight)), "me_three_interpolate_bwd: bad args");
+    ME_CHECK_ARG(ldf >= C && col0 >= 0 && ldo >= col0 + C, "me_three_interpolate_bwd: ldf %d / ldo %d / col0 %d for C %d", ldf, ldo,
+                 col0, C);
+    ME_CHECK_ARG((int64_t)B * n * 3 < (1ll << 31) && (int64_t)B * m < (1ll << 31), "me_three_interpolate_bwd: too many rows for int32 lists");
+    const InterpWs w = interp_ws(B, n, m);
+    if (!workspace || workspace_bytes < w.total) {
+        me_set_error("me_three_interpolate_bwd: workspace of %zu bytes needed", w.total);
+        return ME_ERR_WORKSPACE;
+    }
+    char* ws = static_cast<char*>(workspace);
+    auto I = [&](size_t at) { return reinterpret_cast<int32_t*>(ws + at); };
+    int rc = invert_lists(idx, B, (int64_t)n * 3, m, I(w.off), I(w.cur), I(w.ent), I(w.srt), stream,
+                          "me_three_interpolate_bwd (inverted lists)");
+    if (rc != ME_OK) return rc;
+    const int64_t rows = (int64_t)B * m;
+    const bool vec = C % 4 == 0 && ldf % 4 == 0 && ldo % 4 == 0 && col0 % 4 == 0 && aligned16(dout) && aligned16(dfeats);
+    const int lg = lanes_log2(C, vec ? 4 : 1);
+    if (vec)
+        hipLaunchKernelGGL(three_interp_bwd_kernel<4>, dim3(row_blocks(rows, lg)), dim3(PT_THREADS), 0, stream, dout, (int64_t)ldo, col0,
+                           weight, I(w.off), I(w.srt), dfeats, (int64_t)ldf, C, lg, rows);
+    else
+        hipLaunchKernelGGL(three_interp_bwd_kernel<1>, dim3(row_blocks(rows, lg)), dim3(PT_THREADS), 0, stream, dout, (int64_t)ldo, col0,
+                           weight, I(w.off), I(w.srt), dfeats, (int64_t)ldf, C, lg, rows);
+    ME_CHECK_LAUNCH("me_three_interpolate_bwd");
     return ME_OK;
 }

@@ -459,6 +459,19 @@ def _norm_2d(norm_args, channels):
     raise MetaEncError(f"P3Embed: norm_args {norm_args!r} (bn / bn2d / ln2d are implemented)")
 
 
+def _batch_norm_rows(norm, f: torch.Tensor) -> torch.Tensor:
+    """BatchNorm1d / BatchNorm2d over the rows of token-major [rows, C] (== over (B, C, N[, k]) channel-first), tracking the
+    running statistics in training mode as the module itself does"""
+    momentum = norm.momentum
+    if norm.training and norm.track_running_stats:
+        norm.num_batches_tracked.add_(1)
+        if momentum is None:
+            momentum = 1.0 / float(norm.num_batches_tracked)
+    use_batch = norm.training or norm.running_mean is None
+    return torch.nn.functional.batch_norm(f, norm.running_mean, norm.running_var, norm.weight, norm.bias, use_batch,
+                                          momentum if momentum is not None else 0.0, norm.eps)
+
+
 class P3Embed(nn.Module):
     """openpoints P3Embed, the progressive point patch embed (group_embed.py:176-286) of the ScanObjectNN / ShapeNetPart /
     S3DIS / ScanNet Meta-Transformer recipes: per stage FPS to N // 4 centres of the previous stage's points, KNN grouping,
@@ -542,14 +555,7 @@ class P3Embed(nn.Module):
         if isinstance(norm, LayerNorm2d):
             f = _LayerNormFn.apply(f, norm.weight, norm.bias, norm.eps)
         else:                                       # BatchNorm2d over (B, C, S, k) == batch_norm over the rows of [rows, C]
-            momentum = norm.momentum
-            if norm.training and norm.track_running_stats:
-                norm.num_batches_tracked.add_(1)
-                if momentum is None:
-                    momentum = 1.0 / float(norm.num_batches_tracked)
-            use_batch = norm.training or norm.running_mean is None
-            f = torch.nn.functional.batch_norm(f, norm.running_mean, norm.running_var, norm.weight, norm.bias, use_batch,
-                                               momentum if momentum is not None else 0.0, norm.eps)
+            f = _batch_norm_rows(norm, f)
         return torch.relu(f)
 
     def _stage(self, convs, cur_p: torch.Tensor, cur_f: torch.Tensor, S: int):
@@ -588,3 +594,436 @@ class P3Embed(nn.Module):
             out_p.append(cur_p)
             out_f.append(cur_f.transpose(1, 2))
         return out_p, out_f
+
+
+# ----------------------------------------------------------------------------------------------------- point segmentation decoder
+
+def _three_nn(unknown: torch.Tensor, known: torch.Tensor, want_dist: bool):
+    if unknown.dim() != 3 or known.dim() != 3 or unknown.shape[2] != 3 or known.shape[2] != 3 or unknown.shape[0] != known.shape[0]:
+        raise MetaEncError("three_nn: unknown [B, n, 3] and known [B, m, 3] points required")
+    if not (unknown.is_cuda and known.is_cuda):
+        raise MetaEncError("three_nn: CUDA points required (no CPU fallback)")
+    u, k = unknown.detach().float().contiguous(), known.detach().float().contiguous()
+    B, n, _ = u.shape
+    m = k.shape[1]
+    idx = torch.empty(B, n, 3, dtype=torch.int32, device=u.device)
+    w = torch.empty(B, n, 3, dtype=torch.float32, device=u.device)
+    dist = torch.empty(B, n, 3, dtype=torch.float32, device=u.device) if want_dist else None
+    check(_capi.load().me_three_nn(ptr(u), ptr(k), ptr(idx), ptr(w), ptr(dist), B, n, m, stream_ptr()), "me_three_nn")
+    return idx, w, dist
+
+
+def three_nn(unknown: torch.Tensor, known: torch.Tensor):
+    """upsampling.three_nn: [B, n, 3], [B, m, 3] -> (dist [B, n, 3] fp32, idx [B, n, 3] int32), the 3 nearest known points of
+    every unknown point in the (squared distance, index) order (me_three_nn).  No gradient, as in the reference."""
+    idx, _, dist = _three_nn(unknown, known, True)
+    return dist, idx
+
+
+def three_nn_weights(unknown: torch.Tensor, known: torch.Tensor):
+    """(idx [B, n, 3] int32, weight [B, n, 3] fp32): three_nn and three_interpolation's inverse-distance weights in one kernel"""
+    idx, w, _ = _three_nn(unknown, known, False)
+    return idx, w
+
+
+class _InterpolateFn(torch.autograd.Function):
+    """token-major three_interpolate: out [B*n, C] fp32 = interp(feats [B*m, C]), or base [B*n, C] += interp(feats) in place
+    (base is then the output, so the skip GEMM's result absorbs the interpolation without a second [B*n, C] buffer).  The
+    gradient goes to feats (me_three_interpolate_bwd) and passes through to base; indices and weights carry none."""
+
+    @staticmethod
+    def forward(ctx, feats, idx, weight, base, B, n, m):
+        f = feats.float().contiguous()
+        C = f.shape[1]
+        if base is None:
+            out, acc = torch.empty(B * n, C, dtype=torch.float32, device=f.device), 0
+        else:
+            if base.dtype != torch.float32 or not base.is_contiguous() or base.shape != (B * n, C):
+                raise MetaEncError("three_interpolate: the accumulation target must be contiguous fp32 [B*n, C]")
+            out, acc = base, 1
+            ctx.mark_dirty(base)
+        check(_capi.load().me_three_interpolate(ptr(f), C, ptr(idx), ptr(weight), ptr(out), C, 0, B, n, m, C, acc, stream_ptr()),
+              "me_three_interpolate")
+        ctx.save_for_backward(idx, weight)
+        ctx.meta = (B, n, m, C, feats.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        idx, weight = ctx.saved_tensors
+        B, n, m, C, fdt = ctx.meta
+        df = None
+        if ctx.needs_input_grad[0]:
+            lib = _capi.load()
+            d = dout.float().contiguous()
+            df = torch.empty(B * m, C, dtype=torch.float32, device=d.device)
+            ws = torch.empty(max(1, int(lib.me_three_interpolate_bwd_workspace(B, n, m))), dtype=torch.uint8, device=d.device)
+            check(lib.me_three_interpolate_bwd(ptr(d), C, 0, ptr(idx), ptr(weight), ptr(df), C, B, n, m, C, ptr(ws), ws.numel(),
+                                               stream_ptr()), "me_three_interpolate_bwd")
+            df = df.to(fdt)
+        return df, None, None, dout if ctx.needs_input_grad[3] else None, None, None, None
+
+
+def _interpolate_rows(feats: torch.Tensor, idx: torch.Tensor, weight: torch.Tensor, base: Optional[torch.Tensor] = None):
+    """feats [B, m, C] -> [B*n, C] fp32 (added onto base [B*n, C] when given)"""
+    B, m, C = feats.shape
+    return _InterpolateFn.apply(feats.reshape(B * m, C), idx, weight, base, B, idx.shape[1], m)
+
+
+def three_interpolation(unknown_xyz: torch.Tensor, known_xyz: torch.Tensor, know_feat: torch.Tensor) -> torch.Tensor:
+    """upsampling.three_interpolation: unknown [B, n, 3], known [B, m, 3], features [B, C, m] -> [B, C, n] fp32 (fp32 under
+    autocast too, as the reference's custom_fwd(cast_inputs=float32)).  Differentiable in the features only."""
+    if know_feat.dim() != 3 or known_xyz.dim() != 3 or know_feat.shape[2] != known_xyz.shape[1]:
+        raise MetaEncError("three_interpolation: features [B, C, m] for known points [B, m, 3] required")
+    if not know_feat.is_cuda:
+        raise MetaEncError("three_interpolation: CUDA tensors required (no CPU fallback)")
+    idx, w = three_nn_weights(unknown_xyz, known_xyz)
+    B, n = idx.shape[:2]
+    out = _interpolate_rows(know_feat.transpose(1, 2).float(), idx, w)
+    return out.view(B, n, -1).transpose(1, 2)
+
+
+class LayerNorm1d(nn.LayerNorm):
+    """openpoints LayerNorm1d (layers/norm.py:23-31): a LayerNorm over the channels; it ignores norm_args (eps 1e-5)."""
+
+    def __init__(self, num_channels, **kwargs):
+        super().__init__(num_channels)
+
+
+def _norm_1d(norm_args, channels, who):
+    """create_norm(norm_args, channels, dimension='1d') (layers/norm.py:74-97) for 'bn' / 'bn1d' (BatchNorm1d) and 'ln' / 'ln1d'
+    (LayerNorm1d)"""
+    if norm_args is None:
+        return None
+    if isinstance(norm_args, dict):
+        kw = dict(norm_args)
+        norm = kw.pop("norm", None)
+    else:
+        norm, kw = norm_args, {}
+    if norm is None:
+        return None
+    norm = str(norm).lower()
+    if "1d" not in norm:
+        norm += "1d"
+    if norm == "bn1d":
+        return nn.BatchNorm1d(channels, **kw)
+    if norm == "ln1d":
+        return LayerNorm1d(channels, **kw)
+    raise MetaEncError(f"{who}: norm_args {norm_args!r} (bn / bn1d / ln1d are implemented)")
+
+
+def _act_1d(act_args, who):
+    if act_args is None:
+        return None
+    act = act_args.get("act") if isinstance(act_args, dict) else act_args
+    if act is None:
+        return None
+    act = str(act).lower()
+    if act == "relu":
+        return nn.ReLU(inplace=True)
+    if act == "gelu":
+        return nn.GELU()
+    raise MetaEncError(f"{who}: act_args {act_args!r} (relu / gelu are implemented)")
+
+
+def _check_conv_args(conv_args, who):
+    order = (conv_args or {}).get("order", "conv-norm-act")
+    if order != "conv-norm-act":
+        raise MetaEncError(f"{who}: conv order {order!r} (conv-norm-act is implemented)")
+
+
+def _convblock1d(cin, cout, norm_args=None, act_args=None, order="conv-norm-act", who="create_convblock1d"):
+    """create_convblock1d (layers/conv.py:65-103), order conv-norm-act: Conv1d k=1 (no bias where a norm follows), norm, act"""
+    _check_conv_args({"order": order}, who)
+    norm = _norm_1d(norm_args, cout, who)
+    mods = [nn.Conv1d(cin, cout, 1, bias=norm is None)]
+    if norm is not None:
+        mods.append(norm)
+    act = _act_1d(act_args, who)
+    if act is not None:
+        mods.append(act)
+    return nn.Sequential(*mods)
+
+
+def _w2d(conv: nn.Conv1d) -> torch.Tensor:
+    return conv.weight.reshape(conv.out_channels, conv.in_channels)
+
+
+def _lin(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [rows, K] W^T (+ b) on the exact-fp32 GEMM, the reduction zero-padded to a multiple of 8 where it is not one"""
+    K = x.shape[1]
+    if K % 8:
+        x = torch.nn.functional.pad(x, (0, 8 - K % 8))
+        w = torch.nn.functional.pad(w, (0, 8 - K % 8))
+    return linear(x.float(), w.contiguous(), b)
+
+
+def _post(blk: nn.Sequential, f: torch.Tensor) -> torch.Tensor:
+    """the norm / activation behind a conv block's Conv1d, on token-major rows"""
+    for mod in list(blk)[1:]:
+        if isinstance(mod, nn.BatchNorm1d):
+            f = _batch_norm_rows(mod, f)
+        elif isinstance(mod, nn.LayerNorm):
+            f = _LayerNormFn.apply(f, mod.weight, mod.bias, mod.eps)
+        elif isinstance(mod, nn.ReLU):
+            f = torch.relu(f)
+        elif isinstance(mod, nn.GELU):
+            f = torch.nn.functional.gelu(f)
+        else:
+            raise MetaEncError(f"conv block: {type(mod).__name__} is not implemented")
+    return f
+
+
+def _need_cuda(t: torch.Tensor, who: str):
+    if not t.is_cuda:
+        raise MetaEncError(f"{who}: CUDA tensors required (no CPU fallback)")
+
+
+class FeaturePropogation(nn.Module):
+    """openpoints FeaturePropogation (backbone/pointnext.py:173-226, the reference spelling), upsample branch:
+    convs(cat(f_skip, three_interpolation(p_dense, p_sparse, f_sparse))), or convs(interp) without a skip; convs are
+    create_convblock1d blocks (Conv1d k=1, BatchNorm1d, ReLU) with keys ``convs.{j}.{0|1}.*``.
+
+    The first conv never sees the concatenation: interpolation is linear, so with W = [W_a | W_b]
+    cat(f_skip, interp(f_sparse)) W^T = f_skip W_a^T + interp(f_sparse W_b^T); the W_b GEMM runs on the sparse points and
+    me_three_interpolate adds its result onto the skip GEMM's output in place."""
+
+    def __init__(self, mlp, upsample=True, norm_args={"norm": "bn1d"}, act_args={"act": "relu"}):
+        super().__init__()
+        if not upsample:
+            raise MetaEncError("FeaturePropogation: upsample=False (the PointNet++ global branch) is not implemented")
+        self.convs = nn.Sequential(*[_convblock1d(mlp[i], mlp[i + 1], norm_args=norm_args, act_args=act_args,
+                                                  who="FeaturePropogation") for i in range(len(mlp) - 1)])
+
+    def rows(self, p1: torch.Tensor, f1: Optional[torch.Tensor], p2: torch.Tensor, f2: torch.Tensor,
+             cloud: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """token-major core: dense points p1 [B, n, 3] with skip features f1 [B, n, Cs] (or None), sparse points p2 [B, m, 3] with
+        features f2 [B, m, Cin]; ``cloud`` [B, Cc] are per-cloud channels in front of the skip (the part decoder's class
+        branch).  Returns [B*n, C_out] fp32."""
+        _need_cuda(p1, "FeaturePropogation")
+        B, n, _ = p1.shape
+        m, Cin = f2.shape[1], f2.shape[2]
+        Cs = f1.shape[2] if f1 is not None else 0
+        Cc = cloud.shape[1] if cloud is not None else 0
+        conv = self.convs[0][0]
+        if conv.in_channels != Cc + Cs + Cin:
+            raise MetaEncError(f"FeaturePropogation: the first conv takes {conv.in_channels} channels, given {Cc} + {Cs} + {Cin}")
+        w = _w2d(conv)
+        idx, wt = three_nn_weights(p1, p2)
+        z = _lin(f2.reshape(B * m, Cin), w[:, Cc + Cs:])                         # the interpolated part, on the sparse rows
+        y = _lin(f1.reshape(B * n, Cs), w[:, Cc:Cc + Cs], conv.bias) if Cs else None
+        f = _interpolate_rows(z.view(B, m, -1), idx, wt, y)
+        if cloud is not None:                                                     # [B, C]: constant over the cloud
+            g = _lin(cloud, w[:, :Cc], conv.bias if y is None else None)
+            f = (f.view(B, n, -1) + g.unsqueeze(1)).view(B * n, -1)
+        elif y is None and conv.bias is not None:
+            f = f + conv.bias
+        f = _post(self.convs[0], f)
+        for blk in list(self.convs)[1:]:
+            f = _post(blk, _lin(f, _w2d(blk[0]), blk[0].bias))
+        return f
+
+    def forward(self, pf1, pf2=None):
+        if pf2 is None:
+            raise MetaEncError("FeaturePropogation: the global branch (pf2=None) needs upsample=False, which is not implemented")
+        (p1, f1), (p2, f2) = pf1, pf2
+        B, n = p1.shape[:2]
+        out = self.rows(p1, f1.transpose(1, 2) if f1 is not None else None, p2, f2.transpose(1, 2))
+        return out.view(B, n, -1).transpose(1, 2)
+
+
+def _cat_global(g: Optional[torch.Tensor], f: torch.Tensor) -> torch.Tensor:
+    """cat(broadcast(g [B, G]), f [B, N, C]) channel-first -> [B, G + C, N] (the reference's decoder output)"""
+    if g is None:
+        return f.transpose(1, 2)
+    return torch.cat((g.unsqueeze(2).expand(-1, -1, f.shape[1]), f.transpose(1, 2)), dim=1)
+
+
+class _ViTDecoderBase(nn.Module):
+    """what PointViTDecoder and PointViTPartDecoder (backbone/pointvit.py:177-393) share"""
+
+    def _build(self, encoder_channel_list, decoder_layers, n_decoder_stages, scale, channel_scaling, sampler, global_feat,
+               progressive_input, kwargs, cls_branch=None):
+        who = type(self).__name__
+        if str(sampler).lower() != "fps":
+            raise MetaEncError(f"{who}: sampler {sampler!r} (fps is implemented; random sampling is not)")
+        _check_conv_args(kwargs.get("conv_args"), who)
+        self.decoder_layers = decoder_layers
+        self.global_feat = global_feat.split(",") if global_feat is not None else None
+        num_global_feat = len(self.global_feat) if self.global_feat is not None else 0
+        self.in_channels = encoder_channel_list[-1]
+        self.scale = scale
+        self.n_decoder_stages = n_decoder_stages
+        if progressive_input:
+            skip_dim = [self.in_channels // 2 ** i for i in range(n_decoder_stages - 1, 0, -1)]
+        else:
+            skip_dim = [0 for _ in range(n_decoder_stages - 1)]
+        skip_channels = [encoder_channel_list[0]] + skip_dim
+        fp_channels = [self.in_channels * channel_scaling]
+        for _ in range(n_decoder_stages - 1):
+            fp_channels.insert(0, fp_channels[0] * channel_scaling)
+        if cls_branch is not None:                  # the part decoder's convc, registered before the decoder as in the reference
+            skip_channels[0] += cls_branch()
+        decoder = [[] for _ in range(n_decoder_stages)]
+        for i in range(-1, -n_decoder_stages - 1, -1):
+            mlp = [skip_channels[i] + self.in_channels] + [fp_channels[i]] * self.decoder_layers
+            decoder[i] = nn.Sequential(FeaturePropogation(mlp))
+            self.in_channels = fp_channels[i]
+        self.decoder = nn.Sequential(*decoder)
+        self.out_channels = fp_channels[-n_decoder_stages] * (num_global_feat + 1)
+
+    def _run(self, p, f, cloud=None):
+        """the shared forward on the caller's lists (mutated as the reference mutates them) -> (global [B, G*C] or None,
+        f_out [B, N, C] token-major)"""
+        who = type(self).__name__
+        _need_cuda(p[0], who)
+        if len(p) != self.n_decoder_stages + 1:     # the FPS resampling path: new point sets, no skip features
+            for i in range(self.n_decoder_stages - 1):
+                pos = p[i]
+                idx = furthest_point_sample(pos, pos.shape[1] // self.scale).long()
+                p.insert(1, torch.gather(pos, 1, idx.unsqueeze(-1).expand(-1, -1, 3)))
+                f.insert(1, None)
+        cur = f[-1].transpose(1, 2)                                          # [B, 1 + S, C] token-major
+        cls_token = cur[:, 0].float()
+        cur = cur[:, 1:]
+        f[-1] = cur.transpose(1, 2)
+        L = len(self.decoder)
+        for i in range(-1, -L - 1, -1):
+            skip = f[i - 1]
+            rows = self.decoder[i][0].rows(p[i - 1], skip.transpose(1, 2).float() if skip is not None else None, p[i],
+                                           cur.float(), cloud if i == -L else None)
+            cur = rows.view(p[i - 1].shape[0], p[i - 1].shape[1], -1)
+            f[i - 1] = cur.transpose(1, 2)
+        if self.global_feat is None:
+            return None, cur
+        gs = []
+        for token_type in self.global_feat:
+            if "cls" in token_type:
+                gs.append(cls_token)
+            elif "max" in token_type:
+                gs.append(pool_tokens(cur, "max"))
+            elif token_type in ("avg", "mean"):
+                gs.append(pool_tokens(cur, "mean"))
+        if not gs:
+            raise MetaEncError(f"{who}: global_feat {','.join(self.global_feat)!r} names none of cls / max / avg / mean")
+        return torch.cat(gs, dim=1), cur
+
+
+class PointViTDecoder(_ViTDecoderBase):
+    """openpoints PointViTDecoder (backbone/pointvit.py:177-263), the decoder of the S3DIS / ScanNet recipes: per stage a
+    FeaturePropogation from the coarser point set onto the finer one (keys ``decoder.{s}.0.convs.{j}.{0|1}.*``), then the
+    optional global features (cls token / max / avg over the points) in front of every point's.
+
+    forward(p, f) returns the reference's [B, C_out, N]; forward_split(p, f) returns (global [B, G*C] or None, f_out
+    [B, N, C] token-major) and with SegHead.forward_split skips the materialised concatenation.  three_nn, the interpolation
+    and every 1x1 convolution (exact-fp32 GEMM), LayerNorm and pooling run in libmetaenc.so; BatchNorm1d and ReLU are torch
+    glue.  fp32 throughout, autocast included."""
+
+    def __init__(self, encoder_channel_list, decoder_layers=2, n_decoder_stages=2, scale=4, channel_scaling=1, sampler="fps",
+                 global_feat=None, progressive_input=False, **kwargs):
+        super().__init__()
+        self._build(encoder_channel_list, decoder_layers, n_decoder_stages, scale, channel_scaling, sampler, global_feat,
+                    progressive_input, kwargs)
+
+    def forward_split(self, p, f):
+        return self._run(p, f)
+
+    def forward(self, p, f):
+        return _cat_global(*self.forward_split(p, f))
+
+
+class PointViTPartDecoder(_ViTDecoderBase):
+    """openpoints PointViTPartDecoder (backbone/pointvit.py:266-393), the ShapeNetPart decoder, cls_map 'pointnet2': the shape
+    class one-hot [B, 16] goes through ``convc`` (Conv1d 16 -> 64 with bias, then the recipe's activation) and joins the
+    skip features of the last stage.  The one-hot is constant over a cloud, so convc and its share of the last stage's first
+    conv run once per cloud and are broadcast.  Interfaces as PointViTDecoder, with cls_label [B, 1]."""
+
+    def __init__(self, encoder_channel_list, decoder_layers=2, n_decoder_stages=2, scale=4, channel_scaling=1, sampler="fps",
+                 global_feat=None, progressive_input=False, cls_map="pointnet2", num_classes=16, **kwargs):
+        super().__init__()
+        if cls_map != "pointnet2":
+            raise MetaEncError(f"PointViTPartDecoder: cls_map {cls_map!r} (pointnet2 is implemented; curvenet is not)")
+        self.cls_map, self.num_classes = cls_map, num_classes
+        act_args = kwargs.get("act_args", {"act": "relu"})
+
+        def cls_branch():
+            self.convc = nn.Sequential(_convblock1d(16, 64, norm_args=None, act_args=act_args, who="PointViTPartDecoder"))
+            return 64
+        self._build(encoder_channel_list, decoder_layers, n_decoder_stages, scale, channel_scaling, sampler, global_feat,
+                    progressive_input, kwargs, cls_branch)
+
+    def forward_split(self, p, f, cls_label):
+        _need_cuda(p[0], "PointViTPartDecoder")
+        B = p[0].shape[0]
+        one_hot = torch.zeros(B, self.num_classes, device=p[0].device).scatter_(1, cls_label.long().reshape(B, -1), 1)
+        blk = self.convc[0]
+        cloud = _post(blk, _lin(one_hot, _w2d(blk[0]), blk[0].bias))                  # [B, 64]: convc on every point alike
+        return self._run(p, f, cloud)
+
+    def forward(self, p, f, cls_label):
+        return _cat_global(*self.forward_split(p, f, cls_label))
+
+
+class SegHead(nn.Module):
+    """openpoints SegHead (segmentation/base_seg.py:92-149): optional global features (max / avg over the points) appended
+    to every point's, create_convblock1d blocks with Dropout between them, a final Conv1d with bias; keys
+    ``head.{0|2}.*``.  forward(end_points [B, C, N]) -> logits [B, num_classes, N].
+
+    forward_split(global, f) takes the decoder's split output instead of cat(broadcast(global), f): everything constant over
+    a cloud (the decoder's global features, and the head's own pooled ones) meets its share of the first conv once per
+    cloud, so only f [B, N, C] runs the per-point GEMM."""
+
+    def __init__(self, num_classes, in_channels, mlps=None, norm_args={"norm": "bn1d"}, act_args={"act": "relu"}, dropout=0.5,
+                 global_feat=None, **kwargs):
+        super().__init__()
+        _check_conv_args(kwargs.get("conv_args"), "SegHead")
+        if global_feat is not None:
+            self.global_feat = global_feat.split(",")
+            multiplier = len(self.global_feat) + 1
+        else:
+            self.global_feat = None
+            multiplier = 1
+        in_channels *= multiplier
+        if mlps is None:
+            mlps = [in_channels, in_channels] + [num_classes]
+        else:
+            mlps = [in_channels] + (list(mlps) if isinstance(mlps, (list, tuple)) else [mlps]) + [num_classes]
+        heads = []
+        for i in range(len(mlps) - 2):
+            heads.append(_convblock1d(mlps[i], mlps[i + 1], norm_args=norm_args, act_args=act_args, who="SegHead"))
+            if dropout:
+                heads.append(nn.Dropout(dropout))
+        heads.append(_convblock1d(mlps[-2], mlps[-1], act_args=None, who="SegHead"))
+        self.head = nn.Sequential(*heads)
+
+    def forward_split(self, global_feat: Optional[torch.Tensor], f: torch.Tensor) -> torch.Tensor:
+        """global [B, G] (or None) and token-major f [B, N, C] stand for end_points = cat(broadcast(global), f) -> logits
+        [B, num_classes, N]"""
+        _need_cuda(f, "SegHead")
+        B, N, C = f.shape
+        f = f.float().contiguous()
+        G = global_feat.shape[1] if global_feat is not None else 0
+        cloud = [global_feat.float()] if global_feat is not None else []
+        for feat_type in self.global_feat or []:
+            mode = "max" if "max" in feat_type else "mean" if feat_type in ("avg", "mean") else None
+            if mode is None:
+                continue
+            if global_feat is not None:
+                cloud.append(global_feat.float())                     # pooled over the points, a broadcast is itself
+            cloud.append(pool_tokens(f, mode))
+        pools = sum(1 for t in self.global_feat or [] if "max" in t or t in ("avg", "mean"))
+        conv = self.head[0][0]
+        if conv.in_channels != (G + C) * (1 + pools):
+            raise MetaEncError(f"SegHead: the first conv takes {conv.in_channels} channels, given {G} global + {C} per point")
+        w = _w2d(conv)
+        y = _lin(f.reshape(B * N, C), w[:, G:G + C], conv.bias)
+        if cloud:
+            g = _lin(torch.cat(cloud, dim=1), torch.cat([w[:, :G], w[:, G + C:]], dim=1))
+            y = (y.view(B, N, -1) + g.unsqueeze(1)).view(B * N, -1)
+        y = _post(self.head[0], y)
+        for mod in list(self.head)[1:]:
+            y = mod(y) if isinstance(mod, nn.Dropout) else _post(mod, _lin(y, _w2d(mod[0]), mod[0].bias))
+        return y.view(B, N, -1).transpose(1, 2).contiguous()
+
+    def forward(self, end_points: torch.Tensor) -> torch.Tensor:
+        return self.forward_split(None, end_points.transpose(1, 2))
