@@ -17,10 +17,7 @@
 #include <math.h>
 #include <stdlib.h>
 
-// attention_tiny.hip: N <= 64, one wave per (batch, head)   (-DME_TINY_ATTN=0: A/B arm without it, tools/runs/r5_run_tiny.sh)
-#ifndef ME_TINY_ATTN
-#define ME_TINY_ATTN 1
-#endif
+// attention_tiny.hip: N <= 64, one wave per (batch, head)
 bool attn_tiny_ok(int dtype, int64_t ld_qkv, int64_t ld_out, int B, int N, int H, int hd);
 int launch_attn_tiny_fwd(int dtype, const void* qkv, int64_t ld, void* out, int64_t ldo, float* lse, int B, int N, int H, int hd, float scale,
                          hipStream_t stream);
@@ -912,9 +909,7 @@ template <int HD> struct RCfg {
 // Waves 14 and 15 are the loaders (paced LDS-DMA of the next item's K and V into the other ring half), other waves >= ceil(N / 16)
 // only keep the barrier.
 constexpr int R16_THREADS = 1024;
-#ifndef ME_R16_SLEEP
-#define ME_R16_SLEEP 1      // loader pacing: s_sleep units (64 clocks) behind every DMA piece
-#endif
+constexpr int R16_SLEEP = 1;        // loader pacing: s_sleep units (64 clocks) behind every DMA piece
 // slot of chunk c in row r: c ^ r16_swz(r).  HD = 64: the b128 operand read has lanes {0-3, 12-15} on rows r, chunk c and lanes
 // {20-27} on rows 4-11, chunk c + 1 in one LDS cycle, the transposing read 8 consecutive rows x one aligned chunk pair: row bits
 // 1..2 -> slot bits 1..2 separates both.  HD = 32 (four rows per 256-byte bank row): per 4-row block the values 0, 2, 3, 1.
@@ -967,7 +962,7 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_ring16_kernel(const bf16
 #pragma unroll
             for (int i = 0; i < NRI; ++i) {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, (lds_dma_t*)(half + which * arr_bytes + i * 1024), 16, dma_voff + i * dma_gstep, 0, 0, 0);
-                if (paced && ME_R16_SLEEP) __builtin_amdgcn_s_sleep(ME_R16_SLEEP);
+                if (paced && R16_SLEEP) __builtin_amdgcn_s_sleep(R16_SLEEP);
             }
         };
         int it = blockIdx.x, cur = 0;
@@ -1653,32 +1648,17 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_stream16_kernel(const bf
 // a softmax probability from its log2-domain argument: v_exp_f32 with the clamp output modifier (hipcc folds the med3 into it)
 __device__ __forceinline__ float r16_p(float arg) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(arg), 0.f, 1.f); }
 
-// four probabilities and their dS / scale (the 32-key dK / dV kernel):  pe = exp2(s * sl - l2),  ds = pe * (dp - d).  ME_R16_PK = 1 (A/B arm, OFF): the
-// same on PAIRS -- v_pk_fma_f32 for the argument, v_pk_mul_f32 + v_pk_fma_f32 for dS, 3.5 instead of 5 VALU instructions per score (and, tried with
+// four probabilities and their dS / scale (the 32-key dK / dV kernel):  pe = exp2(s * sl - l2),  ds = pe * (dp - d).  The same on
+// PAIRS (measured and removed) -- v_pk_fma_f32 for the argument, v_pk_mul_f32 + v_pk_fma_f32 for dS, 3.5 instead of 5 VALU instructions per score (and, tried with
 // it, the same form in every other backward kernel and v_pk_fma_f32 / v_pk_add_f32 in the forward kernels' exp2 + row sum) -- measured SLOWER everywhere (same box,
 // profiles/r06_attn_bwd_stream32.txt: N = 197 forward 68.7 -> 74.7 us, backward 212.9 -> 222.7; N = 1568 forward 477 -> 504, backward
 // 1 218 -> 1 247): the packed fp32 operations do not issue at the rate of two scalar ones here, and assembling the pairs costs moves.
-#ifndef ME_R16_PK
-#define ME_R16_PK 0
-#endif
 __device__ __forceinline__ void r16_pds4(const f32x4& s, const f32x4& dp, float sl, const f32x4& l2, const f32x4& d, f32x4& pe, f32x4& ds) {
-#if ME_R16_PK
-    const f32x2 slv = {sl, sl};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const f32x2 arg = f32x2{s[2 * h], s[2 * h + 1]} * slv - f32x2{l2[2 * h], l2[2 * h + 1]};
-        const f32x2 p = {r16_p(arg[0]), r16_p(arg[1])};
-        const f32x2 x = p * f32x2{dp[2 * h], dp[2 * h + 1]} - p * f32x2{d[2 * h], d[2 * h + 1]};
-        pe[2 * h] = p[0]; pe[2 * h + 1] = p[1];
-        ds[2 * h] = x[0]; ds[2 * h + 1] = x[1];
-    }
-#else
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         pe[e] = r16_p(s[e] * sl - l2[e]);
         ds[e] = pe[e] * (dp[e] - d[e]);
     }
-#endif
 }
 
 // -----------------------------------------------------------------------------------------------------
@@ -1989,13 +1969,7 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_ring16_kernel(const bf16
 // never stored.  Replaces the 8-wave / 32-row chunk kernels (same box, profiles/r04_attn_bwd_stream16_vs_chunk.txt: N = 1568 1 442 vs
 // 1 520 us, 1000: 657 vs 711, 592: 409 vs 477, 520: 634 vs 797; 3136: 2 672 vs 2 640).
 // Round 6: where a key block fills seven 32-key waves the second phase runs as attn_bwd_dkdv_stream32_kernel (further down; -15 % on that phase).
-#ifndef ME_ST_BWD_MINN
-#define ME_ST_BWD_MINN 513
-#endif
-#ifndef ME_ST_BWD_ROWS
-#define ME_ST_BWD_ROWS 32                      // keys per compute wave of the streaming dK / dV kernel: 16 (16 waves) or 32 (8 waves)  -- A/B arm
-#endif
-constexpr int ST_BWD_MINN = ME_ST_BWD_MINN;
+constexpr int ST_BWD_MINN = 513;
 
 // loader waves of the streaming backward kernels: array 0 / 1 of a chunk from (a0, ld0) / (a1, ld1); FL: 128 floats of f0 / f1 per chunk.
 // NW waves per workgroup, the last NL of them load (the others past the compute waves keep the barrier count): NL = 4 (two waves per array),
@@ -2368,9 +2342,6 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_dkdv_stream16_kernel(con
 // the steps staged like here: 573 vs 567 us) does
 // not gain -- 12 MFMAs per 12 KB there, and it is not the LDS that paces it -- and stays on 16-row waves.
 constexpr int ST32_THREADS = 512;
-#ifndef ME_ST32_PIPE
-#define ME_ST32_PIPE 2                          // (A/B arms: 1 = the same source order without the scheduling barriers)
-#endif
 
 template <int HD>
 __global__ __launch_bounds__(ST32_THREADS) void attn_bwd_dkdv_stream32_kernel(const bf16_t* __restrict__ qkv, int64_t ld,
@@ -2509,7 +2480,7 @@ __global__ __launch_bounds__(ST32_THREADS) void attn_bwd_dkdv_stream32_kernel(co
                 // softmax arithmetic (under both) -> transposed Q fragments -> dV products (under which those land) -> dK products
                 f32x4 s2[2][2], dp2[2][2];
                 if (qq + 1 < ST_KC / 32) sdp(qq + 1, s2, dp2);
-                if (ME_ST32_PIPE == 2) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
                 bf16x8 td[NDT], tq[NDT];
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt) td[dt] = trread(Db, qq, dt);
@@ -2519,7 +2490,7 @@ __global__ __launch_bounds__(ST32_THREADS) void attn_bwd_dkdv_stream32_kernel(co
                     L[tt] = *reinterpret_cast<const f32x4*>(lsb + 16 * (2 * qq + tt) + 4 * g);
                     D[tt] = *reinterpret_cast<const f32x4*>(deb + 16 * (2 * qq + tt) + 4 * g);
                 }
-                if (ME_ST32_PIPE == 2) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
                 bf16x8 pb[2], dsb[2];
 #pragma unroll
                 for (int tt = 0; tt < 2; ++tt) {
@@ -2532,10 +2503,10 @@ __global__ __launch_bounds__(ST32_THREADS) void attn_bwd_dkdv_stream32_kernel(co
                         for (int e = 0; e < 4; ++e) { pb[r][4 * tt + e] = (bf16_t)pe[e]; dsb[r][4 * tt + e] = (bf16_t)ds[e]; }
                     }
                 }
-                if (ME_ST32_PIPE == 2) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt) tq[dt] = trread(Qb, qq, dt);      // (lands under the dV products)
-                if (ME_ST32_PIPE == 2) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
@@ -2544,7 +2515,7 @@ __global__ __launch_bounds__(ST32_THREADS) void attn_bwd_dkdv_stream32_kernel(co
                 for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
                     for (int r = 0; r < 2; ++r) dk[r][dt] = mma16(tq[dt], dsb[r], dk[r][dt]);
-                if (ME_ST32_PIPE == 2) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
                 if (qq + 1 < ST_KC / 32) {
 #pragma unroll
                     for (int tt = 0; tt < 2; ++tt)
@@ -3170,7 +3141,7 @@ int launch_bwd_stream16(const void* qkv, int64_t ld, const void* out, int64_t ld
     ME_CHECK_LAUNCH("me_attention_bwd(dq stream16)");
     // dK / dV: 32-key waves when the key blocks fill seven of them (see attn_bwd_dkdv_stream32_kernel)
     const int KB32 = (RBk + 31) / 32 * 32;
-    if (ME_ST_BWD_ROWS == 32 && KB32 == 224) {
+    if (KB32 == 224) {
         hipLaunchKernelGGL((attn_bwd_dkdv_stream32_kernel<HD>), dim3(grid), dim3(ST32_THREADS), smem3, stream,
                            reinterpret_cast<const bf16_t*>(qkv), ld, reinterpret_cast<const bf16_t*>(dout), lddo, lse, delta,
                            reinterpret_cast<bf16_t*>(dqkv), lddq, N, H, hd, scale, KB32, nrb, (int)items);
@@ -3348,7 +3319,7 @@ extern "C" int me_attention_fwd(const void* qkv, int64_t ld_qkv, void* out, int6
     ME_CHECK_ARG(ld_out % 4 == 0, "me_attention_fwd: ld_out must be a multiple of 4");
     ME_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "me_attention_fwd: p_drop must be in [0, 1)");
     // very short sequences (the Tabular / Graph recipes): one wave per (batch, head), attention_tiny.hip
-    if (ME_TINY_ATTN && p_drop == 0.f && N <= SM_MINN && attn_tiny_ok(dtype, ld_qkv, ld_out, B, N, H, head_dim))
+    if (p_drop == 0.f && N <= SM_MINN && attn_tiny_ok(dtype, ld_qkv, ld_out, B, N, H, head_dim))
         return launch_attn_tiny_fwd(dtype, qkv, ld_qkv, out, ld_out, lse, B, N, H, head_dim, scale, stream);
     if (p_drop == 0.f && dtype == ME_BF16 && head_dim <= 64 && N > SM_MINN && N <= SM_MAXN) {
         if (N <= RS_MAXN && (int64_t)N * ld_qkv * 2 < (int64_t)0x7e000000) {
@@ -3386,7 +3357,7 @@ extern "C" int me_attention_bwd(const void* qkv, int64_t ld_qkv, const void* out
     const int E = dtype == ME_BF16 ? 8 : 4;
     ME_CHECK_ARG(ld_dout % E == 0 && ld_dqkv % 4 == 0, "me_attention_bwd: bad strides");
     ME_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "me_attention_bwd: p_drop must be in [0, 1)");
-    if (ME_TINY_ATTN && p_drop == 0.f && N <= SM_MINN && attn_tiny_ok(dtype, ld_qkv, ld_out, B, N, H, head_dim) && ld_dout % E == 0 && ld_dqkv % E == 0)
+    if (p_drop == 0.f && N <= SM_MINN && attn_tiny_ok(dtype, ld_qkv, ld_out, B, N, H, head_dim) && ld_dout % E == 0 && ld_dqkv % E == 0)
         return launch_attn_tiny_bwd(dtype, qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, delta, dqkv, ld_dqkv, B, N, H, head_dim, scale, stream);
     if (p_drop == 0.f && dtype == ME_BF16 && head_dim <= 64 && N > SM_MINN && N <= SM_MAXN && ld_out % 8 == 0) {
         if (N <= RS_MAXN && (int64_t)N * ld_qkv * 2 < (int64_t)0x7e000000 && (int64_t)N * ld_dout * 2 < (int64_t)0x7e000000) {

@@ -25,9 +25,6 @@
 // 32 exponentials per lane.
 #include "common.h"
 
-#ifndef F8_FAST_EXP
-#define F8_FAST_EXP 0
-#endif
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
@@ -247,33 +244,6 @@ __global__ __launch_bounds__(256) void attn_fwd_fp8_kernel(const uint8_t* __rest
         }
         const float off = 7.0f - m;                                      // 2^7 = F8_PSCALE
         i32x8 pop;
-#if F8_FAST_EXP
-        // The exponential as a BIT PATTERN: 2^x ~ as_float((x + 127) * 2^23) -- exponent = floor(x), mantissa = frac(x), i.e. 2^f taken
-        // as 1 + f (0 .. 6.1 % high; the common part cancels in the normalisation, and e4m3 keeps three mantissa bits = 6.25 % steps
-        // anyway).  One packed FMA per two scores + one full-rate convert per score instead of an FMA and a transcendental each
-        // (tools/probe_valu: 1.4 + 1.9 against 1.9 + 5.3 clocks of a SIMD's VALU); the conversion saturates at 0 for x < -127
-        // (masked keys) and cannot overflow (x <= 7).  The row sum adds the same values the MFMA is given, before their rounding.
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        const f32x2 c2b = {c2 * 8388608.f, c2 * 8388608.f}, offb = {(off + 127.f) * 8388608.f, (off + 127.f) * 8388608.f};
-        f32x2 psv = {0.f, 0.f};
-        auto bits = [](float t) { unsigned r; asm("v_cvt_u32_f32 %0, %1" : "=v"(r) : "v"(t)); return __uint_as_float(r); };
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            f32x2 pa[2], pc[2];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const f32x2 sa = {s0[4 * w + 2 * e], s0[4 * w + 2 * e + 1]}, sc = {s1[4 * w + 2 * e], s1[4 * w + 2 * e + 1]};
-                const f32x2 ta = __builtin_elementwise_fma(sa, c2b, offb), tc = __builtin_elementwise_fma(sc, c2b, offb);
-                pa[e] = f32x2{bits(ta[0]), bits(ta[1])};
-                pc[e] = f32x2{bits(tc[0]), bits(tc[1])};
-                psv += pa[e];
-                psv += pc[e];
-            }
-            pop[w] = (int)pack4_fp8(pa[0][0], pa[0][1], pa[1][0], pa[1][1]);
-            pop[4 + w] = (int)pack4_fp8(pc[0][0], pc[0][1], pc[1][0], pc[1][1]);
-        }
-        lsum += psv[0] + psv[1];
-#else
         float ps = 0.f;
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
@@ -288,7 +258,6 @@ __global__ __launch_bounds__(256) void attn_fwd_fp8_kernel(const uint8_t* __rest
             pop[4 + w] = (int)pack4_fp8(pb[0], pb[1], pb[2], pb[3]);
         }
         lsum += ps;                                                      // (in units of 2^-7, like the stored probabilities)
-#endif
         // O^T[d][query] += V^T[d][keys] P^T[keys][query]
         o0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(v0, pop, o0, 0, 0, 0, unit, 0, unit);
         o1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(v1, pop, o1, 0, 0, 0, unit, 0, unit);

@@ -428,25 +428,19 @@ struct GemmPlan {
 // CUs a communication library's kernels hold while gradient buckets are reduced (me_gemm_reserve_cus; me_comm_init / _destroy set it)
 std::atomic<int> g_reserved_cus{0};
 
-#ifndef ME_SMALL_SPLIT_DEN
-#define ME_SMALL_SPLIT_DEN 2                     // whole-problem split-K when tiles <= slots / this.  Measured on the reference's shapes
+constexpr int kSmallSplitDen = 2;                // whole-problem split-K when tiles <= slots / this.  Measured on the reference's shapes
                                                  // (profiles/r04_small_split_ab.txt): never = +7..18 % per forward at B = 32..256 x N = 16..197,
                                                  // B = 1 0.92 -> 1.43 ms; / 3 -> / 2: M = 8 224 fwd + dX 6.9 -> 6.74 ms, the rest unchanged
-#endif
-#ifndef ME_SMALL_SPLIT_LONGK
-#define ME_SMALL_SPLIT_LONGK 192
-#endif
+constexpr int kSmallSplitLongK = 192;
 GemmPlan plan_gemm(const me_gemm_desc* d, const GemmParams& p, bool allow_sk = true) {
     GemmPlan pl{0, 0, 128, 0, 1, 0, 0, 0, 1, 0};
-    const GemmDev dev = gemm_dev();
-    const int ffam = dev.family, fbn = dev.bn;
-    if (d->ab_dtype != ME_BF16 || ffam == 0) return pl;
-    // default (measured on the encoder's shapes, tools/gemm_dev): NT with at least half a chip of 256x256 tiles -> g3
+    if (d->ab_dtype != ME_BF16) return pl;
+    // measured on the encoder's shapes: NT with at least half a chip of 256x256 tiles -> g3
     // (K-tile 64, 4-phase ping-pong: 860-1000 TF on the Base shapes against 500-780 for the K-step-32 kernels); fewer
     // tiles or K not a multiple of 128 -> the K-step-32 kernels with their split-K forms; TN (wgrad) -> g2b.
-    int fam = ffam > 0 ? ffam : 2;
-    if (ffam < 0 && d->op == ME_GEMM_TN && d->M >= 256 && d->N >= 256 && d->K >= 4096) fam = 4;      // wgrad: g3 (950 vs 640 TF)
-    if (ffam < 0 && d->op == ME_GEMM_NT && d->M >= 256 && d->N >= 256) {
+    int fam = 2;
+    if (d->op == ME_GEMM_TN && d->M >= 256 && d->N >= 256 && d->K >= 4096) fam = 4;      // wgrad: g3 (950 vs 640 TF)
+    if (d->op == ME_GEMM_NT && d->M >= 256 && d->N >= 256) {
         const int64_t t256 = ((d->M + 255) / 256) * ((d->N + 255) / 256);
         fam = (t256 >= 128 && g3_supported(p, d->op)) ? 4 : ((d->N <= 768 && d->K <= 1024) ? 2 : 3);
     }
@@ -455,17 +449,16 @@ GemmPlan plan_gemm(const me_gemm_desc* d, const GemmParams& p, bool allow_sk = t
     // (the g3 wgrad kernel takes any reduction length: rows past K read zeros through its descriptors -- a ragged token count,
     //  B x N not a multiple of 32, no longer sends the weight gradients of a whole Block to the generic kernel)
     if (!(fam == 4 && d->op == ME_GEMM_TN) && !g2b_supported(p, d->op)) return pl;
-    if (ffam < 0 && (d->M < 128 || d->N < 128)) return pl;       // tiny problems: g128 is enough
+    if (d->M < 128 || d->N < 128) return pl;       // tiny problems: g128 is enough
     pl.family = fam;
     pl.bm = fam == 2 ? 128 : 256;
-    if (kMeDev && fam == 2 && fbn == 64 && d->op == ME_GEMM_NT) pl.bm = 64;      // dev A/B: the 64-row small-M form
     // Small / mid-size NT problems (fewer than half a chip of 256 x 256 tiles: the reference's own batches, B = 32 x 96 .. 257
     // tokens, and B = 1 .. 32 inference): pick the TILE so that the launch has enough workgroups for the chip WITHOUT a K split --
     // the largest of 128 x 256 / 128 x 128 / 64 x 128 that still gives >= 140 tiles, else the smallest.  Measured on M = 197 ..
     // 6 304 (profiles/r05_small_gemm_plans.txt): 1.2 .. 4x faster per launch than the round-4 plans (256-wide tiles + whole-problem
     // split-K + fold), e.g. M = 3 072: qkv 36 -> 19 us, proj 23 -> 11 us, fc2 41 -> 31 us; M = 197: fc1 41 -> 10 us.
     bool small_nt = false;
-    if (ffam < 0 && fam != 4 && d->op == ME_GEMM_NT && d->N % 128 == 0) {
+    if (fam != 4 && d->op == ME_GEMM_NT && d->N % 128 == 0) {
         fam = 2; pl.family = 2; small_nt = true;
         const int64_t tm128 = (d->M + 127) / 128, tm64 = (d->M + 63) / 64;
         const int64_t c256 = tm128 * ((d->N + 255) / 256), c128 = tm128 * (d->N / 128), c64 = tm64 * (d->N / 128);
@@ -520,11 +513,8 @@ GemmPlan plan_gemm(const me_gemm_desc* d, const GemmParams& p, bool allow_sk = t
         pl.ws_bytes = (size_t)slabs * (size_t)g3_tn_slab_stride(d->M, d->N) * sizeof(float);
         if (d->colsum_a)                  // partial column sums of A: one [M] row per (split, N-tile) / per part of the tn = 0 tiles
             pl.ws_bytes += (size_t)slabs * (size_t)((d->N + 255) / 256) * (size_t)d->M * sizeof(float);
-#if G3_TN_FOLD
-        pl.ws_bytes += 256 + (size_t)((d->M + 255) / 256) * sizeof(unsigned);      // tile-row counters of the in-kernel fold (behind the rest, 256-byte aligned)
-#endif
     } else if (d->op == ME_GEMM_TN) {
-        pl.bn = fbn ? fbn : ((d->N % 256 == 0 || d->N > 512) ? 256 : 128);
+        pl.bn = (d->N % 256 == 0 || d->N > 512) ? 256 : 128;
         const int64_t tiles = pl.bn == 256 ? t256 : t128;
         int s = (int)(SLOTS / tiles);
         if (s < 1) s = 1;
@@ -539,7 +529,6 @@ GemmPlan plan_gemm(const me_gemm_desc* d, const GemmParams& p, bool allow_sk = t
         }
     } else {
         if (fam >= 3) pl.bn = 256;
-        else if (fbn) pl.bn = fbn == 64 ? 128 : fbn;
         else if (small_nt) {}                                    // (chosen above)
         else pl.bn = d->N > 128 ? 256 : 128;                     // measured: g2b_256 beats g2b_128 on every encoder shape
         pl.ksteps_per_split = nk;
@@ -555,8 +544,8 @@ GemmPlan plan_gemm(const me_gemm_desc* d, const GemmParams& p, bool allow_sk = t
             const int nkt = (int)(d->K / 64);
             // (not for the shapes the resident kernel takes: with its cheap tile seams the split's slabs + fold cost more
             // than the idle CUs of the last round -- measured 230 vs 241 us on fc2 forward, 170 vs 185 us on qkv dgrad)
-            const bool resident = d->c_dtype == ME_BF16 && d->alpha == 1.0f && dev.g3_persistent == 1;
-            if (!resident && d->N <= 1024 && d->K >= 2048 && dev.tail_split && R4 >= 1 && rem4 * 20 >= SL && rem4 * 10 <= SL * 6 && d->res_row_mod == 0 &&
+            const bool resident = d->c_dtype == ME_BF16 && d->alpha == 1.0f;
+            if (!resident && d->N <= 1024 && d->K >= 2048 && R4 >= 1 && rem4 * 20 >= SL && rem4 * 10 <= SL * 6 && d->res_row_mod == 0 &&
                 d->out_group_rows == 0) {
                 const int64_t m_main = (R4 * SL) / tn_;
                 const int64_t tail_tiles = (tm - m_main) * tn_;
@@ -571,11 +560,6 @@ GemmPlan plan_gemm(const me_gemm_desc* d, const GemmParams& p, bool allow_sk = t
                     else pl.tail_rows = 0;
                 }
             }
-#ifdef ME_DEV
-            // dev build: the persistent stream-K form (its scratch = one fp32 tile per CU)
-            const int64_t tiles = tm * ((d->N + 255) / 256);
-            if (tiles >= 128 && dev.g3_persistent == 2) { pl.ws_bytes = g3_workspace_bytes(); pl.tail_rows = 0; }
-#endif
             return pl;
         }
         // Tile quantisation: T tiles on SLOTS co-resident workgroups take ceil(T / SLOTS) rounds; the encoder's N = 768
@@ -587,7 +571,7 @@ GemmPlan plan_gemm(const me_gemm_desc* d, const GemmParams& p, bool allow_sk = t
         // K = 768 (slices too short) -- hence the fam == 3 / N <= 1024 gate.
         const int64_t tn_ = (d->N + pl.bn - 1) / pl.bn, tiles = tm * tn_;
         const int64_t R = tiles / SLOTS, rem = tiles - R * SLOTS;
-        if (fam == 3 && d->N <= 1024 && dev.tail_split && R >= 1 && rem * 20 >= SLOTS && rem * 10 <= SLOTS * 6 &&
+        if (fam == 3 && d->N <= 1024 && R >= 1 && rem * 20 >= SLOTS && rem * 10 <= SLOTS * 6 &&
             d->res_row_mod == 0 && d->out_group_rows == 0 && d->M % pl.bm == 0) {
             const int64_t m_main = (R * SLOTS) / tn_;
             const int64_t tail_tiles = (tm - m_main) * tn_;
@@ -605,9 +589,9 @@ GemmPlan plan_gemm(const me_gemm_desc* d, const GemmParams& p, bool allow_sk = t
         // idle.  The WHOLE problem then runs split over the reduction (same slabs + fold as the tail split, m_main = 0).
         // (with the tile chosen by count -- small_nt -- a K split pays only for long reductions on a handful of tiles: B = 1 fc2 / dgrads)
         // ... or a very long one on up to half the slots: K >= 6 144 only occurs as the three-plane (ME_BF16X3) form of fc2 / the fc1 dgrad,
-        // 144 tiles x 288 K-steps at the reference's M = 3 072 (ME_SMALL_SPLIT_LONGK K-steps of 32; measured below)
-        if (dev.tail_split && pl.tail_rows == 0 && tiles * ME_SMALL_SPLIT_DEN <= SLOTS && nk >= (small_nt ? 64 : 16) &&
-            (!small_nt || tiles <= 96 || nk >= ME_SMALL_SPLIT_LONGK)) {
+        // 144 tiles x 288 K-steps at the reference's M = 3 072 (kSmallSplitLongK K-steps of 32; measured below)
+        if (pl.tail_rows == 0 && tiles * kSmallSplitDen <= SLOTS && nk >= (small_nt ? 64 : 16) &&
+            (!small_nt || tiles <= 96 || nk >= kSmallSplitLongK)) {
             int s = (int)(SLOTS / tiles);
             while (s > 1 && nk / s < 8) --s;
             if (s >= 2) {
@@ -683,10 +667,8 @@ int fill_params(const me_gemm_desc* d, GemmParams& p) {
     ME_CHECK_ARG(!d->row_stats || (d->op == ME_GEMM_NT && d->residual && (uintptr_t)d->row_stats % 8 == 0),
                  "me_gemm: row_stats goes with ME_GEMM_NT and a residual operand (8-byte aligned)");
     p.row_stats = d->row_stats;
-    p.tn_colsum_out = nullptr;
-    p.g3_full_tiles = 0; p.g3_split = 0; p.g3_ktp = 0; p.g3_slabs = nullptr; p.slab_stride = 0; p.g3_tickets = nullptr; p.g3_half = 0; p.g3_colgroups = 1;
+    p.g3_full_tiles = 0; p.g3_split = 0; p.g3_ktp = 0; p.g3_slabs = nullptr; p.slab_stride = 0; p.g3_tickets = nullptr; p.g3_half = 0;
     if (d->colsum_a) ME_CHECK_ARG(d->op == ME_GEMM_TN, "me_gemm: colsum_a is defined for ME_GEMM_TN only");
-    p.debug = gemm_dev().debug;
     p.tiles_m = (int)((d->M + BM - 1) / BM);
     p.tiles_n = (int)((d->N + BN - 1) / BN);
     ME_CHECK_ARG((int64_t)p.tiles_m * p.tiles_n < (1ll << 31), "me_gemm: too many tiles");
@@ -773,7 +755,7 @@ int gemm_impl(const me_gemm_desc* d, hipStream_t stream, int* plan_out, TnLaunch
     int rc = fill_params(d, p);
     if (rc) return rc;
     GemmPlan pl = plan_gemm(d, p, tn_launch == nullptr);      // (the custom wgrad launchers -- patch embed, three planes -- walk uniform splits)
-    if (tn_launch && !(pl.family == 4 && d->op == ME_GEMM_TN && !G3_TN_FOLD)) return ME_ERR_UNSUPPORTED;
+    if (tn_launch && !(pl.family == 4 && d->op == ME_GEMM_TN)) return ME_ERR_UNSUPPORTED;
     {   // me_gemm_profile_rec.plan
         const bool have_ws = pl.ws_bytes && d->workspace && (size_t)d->workspace_bytes >= pl.ws_bytes;
         const int parts = pl.split_k > 1 ? pl.split_k : (pl.tail_rows > 0 ? pl.tail_split : 1);
@@ -805,22 +787,6 @@ int gemm_impl(const me_gemm_desc* d, hipStream_t stream, int* plan_out, TnLaunch
             ps.ksteps_per_split = pl.ksteps_per_split;
             ps.slab_stride = g3_tn_slab_stride(d->M, d->N);
             if (d->colsum_a) ps.colsum_ws = reinterpret_cast<float*>(d->workspace) + (size_t)pl.split_k * (size_t)ps.slab_stride;
-#if G3_TN_FOLD
-            if (g3_tn_fold_ok(p, pl.split_k)) {
-                // the fold inside the launch: the kernel writes C itself (gemm3.hip, gemm_g3tn_kernel<true>)
-                GemmParams pf = p;
-                pf.split_k = pl.split_k;
-                pf.ksteps_per_split = pl.ksteps_per_split;
-                pf.slab_stride = ps.slab_stride;
-                pf.g3_slabs = reinterpret_cast<float*>(d->workspace);
-                pf.colsum_ws = ps.colsum_ws;
-                pf.tn_colsum_out = d->colsum_a;
-                const size_t used = (size_t)pl.split_k * (size_t)ps.slab_stride * sizeof(float) +
-                                    (d->colsum_a ? (size_t)pl.split_k * (size_t)p.tiles_n * (size_t)d->M * sizeof(float) : 0);
-                pf.g3_tickets = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(d->workspace) + ((used + 255) & ~(size_t)255));
-                return launch_g3_tn_fold(pf, stream);
-            }
-#endif
             if (pl.sk_wgs) {
                 ps.sk_wgs = pl.sk_wgs; ps.sk_upt = pl.sk_upt; ps.sk_levels = pl.sk_levels; ps.sk_l1 = pl.sk_l1;
                 rc = launch_g3_tn_sk(ps, stream);
@@ -850,7 +816,7 @@ int gemm_impl(const me_gemm_desc* d, hipStream_t stream, int* plan_out, TnLaunch
                 p.g3_split = pl.tail_split;
                 p.g3_ktp = pl.tail_ksteps;
                 p.g3_slabs = reinterpret_cast<float*>(d->workspace);
-                rc = launch_g3(p, pick_epi_ex(p), nullptr, stream);
+                rc = launch_g3(p, pick_epi_ex(p), stream);
                 if (rc) return rc;
                 GemmParams pt = p;                               // the fold sees the tail rows as its own problem
                 pt.M = pl.tail_rows;
@@ -868,12 +834,7 @@ int gemm_impl(const me_gemm_desc* d, hipStream_t stream, int* plan_out, TnLaunch
                 ME_CHECK_LAUNCH("me_gemm(g3 tail fold)");
                 return ME_OK;
             }
-#ifdef ME_DEV
-            void* ws = (pl.tail_rows == 0 && have_ws) ? d->workspace : nullptr;
-#else
-            void* ws = nullptr;
-#endif
-            return launch_g3(p, pick_epi_ex(p), ws, stream);
+            return launch_g3(p, pick_epi_ex(p), stream);
         }
         auto run = [&](const GemmParams& q) { return launch_g2b(q, d->op, pl.bm, pl.bn, stream); };
         p.tiles_m = (int)((d->M + pl.bm - 1) / pl.bm);
@@ -945,5 +906,5 @@ int gemm_tn_with_launcher(const me_gemm_desc* d, hipStream_t stream, int (*launc
 int gemm_tn_is_g3(const me_gemm_desc* d) {
     GemmParams p;
     if (!d || d->op != ME_GEMM_TN || fill_params(d, p) != ME_OK) return 0;
-    return (plan_gemm(d, p).family == 4 && !G3_TN_FOLD) ? 1 : 0;
+    return plan_gemm(d, p).family == 4 ? 1 : 0;
 }

@@ -18,7 +18,7 @@
 
 namespace {
 
-// K-step schedule (measured best of three, tools/gemm_bench.py): read the substep-0 fragments, issue the DMA while they
+// K-step schedule (measured best of three): read the substep-0 fragments, issue the DMA while they
 // fly, prefetch the substep-1 fragments, then all 16 MFMAs.  (s_setprio around the MFMAs measured -3 %.)
 //
 // EPI selects a specialised epilogue so that the common cases are small straight-line code:
@@ -216,19 +216,6 @@ __global__ __launch_bounds__((BM == 64 ? 256 : BM * 2)) __attribute__((amdgpu_wa
         if (m < p.M) p.colsum_ws[((int64_t)blockIdx.y * p.tiles_n + tn) * p.M + m] = cs[0];
     }
     // ---- epilogue: accumulators -> per-wave LDS patch -> row-contiguous 16-byte accesses
-#ifdef ME_DEV
-    if (p.debug & 1) {                                    // dev: K-loop only
-        float keep = 0.f;
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < G::NI; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) keep += acc[i][j][e];
-        if (keep == 1.2345e-30f) reinterpret_cast<float*>(p.C)[0] = keep;
-        return;
-    }
-#endif
     // ---- epilogue.  A lane owns one output ROW and scattered 4-column quads (MFMA layout); stored directly that is
     // 16-byte fragments of 32 different lines per instruction.  Each wave therefore transposes 32-row slabs of its
     // accumulators through its own LDS patch (pitch padded by 16 B: conflict-free 16-byte accesses) and re-reads them

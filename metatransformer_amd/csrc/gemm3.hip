@@ -33,29 +33,14 @@
 //        >= 2 barriers earlier for both wave rows).  B-X is read in phase i itself: its four reads are issued first
 //        and retired with lgkmcnt(8) before that phase's first barrier, which the issuing wave row passes later.
 // The shared device code -- state, DMA issue, the 4-phase K-tile, the LDS-free epilogue -- lives in gemm3_core.h; this file holds the
-// kernels the library ships (one tile per workgroup, resident, wgrad) and their launchers.  Dev-build hooks are `if (kMeDev && ...)`
-// (a compile-time false in libmetaenc.so); the dev-only stream-K kernel is in gemm3_dev.hip.
+// kernels the library ships (one tile per workgroup, resident, wgrad) and their launchers.
 #include "gemm3_core.h"
 
-#ifndef G3_ROWOP_AHEAD_HALF
-#define G3_ROWOP_AHEAD_HALF 4                  // ... in a 128-row item's epilogue (two: proj 80.5 -> 84.2 us, fc2 203 -> 206 us)
-#endif
-#ifndef G3_ROWOP_AHEAD_STATS
-#define G3_ROWOP_AHEAD_STATS 4                 // ... in the statistics / gelu'(row operand) epilogues
-#endif
-#ifndef G3_TRAIN_GELU_POLY
-#define G3_TRAIN_GELU_POLY 0                   // (A/B arm: the two bf16-mode polynomials instead of the shared-exponential erf pair where gelu AND gelu' are stored)
-#endif
-#ifndef G3_COLGROUPS
-#define G3_COLGROUPS 0                         // (A/B arm, OFF: a column-grouped tile walk of the resident kernel -- measured +0.8 % on the forward and +0.2 % on the
-                                               //  train step, profiles/r06_colgroups_ab.txt: the weight re-reads it removes are Infinity-Cache hits, the token re-reads
-                                               //  it adds are not all.  Compiled out when 0: its scalars would live across the item loop)
-#endif
-#ifndef G3_ROWOP_AHEAD
-#define G3_ROWOP_AHEAD 4                       // row-operand slabs in flight ahead of their use in a whole tile's epilogue (6 until round 4: proj 84.6 -> 80.6 us,
-                                               // fc2 205.7 -> 201.7 us sustained, gpurun_out r4s / profiles/r04_rowop_ahead.txt: fewer spills at the seam)
-#endif
 namespace {
+constexpr int G3_ROWOP_AHEAD = 4;              // row-operand slabs in flight ahead of their use in a whole tile's epilogue (6 until round 4: proj 84.6 -> 80.6 us,
+                                               // fc2 205.7 -> 201.7 us sustained, profiles/r04_rowop_ahead.txt: fewer spills at the seam)
+constexpr int G3_ROWOP_AHEAD_HALF = 4;         // ... in a 128-row item's epilogue (two: proj 80.5 -> 84.2 us, fc2 203 -> 206 us)
+constexpr int G3_ROWOP_AHEAD_STATS = 4;        // ... in the statistics / gelu'(row operand) epilogues
 
 // ---- one tile per workgroup
 template <int EPI, bool WRAP = false>
@@ -72,10 +57,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // carry the same amount of work.
     const int nwg = gridDim.x, bid = blockIdx.x;
     const int xcd = bid & 7, slot = bid >> 3;
-    if (kMeDev && (p.debug >> 4) && bid < 256) { // dev: stagger the first round (output bursts of the CUs spread out)
-        const int n = (slot & 7) * (p.debug >> 4);
-        for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(4);
-    }
     const int F = p.g3_full_tiles;
     const int nf = (F >> 3) + (xcd < (F & 7) ? 1 : 0);
     const int base_f = xcd * (F >> 3) + (xcd < (F & 7) ? xcd : (F & 7));
@@ -120,15 +101,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     g3_ktile<1, false, 0, false, 0, WRAP>(s, null, 0, null, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (wr == 0) __builtin_amdgcn_s_barrier();
-    if (kMeDev && (p.debug & 1)) {               // dev: K-loop only
-        float keep = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) keep += s.acc[i][j][0] + s.acc[i][j][1] + s.acc[i][j][2] + s.acc[i][j][3];
-        if (keep == 1.2345e-30f) reinterpret_cast<float*>(p.C)[0] = keep;
-        return;
-    }
     if (part >= 0) {
         // a part of a split tile: raw partial sums; the fold that follows the launch applies the real epilogue
         const int64_t row0 = (int64_t)(F / p.tiles_n) * G3_BM;
@@ -356,10 +328,7 @@ __device__ __forceinline__ void g3_epilogue_r(const GemmParams& p, G3State& s, i
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(base)) + (m0 * ld + n0) * esz, 0,
                                                  (int)(((rows - 1) * ld + cols) * esz), 0x00020000);
     };
-    // dev (debug bit 4): the stores go nowhere (zero-record descriptor), everything else unchanged
-    // (debug bit 2 with bit 4: only the first workgroup of every XCD keeps its stores)
-    const bool drop = kMeDev && (p.debug & 4) && !((p.debug & 2) && (blockIdx.x >> 3) == 0);
-    const __amdgpu_buffer_rsrc_t crs = drop ? __builtin_amdgcn_make_buffer_rsrc(p.C, 0, 0, 0x00020000) : tile_rsrc(p.C, p.ldc);
+    const __amdgpu_buffer_rsrc_t crs = tile_rsrc(p.C, p.ldc);
     const __amdgpu_buffer_rsrc_t prs = SAVE ? tile_rsrc(p.preact, p.ldpre, G8S ? 1 : 2) : crs;
     const __amdgpu_buffer_rsrc_t rrs = EPI == 2 ? tile_rsrc(p.residual, p.ldres) : (EPI == 3 || EPI == 6) ? tile_rsrc(p.aux, p.ldaux, G8L ? 1 : 2) : crs;
     const int rop_ld = (int)(EPI == 2 ? p.ldres : p.ldaux);
@@ -525,13 +494,6 @@ __device__ __forceinline__ void g3_epilogue_r(const GemmParams& p, G3State& s, i
                     // gelu and gelu' from the same Phi / Gaussian parts: the backward GEMM multiplies by the saved factor.  (The
                     // erf form stays here: with BOTH outputs wanted it shares one exponential between them, and the two
                     // polynomial chains of the bf16-mode forms measured no faster -- 344 against 339 us per fc1 launch.)
-#if G3_TRAIN_GELU_POLY
-                    const f32x4 t0 = gelu_clamp4(v0), t1 = gelu_clamp4(v1);
-                    const f32x4 d0 = gelu_bf16_grad_from_t4(v0, t0), d1 = gelu_bf16_grad_from_t4(v1, t1);
-                    __builtin_amdgcn_raw_buffer_store_b128(g3r_lanes(pack(d0, d1), to_mem), prs, (int)(poff + (2 * mt + h) * pstep), 0, G3_POL_P);
-                    v0 = gelu_bf16_from_t4(v0, t0);
-                    v1 = gelu_bf16_from_t4(v1, t1);
-#else
                     f32x4 ph0, ga0, ph1, ga1;
                     phi_parts4(v0, ph0, ga0);
                     phi_parts4(v1, ph1, ga1);
@@ -544,7 +506,6 @@ __device__ __forceinline__ void g3_epilogue_r(const GemmParams& p, G3State& s, i
                     }
                     v0 *= ph0;
                     v1 *= ph1;
-#endif
                 } else {
                     if (SAVE) __builtin_amdgcn_raw_buffer_store_b128(g3r_lanes(pack(v0, v1), to_mem), prs, (int)(poff + (2 * mt + h) * pstep), 0, G3_POL_P);
                     v0 = gelu_bf16_4(v0);
@@ -673,31 +634,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int bid = blockIdx.x, xcd = bid & 7, c = bid >> 3, G8 = gridDim.x >> 3;
     const int tiles = p.tiles_m * p.tiles_n, F = p.g3_full_tiles;
     const int nwork = F + (tiles - F) * 2;                             // (F == tiles unless p.g3_half)
-    int nf = (F >> 3) + (xcd < (F & 7) ? 1 : 0);                       // whole tiles / all items of this XCD
-    int nx = (nwork >> 3) + (xcd < (nwork & 7) ? 1 : 0);
+    const int nf = (F >> 3) + (xcd < (F & 7) ? 1 : 0);                 // whole tiles / all items of this XCD
+    const int nx = (nwork >> 3) + (xcd < (nwork & 7) ? 1 : 0);
     const int base_f = xcd * (F >> 3) + (xcd < (F & 7) ? xcd : (F & 7));
     const int base_all = xcd * (nwork >> 3) + (xcd < (nwork & 7) ? xcd : (nwork & 7));
     const int nkt = (int)(p.K / G3_BK);
-    // Column groups (p.g3_colgroups = Gc > 1, round 6): a weight matrix whose column panels do not fit the XCD's 4 MiB L2 together (fc1:
-    // 12 panels x 393 KB = 4.7 MB) is re-read from the Infinity Cache by every round of 32 concurrent tiles -- +343 MB per fc1 launch, at
-    // ~64 pJ per byte (profiles/r06_pmc_fwd.json, r06_energy_probe.txt).  The XCDs then split the COLUMN tiles too: XCD x walks the
-    // sub-grid (row group x / Gc of 8 / Gc, column group x % Gc of Gc) row-major, so its tiles_n / Gc weight panels stay resident; every
-    // token panel is read by Gc XCDs instead of one (+ (Gc - 1) x the A bytes, the smaller side of the trade).  Whole tiles only.
-    const int Gc = G3_COLGROUPS ? p.g3_colgroups : 1;
-    int cg_c0 = 0, cg_cn = p.tiles_n, cg_r0 = 0;
-    if (Gc > 1) {
-        const int Rg = 8 / Gc, rg = xcd / Gc;
-        cg_cn = p.tiles_n / Gc;
-        cg_c0 = (xcd % Gc) * cg_cn;
-        cg_r0 = rg * p.tiles_m / Rg;
-        nf = nx = ((rg + 1) * p.tiles_m / Rg - cg_r0) * cg_cn;
-    }
     auto decode = [&](int slot, int& tile, int& part, int& kt0, int& kt1) {
         part = -1; kt0 = 0; kt1 = nkt;
-        if (Gc > 1) {
-            const int jr = __builtin_amdgcn_readfirstlane(slot / cg_cn);
-            tile = (cg_r0 + jr) * p.tiles_n + cg_c0 + (slot - jr * cg_cn);
-        } else if (slot < nf) {
+        if (slot < nf) {
             tile = base_f + slot;
         } else {
             // a tile of the last, mostly empty round: two 128-row items (part = which half), the whole reduction each
@@ -716,10 +660,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const uint32_t lds_tick = (uint32_t)(uintptr_t)smem + G3_LDS;
     int slot = c;
     if (slot >= nx) return;
-    if (kMeDev && (p.debug >> 4)) {              // dev: stagger the CUs of an XCD (their output bursts spread out)
-        const int n = c * (p.debug >> 4);
-        for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(4);
-    }
 
     G3State s;
     g3_init_lane(s, p, smem, wave, lane);
@@ -757,20 +697,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __builtin_amdgcn_s_barrier();
     if (wr == 1) __builtin_amdgcn_s_barrier();
 
-    // dev: time stamps (s_memtime) of waves 0 and 4: [workgroup][wave row][item][8] = item start, first K-tile done,
-    // second K-tile done, K-loop done, rows realigned, epilogue done (tools/gemm_dev, debug bit 8; dead code in the product build)
-    unsigned long long* trace = kMeDev ? reinterpret_cast<unsigned long long*>(p.colsum_ws) : nullptr;
-    int item = 0;
     int item_par = 0;                    // (PRE 5) which LDS pair buffer holds the current item's LayerNorm pairs
-#define G3R_STAMP(i)                                                                                            \
-    if (kMeDev && trace && (wave & 3) == 0 && item < 16) {                                                      \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                             \
-        if (lane == 0) trace[(((size_t)bid * 2 + wr) * 16 + item) * 8 + (i)] = t_;                              \
-        if ((i) == 0 || (i) == 5) {       /* the constant-rate counter next to the shader clock: effective clock under load */ \
-            const unsigned long long r_ = __builtin_amdgcn_s_memrealtime();                                     \
-            if (lane == 0) trace[(((size_t)bid * 2 + wr) * 16 + item) * 8 + ((i) == 0 ? 6 : 7)] = r_;           \
-        }                                                                                                        \
-    }
     // Which item comes next: static (slot + G8: every workgroup owns a fixed list) or, with p.g3_tickets, CLAIMED from the
     // XCD's counter -- a CU that is slow, or that could not take its workgroup for a while because a communication kernel
     // sat on it, then simply ends up with fewer tiles instead of holding the whole launch back (the first item stays static:
@@ -780,7 +707,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // and whole tiles only in this mode: launch3r).  Tickets 0 .. nx - 1 are drawn per XCD and launch (nx - G8 hits, one miss
     // per workgroup): whoever draws the last one zeroes the counter for the next launch on this stream.
     while (true) {
-        G3R_STAMP(0)
         int nslot = 0, ntile = tile, npart = -1, nkt0 = 0, nkt1 = 2, ntm = 0, ntn = 0;
         bool has_next = false;
         G3Src nxt = null;
@@ -803,10 +729,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 int kb = kt0 + 2, kc = kt0 + 3;
                 if (np == 1) { sb = nxt; kb = nkt0; kc = nkt0 + 1; }
                 g3_ktile<0, false, SEAM, HALF>(s, cur, 0, sb, kb);
-                G3R_STAMP(1)
                 g3_ktile<1, false, 0, HALF, HALF ? SEAM : 0>(s, sb, kb, sb, kc);
             }
-            G3R_STAMP(2)
             if (dyn) {
                 unsigned t;
                 asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(t) : "v"(lds_tick) : "memory");
@@ -822,11 +746,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
             // the two wave rows run their epilogues SIDE BY SIDE: left one barrier apart, row 1 could not start its epilogue
             // before row 0 had finished its own and reached the next K-tile's first barrier, and row 0 would then wait out
-            // row 1's (measured with the time stamps below: 4.6 k of 40 k clocks per tile).  Row 0 gives up its one-barrier
+            // row 1's (measured with per-item time stamps: 4.6 k of 40 k clocks per tile).  Row 0 gives up its one-barrier
             // lead here and row 1 re-opens it behind the epilogue.
-            G3R_STAMP(3)
             if (wr == 0) __builtin_amdgcn_s_barrier();
-            G3R_STAMP(4)
             int64_t nm0 = 0;
             int nrows = 0;
             if (PRE == 5 && has_next) {
@@ -843,8 +765,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         } else {
             run_item(std::false_type{});
         }
-        G3R_STAMP(5)
-        if (kMeDev) ++item;
         if (!has_next) break;
         if (wr == 1) __builtin_amdgcn_s_barrier();
         item_par ^= 1;
@@ -858,16 +778,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // fold (splitk_reduce_kernel, gemm.hip) sums the slabs and applies the epilogue.  Work ids are split-major (id = split *
 // tiles + tile): the workgroups an XCD runs together read the SAME rows of dY and X at the same time, so every operand
 // row comes out of HBM once and is shared through that XCD's L2.
-// FOLD: the split-K fold runs INSIDE the launch (every workgroup is resident: tiles x splits <= CUs).  The S workgroups of an output
-// tile reduce-scatter their partial tiles: the tile is cut into 32 units (16 rows x the 32-column halves of the four wave columns),
-// unit u belongs to split (u S) >> 5; a workgroup writes the units it does not own into its slab (write-through stores: no
-// release fence), announces itself on the tile ROW's counter, waits for the S x tiles_n workgroups of that tile row, and then sums its
-// own units -- own registers first, the other splits in ascending order: deterministic -- and applies the real epilogue (alpha,
-// beta C, output dtype).  One workgroup of the tile row also folds the partial column sums (the bias gradient).  Replaces the
-// separate fold launch (48 per training step: ~25 us each + a kernel boundary) by ~1/S of its traffic per workgroup.  Hand-off
-// protocol: cdna_hip_programming.md, Guideline 16 (sc1 payload, every storing wave drains, one lane publishes / polls relaxed,
-// one agent-scope acquire, then plain loads); the counters are zeroed by a memset node ahead of every launch.
-template <bool FOLD>
+// The fold stays a separate launch: inside this kernel it measured 211 us per wgrad launch against 176 us for kernel + fold (round
+// 4) -- there the slab write-through, the wait for the tile row and the read-back are exposed one after the other on every CU.
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_g3tn_kernel(const GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -931,117 +843,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if (mb < p.M) row[mb] = c1;
         }
     }
-    if (kMeDev && (p.debug & 1)) {
-        float keep = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) keep += s.acc[i][j][0] + s.acc[i][j][1] + s.acc[i][j][2] + s.acc[i][j][3];
-        if (keep == 1.2345e-30f) reinterpret_cast<float*>(p.C)[0] = keep;
-        return;
-    }
-    if (!FOLD) {
-        g3_epilogue<5>(p, s, m0, n0, lane, reinterpret_cast<float*>(p.C) + (int64_t)split * p.slab_stride, 0);
-        return;
-    }
-    // ---- in-kernel fold
-    const int S = p.split_k;
-    const int wc = wave & 3;
-    const int lr = lane & 15, lg = lane >> 4;
-    const int64_t mrow = m0 + wr * 128 + lr;
-    int64_t ncol[2];
-    bool n_ok[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        ncol[q] = n0 + wc * 64 + (2 * q + (lg & 1)) * 16 + 8 * (lg >> 1);
-        n_ok[q] = ncol[q] + 8 <= p.N;
-    }
-    const __amdgpu_buffer_rsrc_t mine = __builtin_amdgcn_make_buffer_rsrc(p.g3_slabs + (int64_t)split * p.slab_stride, 0, (int)(p.M * p.N * 4), 0x00020000);
-    // phase 1: re-deal every 16 x 16 pair into 8 consecutive columns per lane (kept in the accumulators), park the foreign units
-#pragma unroll
-    for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            f32x4 v0 = s.acc[mt][2 * q], v1 = s.acc[mt][2 * q + 1];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0[e]), __float_as_uint(v1[e]), false, false);
-                v0[e] = __uint_as_float(sw[0]);
-                v1[e] = __uint_as_float(sw[1]);
-            }
-            s.acc[mt][2 * q] = v0; s.acc[mt][2 * q + 1] = v1;
-            const int u = ((wr * 8 + mt) << 1) + q;
-            if (((u * S) >> 5) != split) {               // (wave-uniform)
-                const int64_t m = mrow + mt * 16;
-                const uint32_t off = (m < p.M && n_ok[q]) ? (uint32_t)((m * p.N + ncol[q]) * 4) : 0x80000000u;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v0), mine, (int)off, 0, 16);        // sc1: write-through
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v1), mine, (int)(off + 16), 0, 16);
-            }
-        }
-    // publish / wait: every workgroup of this tile ROW (all N-tiles, all splits) -- the column sums need all of them anyway
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        unsigned* ctr = p.g3_tickets + tm;
-        const unsigned want = (unsigned)(S * p.tiles_n);
-        __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned spins = 0;
-        while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > (1u << 26)) __builtin_trap();      // (seconds: a workgroup of the row never ran -- the launch was not resident)
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-    // phase 2: own units = own registers + the other splits' parked values, ascending; four splits' loads in flight at a time
-    const float* slab0 = p.g3_slabs;
-#pragma unroll
-    for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int u = ((wr * 8 + mt) << 1) + q;
-            if (((u * S) >> 5) != split) continue;       // (wave-uniform)
-            const int64_t m = mrow + mt * 16;
-            const bool ok = m < p.M && n_ok[q];
-            f32x4 v0 = s.acc[mt][2 * q], v1 = s.acc[mt][2 * q + 1];
-            const float* src = slab0 + (ok ? m * p.N + ncol[q] : 0);
-            for (int sb = 0; sb < S; sb += 4) {
-                f32x4 t0[4], t1[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int sj = sb + j < S ? sb + j : S - 1;
-                    t0[j] = *reinterpret_cast<const f32x4*>(src + (int64_t)sj * p.slab_stride);
-                    t1[j] = *reinterpret_cast<const f32x4*>(src + (int64_t)sj * p.slab_stride + 4);
-                }
-                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const bool use = sb + j < S && sb + j != split;
-                    v0 += use ? t0[j] : z;
-                    v1 += use ? t1[j] : z;
-                }
-            }
-            if (ok) {
-                epilogue_quad_lin(p, m, ncol[q], v0);
-                epilogue_quad_lin(p, m, ncol[q] + 4, v1);
-            }
-        }
-    // the bias gradient: partial rows [split * tiles_n + tn][M] of this tile row, folded in row order by one workgroup
-    if (do_cs && p.tn_colsum_out && split == 0 && tn == 0 && tid < 256) {
-        const int64_t m = m0 + tid;
-        if (m < p.M) {
-            const int n_part = S * p.tiles_n;
-            float t = 0.f;
-            for (int j = 0; j < n_part; j += 4) {
-                float c[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) c[e] = p.colsum_ws[(int64_t)(j + e < n_part ? j + e : n_part - 1) * p.M + m];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) t += j + e < n_part ? c[e] : 0.f;
-            }
-            p.tn_colsum_out[m] = p.beta != 0.0f ? t + p.beta * p.tn_colsum_out[m] : t;
-        }
-    }
+    g3_epilogue<5>(p, s, m0, n0, lane, reinterpret_cast<float*>(p.C) + (int64_t)split * p.slab_stride, 0);
 }
 
 
@@ -1155,7 +957,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // keeps the counter set of its capture stream, but replays run on whatever stream launches the graph (torch.cuda.graph
 // captures every graph on one shared stream), so replays on different streams -- or a replay next to eager work on the capture
 // stream -- would draw from ONE set and break the "exactly nx draws, the last one resets" invariant.  On a free GPU the two
-// schedules time the same (tools/gemm_dev g3 / g3s); claiming matters next to a communication kernel, i.e. in eager training.
+// schedules time the same; claiming matters next to a communication kernel, i.e. in eager training.
 unsigned* g3r_tickets(hipStream_t stream) {
     constexpr int SETS = 64, SET_WORDS = 8 * 16;
     struct Pool {
@@ -1193,17 +995,9 @@ unsigned* g3r_tickets(hipStream_t stream) {
 }
 
 template <int EPI, int PRE> int launch3r(const GemmParams& q0, int G, hipStream_t stream) {
-#ifndef G3_HI_EPI2
-#define G3_HI_EPI2 1                           // (A/B arm: 128-row items in the plain residual kernel too)
-#endif
-#ifndef G3_HI_EPI1
-#define G3_HI_EPI1 1                           // (A/B arm: ... and in the GELU kernels -- fc1's 2 364 tiles leave a last round of 60)
-#endif
-#ifndef G3_HI_EPI6
-#define G3_HI_EPI6 0                           // (A/B arm: ... and in the x-row-operand kernel, fc2 dgrad, the same 2 364 tiles: 243 -> 251 us
-                                               //  sustained with four row-operand slabs in flight, 263 with two; train +0.4 ms with six -- off)
-#endif
-    constexpr bool HI = EPI == 0 || (G3_HI_EPI2 && EPI == 2) || (G3_HI_EPI1 && EPI == 1) || (G3_HI_EPI6 && EPI == 6);      // which forms carry the 128-row items (see the kernel)
+    // which forms carry the 128-row items (see the kernel): the plain, residual and GELU kernels (fc1's 2 364 tiles leave a last round of
+    // 60); not the x-row-operand kernel (fc2 dgrad, the same 2 364 tiles: 243 -> 251 us sustained with them, measured and removed)
+    constexpr bool HI = EPI == 0 || EPI == 2 || EPI == 1;
     constexpr int LDS_BYTES = G3_LDS + 64 + (PRE == 5 ? 4096 : PRE == 4 ? 8192 : 0);      // operand buffers + the ticket word (+ PRE 5: two buffers of 256 LayerNorm row pairs; PRE 4: 256 rows x 4 wave columns of partial pairs)
     static OncePerDevice once;
     if (once.need())
@@ -1214,31 +1008,12 @@ template <int EPI, int PRE> int launch3r(const GemmParams& q0, int G, hipStream_
     // each -- same kernel, same epilogue, no slabs (g3_phase<.., HALF>): the last round then costs a little over half a round.
     const int tiles = q.tiles_m * q.tiles_n, rem = tiles % G;
     q.g3_full_tiles = tiles; q.g3_split = 1; q.g3_half = 0;
-    // column groups (see the kernel): the fewest groups that make an XCD's share of the weight panels fit its L2 next to the token panels in
-    // flight (<= 2.5 MB), when the column tiles divide evenly and every XCD still gets a round of tiles
-    q.g3_colgroups = 1;
-    if (G3_COLGROUPS && G == 256 && q.tiles_n >= 4) {
-        const int64_t panel = 256 * q.K * 2;
-        for (int gc = 1; gc <= 4; gc *= 2) {
-            if (q.tiles_n % gc) break;
-            if ((q.tiles_n / gc) * panel <= (5ll << 19)) {
-                // worth it when the weight re-reads it removes (one pass over B per round of 32 tiles and XCD) outweigh the token re-reads it adds
-                const int64_t b_reread = q.N * q.K * 2 * ((int64_t)tiles / 32), a_extra = (int64_t)(gc - 1) * q.M * q.K * 2;
-                if (gc > 1 && (int64_t)(q.tiles_m / (8 / gc)) * (q.tiles_n / gc) >= 64 && b_reread > 2 * a_extra) q.g3_colgroups = gc;
-                break;
-            }
-        }
-    }
-    if (q.g3_colgroups > 1) {
-        // (whole tiles only: the 128-row items' bookkeeping assumes the row-major tile list)
-    } else if (HI && tiles >= G && rem > 0 && 2 * rem <= G && q.K >= 4 * G3_BK && gemm_dev().tail_split != 3) {
+    if (HI && tiles >= G && rem > 0 && 2 * rem <= G && q.K >= 4 * G3_BK) {
         q.g3_full_tiles = tiles - rem;
         q.g3_half = 1;
     }
     // claimed items need >= 2 K-tile pairs per item (see the kernel)
-    q.g3_tickets = (q.K >= 4 * G3_BK && gemm_dev().g3_persistent == 1) ? g3r_tickets(stream) : nullptr;
-    if (kMeDev && gemm_dev().tail_split == 2) q.g3_tickets = nullptr;          // dev: "g3s" = static schedule
-    ME_DEV_ONLY(q.colsum_ws = (q.debug & 8) ? reinterpret_cast<float*>(g_gemm_dev_trace) : nullptr;)
+    q.g3_tickets = q.K >= 4 * G3_BK ? g3r_tickets(stream) : nullptr;
     hipLaunchKernelGGL((gemm_g3r_kernel<EPI, PRE, HI>), dim3((unsigned)G), dim3(512), LDS_BYTES, stream, q);
     ME_CHECK_LAUNCH("me_gemm(g3 resident)");
     return ME_OK;
@@ -1254,15 +1029,13 @@ int launch3r_any(int epi, int pre, const GemmParams& q, int G, hipStream_t strea
     }
 }
 
-template <int EPI> int launch3e(const GemmParams& p, void* ws, hipStream_t stream) {
+template <int EPI> int launch3e(const GemmParams& p, hipStream_t stream) {
     static OncePerDevice once;
     if (once.need()) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g3_kernel<EPI>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
     }
     const int tiles = p.tiles_m * p.tiles_n;
-    if (kMeDev && ws) return launch_g3p(p, EPI, ws, stream);       // dev build: the persistent stream-K form (gemm3_dev.hip)
-    (void)ws;
     GemmParams q = p;
     if (q.g3_split <= 1 || q.g3_slabs == nullptr) { q.g3_full_tiles = tiles; q.g3_split = 1; q.g3_ktp = 0; q.g3_slabs = nullptr; }
     const int nwg = q.g3_full_tiles + (tiles - q.g3_full_tiles) * q.g3_split;
@@ -1282,29 +1055,27 @@ template <int EPI> int launch3e(const GemmParams& p, void* ws, hipStream_t strea
             return ME_ERR_UNSUPPORTED;
         }
     }
-    if (gemm_dev().g3_persistent == 1) {
-        int repi = EPI <= 3 ? EPI : -1, pre = (EPI == 1 && p.preact) ? 1 : 0;
-        const bool plain = p.beta == 0.0f && p.out_group_rows == 0 && p.res_row_mod == 0 && !p.colscale && !p.residual;
-        if (EPI == 4 && p.row_affine && !p.flags && plain && !p.preact && !p.aux) {       // folded LayerNorm (bias / GELU forms)
-            repi = p.act == ME_ACT_GELU ? 1 : 0;
-            pre = p.row_nparts ? 5 : 3;       // (5: row_affine holds the 64-column partials of the launch in front, see g3_epilogue_r)
-        }
-        if (EPI == 4 && p.flags && !p.row_affine) {
-            // the two halves of the "save gelu'" pair (pick_epi sends flagged descriptors to the generic epilogue)
-            if (plain && p.flags == ME_GEMM_SAVE_GELU_GRAD && p.act == ME_ACT_GELU && p.preact && !p.aux) { repi = 1; pre = 2; }
-            if (plain && p.flags == ME_GEMM_AUX_IS_FACTOR && p.act == ME_ACT_NONE && p.aux && (p.aux_dtype == ME_BF16 || p.aux_dtype == ME_GG8) && !p.preact) repi = 6;
-        }
-        if (EPI == 6) repi = 6;                                   // (pick_epi_ex has checked the same conditions)
-        if (EPI == 7) { repi = 1; pre = 2; }
-        if (repi == 1 && pre == 2 && p.preact_dtype == ME_GG8) pre = 6;       // gelu' in eight bits, both halves of the pair
-        if (repi == 6 && p.aux_dtype == ME_GG8) pre = 6;
-        if (EPI == 2 && p.row_stats) pre = 4;
-        const int G = g3_cus() & ~7;
-        const int64_t ldmax = std::max(std::max(p.ldc, p.preact ? p.ldpre : 0), std::max(p.residual ? p.ldres : 0, p.aux ? p.ldaux : 0));
-        if (repi >= 0 && !p.colscale && G >= 8 && nwg >= G && q.g3_split <= 1 && p.alpha == 1.0f && p.c_dtype == ME_BF16 && (!(pre == 1 || pre == 2) || p.preact_dtype == ME_BF16) && (pre != 6 || !p.preact || p.ldpre % 8 == 0) &&
-            256 * ldmax * 2 < (1ll << 31))
-            return launch3r_any(repi, pre, q, G, stream);
+    int repi = EPI <= 3 ? EPI : -1, pre = (EPI == 1 && p.preact) ? 1 : 0;
+    const bool plain = p.beta == 0.0f && p.out_group_rows == 0 && p.res_row_mod == 0 && !p.colscale && !p.residual;
+    if (EPI == 4 && p.row_affine && !p.flags && plain && !p.preact && !p.aux) {       // folded LayerNorm (bias / GELU forms)
+        repi = p.act == ME_ACT_GELU ? 1 : 0;
+        pre = p.row_nparts ? 5 : 3;       // (5: row_affine holds the 64-column partials of the launch in front, see g3_epilogue_r)
     }
+    if (EPI == 4 && p.flags && !p.row_affine) {
+        // the two halves of the "save gelu'" pair (pick_epi sends flagged descriptors to the generic epilogue)
+        if (plain && p.flags == ME_GEMM_SAVE_GELU_GRAD && p.act == ME_ACT_GELU && p.preact && !p.aux) { repi = 1; pre = 2; }
+        if (plain && p.flags == ME_GEMM_AUX_IS_FACTOR && p.act == ME_ACT_NONE && p.aux && (p.aux_dtype == ME_BF16 || p.aux_dtype == ME_GG8) && !p.preact) repi = 6;
+    }
+    if (EPI == 6) repi = 6;                                   // (pick_epi_ex has checked the same conditions)
+    if (EPI == 7) { repi = 1; pre = 2; }
+    if (repi == 1 && pre == 2 && p.preact_dtype == ME_GG8) pre = 6;       // gelu' in eight bits, both halves of the pair
+    if (repi == 6 && p.aux_dtype == ME_GG8) pre = 6;
+    if (EPI == 2 && p.row_stats) pre = 4;
+    const int G = g3_cus() & ~7;
+    const int64_t ldmax = std::max(std::max(p.ldc, p.preact ? p.ldpre : 0), std::max(p.residual ? p.ldres : 0, p.aux ? p.ldaux : 0));
+    if (repi >= 0 && !p.colscale && G >= 8 && nwg >= G && q.g3_split <= 1 && p.alpha == 1.0f && p.c_dtype == ME_BF16 && (!(pre == 1 || pre == 2) || p.preact_dtype == ME_BF16) && (pre != 6 || !p.preact || p.ldpre % 8 == 0) &&
+        256 * ldmax * 2 < (1ll << 31))
+        return launch3r_any(repi, pre, q, G, stream);
     if (p.row_stats) {
         me_set_error("me_gemm: row_stats needs the resident residual kernel (see me_gemm_emits_row_stats)");
         return ME_ERR_UNSUPPORTED;
@@ -1332,9 +1103,9 @@ unsigned* me_work_counters(hipStream_t stream) { return g3r_tickets(stream); }
 int launch_g3_tn(const GemmParams& p, hipStream_t stream) {
     static OncePerDevice once;
     if (once.need())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g3tn_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g3tn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
     const int nwg = p.tiles_m * p.tiles_n * p.split_k;
-    hipLaunchKernelGGL(gemm_g3tn_kernel<false>, dim3((unsigned)nwg), dim3(512), G3_LDS, stream, p);
+    hipLaunchKernelGGL(gemm_g3tn_kernel, dim3((unsigned)nwg), dim3(512), G3_LDS, stream, p);
     ME_CHECK_LAUNCH("me_gemm(g3 tn)");
     return ME_OK;
 }
@@ -1347,29 +1118,6 @@ int launch_g3_tn_sk(const GemmParams& p, hipStream_t stream) {
     ME_CHECK_LAUNCH("me_gemm(g3 tn, balanced partition)");
     return ME_OK;
 }
-
-#if G3_TN_FOLD
-// every workgroup of the launch must be resident at the same time (they wait for each other): one per CU, at most as many as CUs;
-// slab offsets are 32-bit; at most 32 splits (the ownership map has 32 units per tile)
-bool g3_tn_fold_ok(const GemmParams& p, int split_k) {
-    const int64_t nwg = (int64_t)p.tiles_m * p.tiles_n * split_k;
-    return nwg <= g3_cus() && split_k <= 32 && p.M * p.N * 4 < (1ll << 31) && p.out_group_rows == 0 && p.res_row_mod == 0;
-}
-
-int launch_g3_tn_fold(const GemmParams& p, hipStream_t stream) {
-    static OncePerDevice once;
-    if (once.need())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g3tn_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
-    const int nwg = p.tiles_m * p.tiles_n * p.split_k;
-    if (hipMemsetAsync(p.g3_tickets, 0, (size_t)p.tiles_m * sizeof(unsigned), stream) != hipSuccess) {
-        me_set_error("me_gemm(g3 tn fold): hipMemsetAsync of the tile-row counters failed");
-        return ME_ERR_HIP;
-    }
-    hipLaunchKernelGGL(gemm_g3tn_kernel<true>, dim3((unsigned)nwg), dim3(512), G3_LDS, stream, p);
-    ME_CHECK_LAUNCH("me_gemm(g3 tn fold)");
-    return ME_OK;
-}
-#endif
 
 bool g3_tn_supported(const GemmParams& p) {
     // 16-byte chunks of 8 columns; lane offsets and per-K-tile steps are 32-bit; the bounds check spans the whole matrix
@@ -1388,7 +1136,7 @@ bool g3_supported(const GemmParams& p, int op) {
 // Will launch_g3(p, 2, ..) run the resident residual kernel, i.e. can p.row_stats be served?  (the conditions of launch3e, restated
 // for a descriptor that has not been planned yet: whole tiles, every CU gets one, bf16 output and residual, plain epilogue)
 bool g3_emits_row_stats(const GemmParams& p) {
-    if (!g3_supported(p, ME_GEMM_NT) || gemm_dev().g3_persistent != 1 || pick_epi(p) != 2 || p.colscale) return false;
+    if (!g3_supported(p, ME_GEMM_NT) || pick_epi(p) != 2 || p.colscale) return false;
     const int G = g3_cus() & ~7;
     const int64_t tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
     const int64_t ldmax = std::max(p.ldc, p.ldres);
@@ -1398,12 +1146,8 @@ bool g3_emits_row_stats(const GemmParams& p) {
 
 // Will launch_g3 run the resident kernel's folded-LayerNorm epilogue on partials (PRE 5), i.e. can me_gemm_desc.row_parts be served?
 // (the conditions of launch3e restated, as above; p.row_affine / row_nparts / col_shift already set by fill_params)
-#ifndef ME_NO_ROW_PARTS
-#define ME_NO_ROW_PARTS 0                      // (A/B arm: 1 = never; the Blocks then run me_row_stats_combine between the GEMMs, as round 5 did)
-#endif
 bool g3_takes_row_parts(const GemmParams& p) {
-    if (ME_NO_ROW_PARTS) return false;
-    if (!g3_supported(p, ME_GEMM_NT) || gemm_dev().g3_persistent != 1 || !p.row_affine || !p.col_shift) return false;
+    if (!g3_supported(p, ME_GEMM_NT) || !p.row_affine || !p.col_shift) return false;
     if (p.row_nparts < 1 || p.row_nparts > 4 || (int64_t)p.row_nparts * 256 != p.K) return false;
     if (p.flags || p.preact || p.aux || p.residual || p.colscale || p.beta != 0.0f || p.out_group_rows != 0 || p.res_row_mod != 0) return false;
     const int G = g3_cus() & ~7;
@@ -1413,10 +1157,7 @@ bool g3_takes_row_parts(const GemmParams& p) {
 
 // ME_GG8 (gelu' in eight bits): the two flagged descriptors of the training MLP, when launch3e sends them to the resident kernel
 bool g3_takes_gg8(const GemmParams& p) {
-#ifdef ME_NO_GG8
-    return false;                               // (A/B arm)
-#endif
-    if (!g3_supported(p, ME_GEMM_NT) || gemm_dev().g3_persistent != 1) return false;
+    if (!g3_supported(p, ME_GEMM_NT)) return false;
     if (p.row_affine || p.residual || p.colscale || p.beta != 0.0f || p.out_group_rows != 0 || p.res_row_mod != 0 || p.a_wrap_kt) return false;
     const bool save = p.flags == ME_GEMM_SAVE_GELU_GRAD && p.act == ME_ACT_GELU && p.preact && p.preact_dtype == ME_GG8 && !p.aux;
     const bool load = p.flags == ME_GEMM_AUX_IS_FACTOR && p.act == ME_ACT_NONE && p.aux && p.aux_dtype == ME_GG8 && !p.preact;
@@ -1427,26 +1168,18 @@ bool g3_takes_gg8(const GemmParams& p) {
     return G >= 8 && tiles >= G && p.alpha == 1.0f && p.c_dtype == ME_BF16 && 256 * ldmax * 2 < (1ll << 31);
 }
 
-// scratch of the persistent stream-K form (dev build): one fp32 partial tile per workgroup + the hand-over flags (+ 1
-// error word)
-size_t g3_workspace_bytes() {
-    const size_t G = (size_t)g3_cus();
-    return G * G3_SLAB_FLOATS * sizeof(float) + (G + 1) * sizeof(unsigned);
-}
-
-// one tile per workgroup; in the dev build ws != nullptr (>= g3_workspace_bytes()) selects the persistent stream-K form
-int launch_g3(const GemmParams& p, int epi, void* ws, hipStream_t stream) {
+int launch_g3(const GemmParams& p, int epi, hipStream_t stream) {
     if (p.colscale && epi != 2 && epi != 8) epi = 4;      // (the residual forms carry the column scale -- layer-scale Blocks; the others do not)
     switch (epi) {
-        case 0: return launch3e<0>(p, ws, stream);
-        case 1: return launch3e<1>(p, ws, stream);
-        case 2: return launch3e<2>(p, ws, stream);
-        case 3: return launch3e<3>(p, ws, stream);
-        case 6: return launch3e<6>(p, ws, stream);
-        case 7: return launch3e<7>(p, ws, stream);
-        case 8: return launch3e<8>(p, ws, stream);
-        case 9: return launch3e<9>(p, ws, stream);
-        case 10: return launch3e<10>(p, ws, stream);
-        default: return launch3e<4>(p, ws, stream);
+        case 0: return launch3e<0>(p, stream);
+        case 1: return launch3e<1>(p, stream);
+        case 2: return launch3e<2>(p, stream);
+        case 3: return launch3e<3>(p, stream);
+        case 6: return launch3e<6>(p, stream);
+        case 7: return launch3e<7>(p, stream);
+        case 8: return launch3e<8>(p, stream);
+        case 9: return launch3e<9>(p, stream);
+        case 10: return launch3e<10>(p, stream);
+        default: return launch3e<4>(p, stream);
     }
 }

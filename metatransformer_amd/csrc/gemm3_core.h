@@ -32,7 +32,7 @@
 //   WAR  slot reuse: half-tile i+8 is issued in phase i+1.  A-X, B-Y, A-Y were last read in phase i-1 (two phases and
 //        >= 2 barriers earlier for both wave rows).  B-X is read in phase i itself: its four reads are issued first
 //        and retired with lgkmcnt(8) before that phase's first barrier, which the issuing wave row passes later.
-// (shared by gemm3.hip and, in the dev build only, gemm3_dev.hip: state, DMA issue, the 4-phase K-tile, the LDS-free epilogue)
+// (used by gemm3.hip: state, DMA issue, the 4-phase K-tile, the LDS-free epilogue)
 #pragma once
 #include "gemm_common.h"
 #include <algorithm>
@@ -47,36 +47,23 @@ typedef __attribute__((address_space(3))) void lds_void3;
 
 constexpr int G3_BM = 256, G3_BN = 256, G3_BK = 64;
 // Cache policy (the `aux` operand of the buffer instructions: 1 = sc0, 2 = nt, 16 = sc1) of the resident kernel's five streams.
-// Compile-time so that an A/B is one more build of the library (tools/r4_policy_builds.sh), never a branch around a
-// memory operation: A = token rows (DMA), B = weight rows (DMA), C = output stores, R = row-operand loads, P = saved-tensor stores.
-// Defaults (round 4, profiles/r04_policy_ab.txt): the outputs, the saved tensor and the row operands are NON-TEMPORAL -- a
+// A = token rows (DMA), B = weight rows (DMA), C = output stores, R = row-operand loads, P = saved-tensor stores.
+// Round 4 (profiles/r04_policy_ab.txt): the outputs, the saved tensor and the row operands are NON-TEMPORAL -- a
 // launch writes 77 .. 620 MB that nothing re-reads before it has left the 4 MB L2s anyway, and kept out of them it stops evicting
 // the operand panels the other CUs of the XCD are about to re-read.  Kernel level (sustained loops, rotating buffers): qkv 186 ->
 // 154 us, fc1 + GELU 284 -> 247 us, fc1 + saved gelu' 295 -> 274 us, proj 80 -> 76 us at the same 1.39 kW socket power; whole
 // step, same box: train 33.2 -> 32.0 ms, forward 9.64 -> 9.51 ms.  sc1 (write-through) stores: no gain; nt on the token rows (A)
 // gives most of it back (the 9 .. 12 column tiles of a tile row share them through the L2).
-#ifndef G3_POL_A
-#define G3_POL_A 0
-#endif
-#ifndef G3_POL_B
-#define G3_POL_B 0
-#endif
-#ifndef G3_POL_C
-#define G3_POL_C 2
-#endif
-#ifndef G3_POL_R
-#define G3_POL_R 2
-#endif
-#ifndef G3_POL_C_RES
-#define G3_POL_C_RES 0             // C policy of the residual epilogue: the 77 MB token stream is what the NEXT kernel reads straight away
-#endif                             // (LayerNorm / statistics / the folded GEMM's A operand) -- kept cacheable: forward 9.59 -> 9.43 ms same box
-#ifndef G3_POL_P
-#define G3_POL_P 2
-#endif
+constexpr int G3_POL_A = 0;
+constexpr int G3_POL_B = 0;
+constexpr int G3_POL_C = 2;
+constexpr int G3_POL_R = 2;
+constexpr int G3_POL_C_RES = 0;    // C policy of the residual epilogue: the 77 MB token stream is what the NEXT kernel reads straight away
+                                   // (LayerNorm / statistics / the folded GEMM's A operand) -- kept cacheable: forward 9.59 -> 9.43 ms same box
+constexpr int G3_POL_P = 2;
 constexpr int G3_HALF = 128 * 128;              // bytes in a half-tile
 constexpr int G3_BUF = 4 * G3_HALF;             // 64 KiB
 constexpr int G3_LDS = 2 * G3_BUF;              // 128 KiB
-constexpr int G3_SLAB_FLOATS = G3_BM * G3_BN;   // one fp32 partial tile per workgroup (stream-K fix-up)
 
 // Everything the K-loop keeps in registers.  All arrays are indexed with compile-time constants only.
 struct G3State {
@@ -619,10 +606,6 @@ __device__ __forceinline__ void g3_epilogue(const GemmParams& p, G3State& s, int
             }
             if (EPI == 6) { v0 *= qa; v1 *= qb; }
             if (EPI == 2) { v0 = v0 * cscale[q][0] + qa; v1 = v1 * cscale[q][1] + qb; }
-            if (kMeDev && (p.debug & 4)) {             // dev: epilogue arithmetic without the stores
-                asm volatile("" ::"v"(v0), "v"(v1));
-                continue;
-            }
             if (ok) store8_from_f32(p.C, p.c_dtype, m * p.ldc + n[q], v0, v1);
         }
     }

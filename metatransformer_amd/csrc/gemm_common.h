@@ -14,7 +14,6 @@ struct GemmParams {
     const void* residual; int64_t ldres; int res_dtype;
     int64_t res_row_mod, out_group_rows, out_group_stride, out_row_offset;
     int tiles_m, tiles_n;
-    int debug;                              // dev builds only (GemmDev::debug, 0 in the shipped library): 1 = skip the epilogue
     int split_k, ksteps_per_split;          // split-K (wgrad): grid.y = split_k, slab z written to C + z*M*ldc
     float* colsum_ws;                       // TN only: partial column sums of A, [split_k * tiles_n][M] (null = off)
     // g3 tail split (gemm3.hip): tiles [g3_full_tiles, tiles) run as g3_split workgroups each, g3_ktp K-tiles (of 64) per
@@ -22,14 +21,12 @@ struct GemmParams {
     int g3_full_tiles, g3_split, g3_ktp;
     float* g3_slabs;
     int g3_half;                            // resident kernel: tiles [g3_full_tiles, tiles) run as two 128-row items each (real epilogue, no slabs)
-    int g3_colgroups;                       // resident kernel: the XCDs split the column tiles into this many groups (1 = every XCD walks whole tile rows)
     unsigned* g3_tickets;                   // resident g3 kernel: per-XCD work counters (16 words apart), null = static schedule
     int64_t slab_stride;                    // g3 wgrad: floats between the split-K slabs in C (>= M * N, padded: see g3_tn_slab_stride)
     const float* row_affine;                // folded LayerNorm (me_gemm_desc.row_affine): [M][2] = (rstd, -rstd * mean), or null
     int row_nparts; float row_eps;          // row_nparts > 0 (me_gemm_desc.row_parts): row_affine holds [row_nparts][M] partial (mean, M2) pairs instead --
                                             // resident kernel only (g3_takes_row_parts); the pairs are LayerNorm(K = 64 row_nparts, row_eps)'s
     const float* col_shift;                 // ... and s[n] = sum_k W'[n, k]
-    float* tn_colsum_out;                   // g3 wgrad with the in-kernel fold: where the folded column sums of A go (follows C's beta), or null
     int sk_wgs, sk_upt, sk_levels, sk_l1;   // g3 wgrad on sk_wgs > 0 workgroups that are NOT a multiple of the tile count (gemm3.hip: gemm_g3tn_sk_kernel): sk_levels
                                             // whole split levels of sk_l1 K-tile pairs per tile (one workgroup each, split-major as the uniform grid) + the rest of every
                                             // tile's sk_upt pairs shared evenly, across tile boundaries, by the sk_wgs - sk_levels x tiles workgroups left over
@@ -245,45 +242,15 @@ static inline int pick_epi_ex(const GemmParams& p) {
 // kernel families (each in its own translation unit)
 int launch_g2b(const GemmParams& p, int op, int bm, int bn, hipStream_t stream);
 bool g2b_supported(const GemmParams& p, int op);
-int launch_g3(const GemmParams& p, int epi, void* ws, hipStream_t stream);      // ws = nullptr: one tile per workgroup
+int launch_g3(const GemmParams& p, int epi, hipStream_t stream);
 bool g3_supported(const GemmParams& p, int op);
 bool g3_emits_row_stats(const GemmParams& p);          // will launch_g3 run the resident residual kernel that can emit p.row_stats?
 bool g3_takes_row_parts(const GemmParams& p);          // ... the resident folded-LayerNorm epilogue that consumes such partials directly (p.row_nparts)?
 bool g3_takes_gg8(const GemmParams& p);         // ME_GG8 preact / aux: the resident kernel's PRE 6 forms only
-size_t g3_workspace_bytes();
 int launch_g3_tn(const GemmParams& p, hipStream_t stream);      // p.split_k slabs into p.C, p.ksteps_per_split K-tiles of 64 each
 int launch_g3_tn_sk(const GemmParams& p, hipStream_t stream);   // the balanced static partition (p.sk_wgs workgroups; p.split_k = the most slabs a tile gets)
-// A/B arm, measured and NOT shipped (round 4): -DG3_TN_FOLD=1 = the split-K fold of the wgrad kernel INSIDE its launch.  Same-box
-// result: wgrad 211 us per launch against 176 us for kernel + separate fold launch (train step 32.8 vs 31.35 ms): the S partial
-// tiles of a tile are 64 MB per launch either way, and inside the launch their write-through, the wait for the tile row and the
-// read-back are exposed one after the other on every CU, where the separate fold streams them at full-chip bandwidth while the
-// next kernel's launch overlaps the tail (the guide's "splitk-seam" verdict, reproduced at this size).
-#ifndef G3_TN_FOLD
-#define G3_TN_FOLD 0
-#endif
-// the same with the split-K fold inside the launch (p.C = the real output, p.g3_slabs = p.split_k slabs, p.g3_tickets = one zeroed
-// counter per tile row); only when every workgroup of the launch is resident at once (g3_tn_fold_ok)
-int launch_g3_tn_fold(const GemmParams& p, hipStream_t stream);
-bool g3_tn_fold_ok(const GemmParams& p, int split_k);
 bool g3_tn_supported(const GemmParams& p);
 // floats between the split-K slabs of the g3 wgrad kernel.  (Padding the stride off the 256 KiB multiples the encoder's
 // shapes give was tried against HBM channel aliasing in the fold: 34 us against 23, i.e. worse -- the slabs stay dense.)
 static inline int64_t g3_tn_slab_stride(int64_t M, int64_t N) { return M * N; }
 
-// Dev switches for A/B runs (tools/gemm_dev): they exist only in the dev build of the library (-DME_DEV, built by
-// `python -m metatransformer_amd.build --dev` into tools/_build/); the shipped library has no knobs and reads no
-// environment variables.
-struct GemmDev { int family, bn, debug, tail_split, g3_persistent; };
-#ifdef ME_DEV
-constexpr bool kMeDev = true;
-#define ME_DEV_ONLY(...) __VA_ARGS__
-int launch_g3p(const GemmParams& p, int epi, void* ws, hipStream_t stream);      // gemm3_dev.hip
-extern GemmDev g_gemm_dev;
-extern void* g_gemm_dev_trace;      // device buffer for the resident kernel's time stamps (tools/gemm_dev --trace)
-static inline GemmDev gemm_dev() { return g_gemm_dev; }
-#else
-constexpr bool kMeDev = false;
-#define ME_DEV_ONLY(...)
-static inline int launch_g3p(const GemmParams&, int, void*, hipStream_t) { return ME_ERR_UNSUPPORTED; }
-static inline GemmDev gemm_dev() { return GemmDev{-1, 0, 0, 1, 1}; }
-#endif

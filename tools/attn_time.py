@@ -1,12 +1,12 @@
 """Developer tool: time the attention forward / backward entry points through the product library (no stamps) on rotating
-buffers.    python tools/attn_time.py [--lib tools/_build_prod_X/libmetaenc.so] [B N H hd]"""
+buffers.    python tools/attn_time.py [--lib path/to/libmetaenc.so] [B N H hd]"""
 import os
 import sys
 import torch
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
 from metatransformer_amd import _capi, ops
 
-if "--lib" in sys.argv:          # an A/B arm of the library (python -m metatransformer_amd.build --variant NAME -D...)
+if "--lib" in sys.argv:          # an older build of the library (build that commit in a git worktree)
     i = sys.argv.index("--lib")
     _capi.LIB_PATH = os.path.abspath(sys.argv[i + 1])
     del sys.argv[i:i + 2]

@@ -3,7 +3,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from metatransformer_amd import _capi, ops
-if "--lib" in sys.argv:          # an A/B arm of the library (python -m metatransformer_amd.build --variant NAME ...)
+if "--lib" in sys.argv:          # an older build of the library (build that commit in a git worktree)
     i = sys.argv.index("--lib")
     _capi.LIB_PATH = os.path.abspath(sys.argv[i + 1])
     del sys.argv[i:i + 2]

@@ -1,7 +1,7 @@
 """Weight-gradient GEMMs (split-K wgrad kernel + fp32 slab fold) of the Base and Large encoders at the BASELINE token counts, timed per
-kernel: run under rocprofv3 --kernel-trace (tools/runs/r5_run_fold.sh folds the trace).
+kernel: run under rocprofv3 --kernel-trace.
 
-    python tools/fold_time.py [--lib tools/_build_prod_X/libmetaenc.so]
+    python tools/fold_time.py [--lib path/to/libmetaenc.so]      (--lib: an older build of the library, e.g. from a git worktree)
 """
 import os
 import sys

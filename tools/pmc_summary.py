@@ -53,7 +53,7 @@ def main(mode):
             e["hbm_traffic_MB"] = round(e["fetch_MB"] + e["write_MB"], 1)
         # (GRBM_GUI_ACTIVE over the launch's wall time is NOT used as a clock estimate here: the counter is summed over the eight XCDs
         # and over a different pass than the durations -- it gave 2.1 .. 2.7 "GHz".  The effective clock under a kernel is measured
-        # inside it instead: s_memtime against s_memrealtime, tools/gemm_dev debug bit 8 -> profiles/r03_gemm_dev_clock.txt.)
+        # inside it instead: s_memtime against s_memrealtime (round 3).)
         if "SQ_VALU_MFMA_BUSY_CYCLES" in c and "GRBM_GUI_ACTIVE" in c:
             e["mfma_busy_frac"] = round(c["SQ_VALU_MFMA_BUSY_CYCLES"] / (c["GRBM_GUI_ACTIVE"] / 8 * 256 * 4), 4)
         if "SQ_WAVE_CYCLES" in c:

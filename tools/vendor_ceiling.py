@@ -1,5 +1,5 @@
 """Measured ceiling only (never on the product path): torch.matmul -> hipBLASLt/rocBLAS on the encoder's GEMM shapes,
-with rotating buffers like tools/gemm_bench.py."""
+with rotating buffers."""
 import torch
 dev = torch.device("cuda:0")
 M = 256 * 197
