@@ -580,6 +580,30 @@ size_t me_three_interpolate_bwd_workspace(int B, int n, int m);
 int me_three_interpolate_bwd(const float* dout, int ldo, int col0, const int32_t* idx, const float* weight, float* dfeats,
                              int ldf, int B, int n, int m, int C, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ multi-scale deformable attention (ViT-Adapter)
+ * The sampling core of MSDeformAttn (Deformable DETR; Image/{detection,segmentation}/ops/functions/ms_deform_attn_func.py:19-46,
+ * called by the Injector / Extractor of mmdet_custom/models/backbones/adapter_modules.py:90-191), fp32 throughout:
+ *   value [N, S, M, D]: S = sum_l H_l W_l rows, level l at rows level_start[l] .. + H_l W_l, row-major H_l x W_l; M heads of D
+ *   channels.  loc [N, Lq, M, L, P, 2] = (x, y) normalised to [0, 1] over the level; attn [N, Lq, M, L, P].
+ * spatial_shapes [L, 2] = (H_l, W_l) and level_start [L] are HOST int32 arrays (read at the call, nothing is read back from the
+ * device); L <= 8 and D a multiple of 4 up to 128, ME_ERR_UNSUPPORTED otherwise.  The levels must tile the S rows in order
+ * (level_start[0] = 0, level_start[l + 1] = level_start[l] + H_l W_l, the last ending at S): anything else is ME_ERR_ARG.
+ * me_ms_deform_attn_fwd: out [N, Lq, M * D]:  out[n, q, m D + d] = sum_{l, p} attn[n, q, m, l, p] *
+ *   bilinear(value_l[n, :, m, d]; x W_l - 0.5, y H_l - 0.5), corners outside the level contributing zero (grid_sample with
+ *   padding_mode = 'zeros', align_corners = False).  N, Lq or S = 0: ME_OK, nothing written.
+ * me_ms_deform_attn_bwd: from dout [N, Lq, M * D]: dvalue [N, S, M, D], dloc (shape of loc), dattn (shape of attn).  dvalue may be
+ *   NULL, or dloc and dattn both NULL, to skip that part.  Every element of what is asked for is written; value rows no sample
+ *   touches get exact zeros.  Deterministic: the (sample, corner) -> value row map is inverted by a counting sort and every row
+ *   sums its list in ascending (n, q, m, l, p, corner) order, the corner weight recomputed (no float atomics), so two runs are
+ *   bit-identical.  A location exactly on a pixel boundary takes the one-sided derivative towards the lower-right pixel.
+ *   workspace (dvalue only): me_ms_deform_attn_bwd_workspace(N, S, M, Lq, L, P) bytes, 16-byte aligned. */
+int me_ms_deform_attn_fwd(const float* value, const int32_t* spatial_shapes, const int32_t* level_start, const float* loc,
+                          const float* attn, float* out, int N, int S, int M, int D, int Lq, int L, int P, void* stream);
+size_t me_ms_deform_attn_bwd_workspace(int N, int S, int M, int Lq, int L, int P);
+int me_ms_deform_attn_bwd(const float* value, const int32_t* spatial_shapes, const int32_t* level_start, const float* loc,
+                          const float* attn, const float* dout, float* dvalue, float* dloc, float* dattn, int N, int S, int M, int D,
+                          int Lq, int L, int P, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ position-embedding table resize
  * Replaces TIMMVisionTransformer.resize_pos_embed (Image/detection/mmdet_custom/models/backbones/base/vit.py:459-486,
  * also vit_adapter.py:73-78): the [h*w, cols] grid part of a pos-embed table resampled to [H*W, cols] with
