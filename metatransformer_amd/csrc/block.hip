@@ -2,14 +2,12 @@
 // Restates Block.forward, PointCloud/openpoints/models/layers/attention.py:55-58 (and what autograd derives from it):
 // no new arithmetic here, only the launch sequence, the activation stash and the scratch carving, so that a host makes
 // ONE call per block and direction and the GPU never waits for the host between the ~10 (forward) / ~20 (backward) kernels.
-#include "common.h"
+#include "gemm_host.h"
 #include <string.h>
 #include <stdlib.h>
 #include <atomic>
 #include <map>
 #include <mutex>
-
-int gemm_tn_x3_planes(const me_gemm_desc* d, hipStream_t stream);      // gemm3_x3.hip
 
 namespace {
 

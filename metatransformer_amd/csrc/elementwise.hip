@@ -627,7 +627,7 @@ __global__ __launch_bounds__(EW_THREADS) void adamw_seg_kernel(float* __restrict
 // Replaces TIMMVisionTransformer.resize_pos_embed (Image/detection/mmdet_custom/models/backbones/base/vit.py:459-486:
 // reshape the [h*w, C] table to [1, C, h, w], F.interpolate(size=(H, W), mode, align_corners=False), flatten back) on the
 // token-major layout directly: rows are grid positions, channels contiguous -- no permutes.  The sampling arithmetic is
-// ATen's upsample_bicubic2d / upsample_bilinear2d restated: source coordinate s = (in/out) * (d + 0.5) - 0.5 (bilinear
+// ATen's upsample_bicubic2d / upsample_bilinear2d, written out: source coordinate s = (in/out) * (d + 0.5) - 0.5 (bilinear
 // clamps it at 0, bicubic does not), cubic-convolution weights with A = -0.75, taps clamped to the table edge, fp32.
 __device__ __forceinline__ float cubic1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
 __device__ __forceinline__ float cubic2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }

@@ -365,7 +365,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p, 
     }
 }
 
-static void launch_splitk_reduce(const GemmParams& p, unsigned /*nb*/, hipStream_t stream, const float* slabs, int S, const float* cs_part,
+static void launch_splitk_reduce(const GemmParams& p, hipStream_t stream, const float* slabs, int S, const float* cs_part,
                                  int n_part, float* colsum_out, int64_t sstride = 0) {
     if (sstride == 0) sstride = p.M * p.N;
     const unsigned gx = (unsigned)((p.N / 4 + 63) / 64);
@@ -410,16 +410,16 @@ static void launch_splitk_reduce(const GemmParams& p, unsigned /*nb*/, hipStream
 }
 
 struct GemmPlan {
-    int family;      // 0 = g128, 2 = g2b (two 4-wave workgroups / CU), 3 = g2w (8 waves, K-step 32), 4 = g3 (8 waves, K-tile 64)
-    int bn;          // 256 / 128
-    int bm;          // 256 / 128
-    int kstep;       // reduction elements per pipeline step (32; g3: 64)
-    int split_k;     // >= 1
-    int ksteps_per_split;
-    size_t ws_bytes;
+    GemmFamily family = GEMM_G128;
+    int bn = 0;          // 256 / 128
+    int bm = 128;        // 256 / 128 / 64
+    int kstep = 0;       // reduction elements per pipeline step (32; g3: 64)
+    int split_k = 1;     // >= 1
+    int ksteps_per_split = 0;
+    size_t ws_bytes = 0;
     // NT tail split: the last tail_rows rows run as their own split-K problem (see plan_gemm)
-    int64_t tail_rows;
-    int tail_split, tail_ksteps;
+    int64_t tail_rows = 0;
+    int tail_split = 1, tail_ksteps = 0;
     // g3 wgrad next to a communication kernel (me_gemm_reserve_cus): the balanced static partition over sk_wgs workgroups of sk_upt
     // K-tile pairs per tile (gemm3.hip, gemm_g3tn_sk_kernel); split_k then = the most slabs a tile gets
     int sk_wgs = 0, sk_upt = 0, sk_levels = 0, sk_l1 = 0;
@@ -433,36 +433,35 @@ constexpr int kSmallSplitDen = 2;                // whole-problem split-K when t
                                                  // B = 1 0.92 -> 1.43 ms; / 3 -> / 2: M = 8 224 fwd + dX 6.9 -> 6.74 ms, the rest unchanged
 constexpr int kSmallSplitLongK = 192;
 GemmPlan plan_gemm(const me_gemm_desc* d, const GemmParams& p, bool allow_sk = true) {
-    GemmPlan pl{0, 0, 128, 0, 1, 0, 0, 0, 1, 0};
+    GemmPlan pl;
     if (d->ab_dtype != ME_BF16) return pl;
     // measured on the encoder's shapes: NT with at least half a chip of 256x256 tiles -> g3
     // (K-tile 64, 4-phase ping-pong: 860-1000 TF on the Base shapes against 500-780 for the K-step-32 kernels); fewer
     // tiles or K not a multiple of 128 -> the K-step-32 kernels with their split-K forms; TN (wgrad) -> g2b.
-    int fam = 2;
-    if (d->op == ME_GEMM_TN && d->M >= 256 && d->N >= 256 && d->K >= 4096) fam = 4;      // wgrad: g3 (950 vs 640 TF)
+    GemmFamily fam = GEMM_G2B;
+    if (d->op == ME_GEMM_TN && d->M >= 256 && d->N >= 256 && d->K >= 4096) fam = GEMM_G3;      // wgrad: g3 (950 vs 640 TF)
     if (d->op == ME_GEMM_NT && d->M >= 256 && d->N >= 256) {
         const int64_t t256 = ((d->M + 255) / 256) * ((d->N + 255) / 256);
-        fam = (t256 >= 128 && g3_supported(p, d->op)) ? 4 : ((d->N <= 768 && d->K <= 1024) ? 2 : 3);
+        fam = (t256 >= 128 && g3_supported(p, d->op)) ? GEMM_G3 : ((d->N <= 768 && d->K <= 1024) ? GEMM_G2B : GEMM_G2W);
     }
-    if (fam == 4 && d->op == ME_GEMM_NT && !g3_supported(p, d->op)) fam = 3;
-    if (fam == 4 && d->op == ME_GEMM_TN && (!g3_tn_supported(p) || d->M < 256 || d->N < 256)) fam = 2;
+    if (fam == GEMM_G3 && d->op == ME_GEMM_NT && !g3_supported(p, d->op)) fam = GEMM_G2W;
+    if (fam == GEMM_G3 && d->op == ME_GEMM_TN && (!g3_tn_supported(p) || d->M < 256 || d->N < 256)) fam = GEMM_G2B;
     // (the g3 wgrad kernel takes any reduction length: rows past K read zeros through its descriptors -- a ragged token count,
     //  B x N not a multiple of 32, no longer sends the weight gradients of a whole Block to the generic kernel)
-    if (!(fam == 4 && d->op == ME_GEMM_TN) && !g2b_supported(p, d->op)) return pl;
+    if (!(fam == GEMM_G3 && d->op == ME_GEMM_TN) && !g2b_supported(p, d->op)) return pl;
     if (d->M < 128 || d->N < 128) return pl;       // tiny problems: g128 is enough
     pl.family = fam;
-    pl.bm = fam == 2 ? 128 : 256;
+    pl.bm = fam == GEMM_G2B ? 128 : 256;
     // Small / mid-size NT problems (fewer than half a chip of 256 x 256 tiles: the reference's own batches, B = 32 x 96 .. 257
     // tokens, and B = 1 .. 32 inference): pick the TILE so that the launch has enough workgroups for the chip WITHOUT a K split --
     // the largest of 128 x 256 / 128 x 128 / 64 x 128 that still gives >= 140 tiles, else the smallest.  Measured on M = 197 ..
     // 6 304 (profiles/r05_small_gemm_plans.txt): 1.2 .. 4x faster per launch than the round-4 plans (256-wide tiles + whole-problem
     // split-K + fold), e.g. M = 3 072: qkv 36 -> 19 us, proj 23 -> 11 us, fc2 41 -> 31 us; M = 197: fc1 41 -> 10 us.
     bool small_nt = false;
-    if (fam != 4 && d->op == ME_GEMM_NT && d->N % 128 == 0) {
-        fam = 2; pl.family = 2; small_nt = true;
-        const int64_t tm128 = (d->M + 127) / 128, tm64 = (d->M + 63) / 64;
-        const int64_t c256 = tm128 * ((d->N + 255) / 256), c128 = tm128 * (d->N / 128), c64 = tm64 * (d->N / 128);
-        (void)c64;
+    if (fam != GEMM_G3 && d->op == ME_GEMM_NT && d->N % 128 == 0) {
+        fam = pl.family = GEMM_G2B; small_nt = true;
+        const int64_t tm128 = (d->M + 127) / 128;
+        const int64_t c256 = tm128 * ((d->N + 255) / 256), c128 = tm128 * (d->N / 128);
         if (c256 >= 140 && d->N % 256 == 0) { pl.bm = 128; pl.bn = 256; }
         else if (c128 >= 140) { pl.bm = 128; pl.bn = 128; }
         else { pl.bm = 64; pl.bn = 128; }
@@ -471,10 +470,9 @@ GemmPlan plan_gemm(const me_gemm_desc* d, const GemmParams& p, bool allow_sk = t
     const int64_t tm = (d->M + pl.bm - 1) / pl.bm;
     const int64_t t256 = tm * ((d->N + 255) / 256), t128 = tm * ((d->N + 127) / 128);
     const int nk = (int)(d->K / pl.kstep);
-    const int SLOTS = fam == 2 ? 512 : 256;                      // co-resident workgroups on the chip
-    if (d->op == ME_GEMM_TN && fam == 4) {
-        // wgrad on the g3 skeleton (gemm3.hip): 256 x 256 output tiles, the reduction split over the CUs in K-tile pairs
-        if (!g3_tn_supported(p)) return GemmPlan{0, 0, 128, 0, 1, 0, 0, 0, 1, 0};
+    const int SLOTS = fam == GEMM_G2B ? 512 : 256;               // co-resident workgroups on the chip
+    if (d->op == ME_GEMM_TN && fam == GEMM_G3) {
+        // wgrad on the g3 skeleton (gemm3.hip): 256 x 256 output tiles, the reduction split over the CUs in K-tile pairs (g3_tn_supported: checked above)
         pl.bn = 256; pl.bm = 256; pl.kstep = 64;
         const int64_t tiles = ((d->M + 255) / 256) * ((d->N + 255) / 256);
         const int nkt = (int)((d->K + 63) / 64);
@@ -524,15 +522,15 @@ GemmPlan plan_gemm(const me_gemm_desc* d, const GemmParams& p, bool allow_sk = t
         pl.split_k = (nk + pl.ksteps_per_split - 1) / pl.ksteps_per_split;
         if (pl.split_k > 1) {
             pl.ws_bytes = (size_t)pl.split_k * (size_t)d->M * (size_t)d->N * sizeof(float);
-            if (d->colsum_a && fam == 2)      // partial column sums of A: one [M] row per (split, N-tile)
+            if (d->colsum_a && fam == GEMM_G2B)      // partial column sums of A: one [M] row per (split, N-tile)
                 pl.ws_bytes += (size_t)pl.split_k * (size_t)((d->N + pl.bn - 1) / pl.bn) * (size_t)d->M * sizeof(float);
         }
     } else {
-        if (fam >= 3) pl.bn = 256;
+        if (fam != GEMM_G2B) pl.bn = 256;
         else if (small_nt) {}                                    // (chosen above)
         else pl.bn = d->N > 128 ? 256 : 128;                     // measured: g2b_256 beats g2b_128 on every encoder shape
         pl.ksteps_per_split = nk;
-        if (fam == 4) {
+        if (fam == GEMM_G3) {
             // Tile quantisation (see gemm3.hip): when the last round is mostly empty its tiles run as `tail_split` parts each
             // inside the same launch (fp32 slabs + the deterministic fold, which also applies the epilogue).  Gated to narrow
             // outputs with a long reduction (N <= 1024, K >= 2048: fc2, the qkv / fc1 dgrads -- measured +2..6 %); at
@@ -568,10 +566,10 @@ GemmPlan plan_gemm(const me_gemm_desc* d, const GemmParams& p, bool allow_sk = t
         // workgroups (fp32 slabs + the deterministic fold that also applies the epilogue): 2 rounds + 1/3 instead of 3.
         // Measured: +4..5 % on the 256x256 kernel at N = 768 (fc2 forward, fc1 / qkv dgrad); a loss at N = 3072 (one
         // sparse round in ten is cheap: its workgroups run faster on an emptier chip) and on the two-workgroup kernel at
-        // K = 768 (slices too short) -- hence the fam == 3 / N <= 1024 gate.
+        // K = 768 (slices too short) -- hence the g2w / N <= 1024 gate.
         const int64_t tn_ = (d->N + pl.bn - 1) / pl.bn, tiles = tm * tn_;
         const int64_t R = tiles / SLOTS, rem = tiles - R * SLOTS;
-        if (fam == 3 && d->N <= 1024 && R >= 1 && rem * 20 >= SLOTS && rem * 10 <= SLOTS * 6 &&
+        if (fam == GEMM_G2W && d->N <= 1024 && R >= 1 && rem * 20 >= SLOTS && rem * 10 <= SLOTS * 6 &&
             d->res_row_mod == 0 && d->out_group_rows == 0 && d->M % pl.bm == 0) {
             const int64_t m_main = (R * SLOTS) / tn_;
             const int64_t tail_tiles = (tm - m_main) * tn_;
@@ -675,73 +673,169 @@ int fill_params(const me_gemm_desc* d, GemmParams& p) {
     return ME_OK;
 }
 
+// Everything that is decided about a descriptor before a launch, decided once: the validated parameter block (tiles counted in the
+// plan's tile), the plan, for a g3 NT problem the form of the whole problem (g3_form, gemm3.hip), and what the plan can serve.  The
+// planning queries of include/metaenc.h return these answers; gemm_impl turns a "no" into an error.
+struct GemmRoute {
+    GemmParams p;
+    GemmPlan pl;
+    G3Form form;             // (GEMM_G3, NT)
+    bool colsum_a = false;   // the bias gradient folds with the slabs of a split-K wgrad launch
+    bool a_wrap = false;     // a_wrap_k: the one-tile g3 kernel's wrapped-A instantiations
+    bool gg8 = false;        // ME_GG8 preact / aux: the resident kernel's eight-bit forms
+    bool row_parts = false;  // row_parts: the resident kernel's folded-LayerNorm epilogue on partials
+    bool row_stats_kernel = false, row_stats = false;      // row_stats: the resident residual kernel runs / ... and its partials are whole and addressable
+};
+
+int route_gemm(const me_gemm_desc* d, GemmRoute& r, bool allow_sk = true) {
+    GemmParams& p = r.p;
+    const int rc = fill_params(d, p);
+    if (rc) return rc;
+    const GemmPlan& pl = r.pl = plan_gemm(d, p, allow_sk);
+    if (pl.family != GEMM_G128) {
+        p.tiles_m = (int)((d->M + pl.bm - 1) / pl.bm);
+        p.tiles_n = (int)((d->N + pl.bn - 1) / pl.bn);
+    }
+    r.colsum_a = d->op == ME_GEMM_TN && ((pl.family == GEMM_G2B && pl.split_k > 1) || pl.family == GEMM_G3);
+    if (pl.family != GEMM_G3 || d->op != ME_GEMM_NT) return ME_OK;
+    const int cus = g3_cu_count();
+    r.form = g3_form(p, cus);
+    r.a_wrap = r.form.kernel == G3_ONE_TILE_WRAP;
+    r.gg8 = pl.tail_rows == 0 && r.form.kernel == G3_RESIDENT && r.form.pre == G3_PRE_GG8;
+    // (kept as found: the row_stats / row_parts answers have never looked at a_wrap_k -- they describe the descriptor without it.  No caller
+    // combines them; a descriptor that does is refused for its a_wrap_k when a row_stats epilogue is involved, and with row_parts runs the
+    // wrapped kernel's generic epilogue, which reads the partials as finished pairs.)
+    GemmParams pu = p;
+    pu.a_wrap_kt = 0;
+    const G3Form fu = g3_form(pu, cus);
+    const bool resident = pl.tail_rows == 0 && fu.kernel == G3_RESIDENT;      // (the form of the whole problem: not what a planned tail split launches)
+    r.row_parts = resident && fu.pre == G3_PRE_ROW_PARTS && p.M * 8 * 16 < (1ll << 31);
+    r.row_stats_kernel = resident && fu.repi == 2;
+    r.row_stats = r.row_stats_kernel && p.res_dtype == ME_BF16 && p.N % 256 == 0 && p.M * 8 < (1ll << 31);
+    return ME_OK;
+}
+
+// rows [m1, M) of p as a problem of their own: every row-indexed output / epilogue operand moves down by m1 rows (A stays the caller's)
+GemmParams tail_rows_of(const GemmParams& p, int64_t m1) {
+    GemmParams pt = p;
+    pt.M = p.M - m1;
+    pt.C = reinterpret_cast<char*>(p.C) + (size_t)m1 * p.ldc * me_dtype_size(p.c_dtype);
+    if (p.preact) pt.preact = reinterpret_cast<char*>(p.preact) + (size_t)m1 * p.ldpre * me_dtype_size(p.preact_dtype);
+    if (p.aux) pt.aux = reinterpret_cast<const char*>(p.aux) + (size_t)m1 * p.ldaux * me_dtype_size(p.aux_dtype);
+    if (p.residual) pt.residual = reinterpret_cast<const char*>(p.residual) + (size_t)m1 * p.ldres * me_dtype_size(p.res_dtype);
+    if (p.row_affine) pt.row_affine = p.row_affine + 2 * m1;
+    return pt;
+}
+
+// tn_launch: a replacement for launch_g3_tn (gemm_tn_with_launcher, gemm_host.h)
+int gemm_impl(const me_gemm_desc* d, hipStream_t stream, int* plan_out, GemmTnLaunch tn_launch = nullptr, const void* tn_ctx = nullptr) {
+    GemmRoute r;
+    int rc = route_gemm(d, r, tn_launch == nullptr);      // (the custom wgrad launchers -- patch embed, three planes -- walk uniform splits)
+    if (rc) return rc;
+    GemmParams& p = r.p;
+    const GemmPlan& pl = r.pl;
+    if (tn_launch && !(pl.family == GEMM_G3 && d->op == ME_GEMM_TN)) return ME_ERR_UNSUPPORTED;
+    const bool have_ws = pl.ws_bytes && d->workspace && (size_t)d->workspace_bytes >= pl.ws_bytes;
+    float* const ws = reinterpret_cast<float*>(d->workspace);
+    {   // me_gemm_profile_rec.plan
+        const int parts = pl.split_k > 1 ? pl.split_k : (pl.tail_rows > 0 ? pl.tail_split : 1);
+        *plan_out = (pl.family & 15) | ((have_ws && parts > 1) ? 16 : 0) | (pl.sk_wgs ? 32 : 0) | ((have_ws ? parts : 1) << 8);
+    }
+    if (d->colsum_a)
+        ME_CHECK_ARG(r.colsum_a && have_ws, "me_gemm: colsum_a needs the split-K wgrad kernel and its workspace (see me_gemm_fuses_colsum)");
+    // (kept as found: the kernel drops the partials of a ragged last column tile by itself, so me_gemm has never asked for N % 256 == 0 here;
+    //  and next to a_wrap_k only the family is asked -- the wrapped kernel then runs and writes no statistics)
+    if (d->row_stats)
+        ME_CHECK_ARG(d->a_wrap_k ? pl.family == GEMM_G3 && d->op == ME_GEMM_NT && pl.tail_rows == 0 : r.row_stats_kernel,
+                     "me_gemm: row_stats is not available for this problem (see me_gemm_emits_row_stats)");
+    if (d->a_wrap_k)
+        ME_CHECK_ARG(r.a_wrap, "me_gemm: a_wrap_k is not available for this problem (see me_gemm_takes_a_wrap)");
+    if (d->row_parts)
+        ME_CHECK_ARG(r.row_parts, "me_gemm: row_parts is not available for this problem (see me_gemm_takes_row_parts)");
+    if ((d->preact && d->preact_dtype == ME_GG8) || (d->aux && d->aux_dtype == ME_GG8))
+        ME_CHECK_ARG(r.gg8, "me_gemm: ME_GG8 is not available for this problem (see me_gemm_takes_gg8)");
+
+    if (pl.family == GEMM_G3 && d->op == ME_GEMM_TN) {      // ---- g3 wgrad (uniform or balanced partition) -> fold
+        ME_CHECK_ARG(have_ws, "me_gemm(TN, g3): workspace of me_gemm_workspace_bytes() required");
+        GemmParams ps = p;
+        ps.C = ws;
+        ps.split_k = pl.split_k;
+        ps.ksteps_per_split = pl.ksteps_per_split;
+        ps.slab_stride = g3_tn_slab_stride(d->M, d->N);
+        if (d->colsum_a) ps.colsum_ws = ws + (size_t)pl.split_k * (size_t)ps.slab_stride;
+        if (pl.sk_wgs) {
+            ps.sk_wgs = pl.sk_wgs; ps.sk_upt = pl.sk_upt; ps.sk_levels = pl.sk_levels; ps.sk_l1 = pl.sk_l1;
+            rc = launch_g3_tn_sk(ps, stream);
+            p.sk_wgs = pl.sk_wgs; p.sk_upt = pl.sk_upt; p.sk_levels = pl.sk_levels; p.sk_l1 = pl.sk_l1;      // (the fold sums each tile's own number of slabs)
+        } else {
+            rc = tn_launch ? tn_launch(ps, stream, tn_ctx) : launch_g3_tn(ps, stream);
+        }
+        if (rc) return rc;
+        launch_splitk_reduce(p, stream, ws, pl.split_k, ps.colsum_ws, pl.split_k * p.tiles_n, d->colsum_a, ps.slab_stride);
+        ME_CHECK_LAUNCH("me_gemm(g3 tn fold)");
+        return ME_OK;
+    }
+    if (pl.family == GEMM_G3) {                             // ---- g3 NT: whole, or main + tail K-parts in one launch -> fold of the tail
+        if (!(pl.tail_rows > 0 && have_ws)) return launch_g3(p, r.form, stream);
+        const int64_t m1 = d->M - pl.tail_rows;          // rows covered by whole tiles (a multiple of 256)
+        p.g3_full_tiles = (int)(m1 / 256) * p.tiles_n;
+        p.g3_split = pl.tail_split;
+        p.g3_ktp = pl.tail_ksteps;
+        p.g3_slabs = ws;
+        rc = launch_g3(p, g3_form(p, g3_cu_count()), stream);
+        if (rc) return rc;
+        GemmParams pt = tail_rows_of(p, m1);             // the fold sees the tail rows as its own problem
+        pt.A = nullptr;
+        launch_splitk_reduce(pt, stream, ws, pl.tail_split, nullptr, 0, nullptr);
+        ME_CHECK_LAUNCH("me_gemm(g3 tail fold)");
+        return ME_OK;
+    }
+    if (pl.family == GEMM_G128) {
+        if (d->ab_dtype == ME_BF16)
+            return d->op == ME_GEMM_NT ? launch_g128<bf16_t, false>(p, stream) : launch_g128<bf16_t, true>(p, stream);
+        return d->op == ME_GEMM_NT ? launch_g128<float, false>(p, stream) : launch_g128<float, true>(p, stream);
+    }
+    // ---- g2 family: plain, whole-problem split-K (wgrad), or main + tail split (a whole small problem is all tail)
+    auto run = [&](const GemmParams& q) { return launch_g2b(q, d->op, pl.bm, pl.bn, stream); };
+    p.ksteps_per_split = pl.ksteps_per_split;
+    if (pl.split_k > 1 && have_ws) {
+        GemmParams ps = p;
+        ps.C = ws;
+        ps.split_k = pl.split_k;
+        if (d->colsum_a) ps.colsum_ws = ws + (size_t)pl.split_k * (size_t)d->M * (size_t)d->N;
+        rc = run(ps);
+        if (rc) return rc;
+        launch_splitk_reduce(p, stream, ws, pl.split_k, ps.colsum_ws, pl.split_k * p.tiles_n, d->colsum_a);
+        ME_CHECK_LAUNCH("me_gemm(splitk reduce)");
+        return ME_OK;
+    }
+    p.ksteps_per_split = (int)(d->K / pl.kstep);
+    if (!(pl.tail_rows > 0 && have_ws)) return run(p);
+    const int64_t m1 = d->M - pl.tail_rows;
+    if (m1 > 0) {
+        GemmParams pm = p;                   // main part: rows [0, m1), fused epilogue as usual
+        pm.M = m1;
+        pm.tiles_m = (int)(m1 / pl.bm);
+        rc = run(pm);
+        if (rc) return rc;
+    }
+    GemmParams pt = tail_rows_of(p, m1);     // tail: rows [m1, M)
+    pt.tiles_m = (int)((pl.tail_rows + pl.bm - 1) / pl.bm);
+    pt.A = reinterpret_cast<const char*>(p.A) + (size_t)m1 * p.lda * me_dtype_size(d->ab_dtype);
+    GemmParams ps = pt;                      // the split launch writes slabs [S][tail_rows][N]
+    ps.C = ws;
+    ps.split_k = pl.tail_split;
+    ps.ksteps_per_split = pl.tail_ksteps;
+    rc = run(ps);
+    if (rc) return rc;
+    launch_splitk_reduce(pt, stream, ws, pl.tail_split, nullptr, 0, nullptr);
+    ME_CHECK_LAUNCH("me_gemm(tail fold)");
+    return ME_OK;
+}
+
 }  // namespace
 
-// (patch_embed.hip: the same validation and parameter block for the projection it runs on its own kernel)
 int gemm_fill_params(const me_gemm_desc* d, GemmParams& p) { return fill_params(d, p); }
-
-extern "C" size_t me_gemm_workspace_bytes(const me_gemm_desc* d) {
-    GemmParams p;
-    if (fill_params(d, p) != ME_OK) return 0;
-    return plan_gemm(d, p).ws_bytes;
-}
-
-extern "C" int me_gemm_fuses_colsum(const me_gemm_desc* d) {
-    GemmParams p;
-    if (!d || d->op != ME_GEMM_TN || fill_params(d, p) != ME_OK) return 0;
-    const GemmPlan pl = plan_gemm(d, p);
-    return (pl.family == 2 && pl.split_k > 1) || pl.family == 4;
-}
-
-extern "C" int me_gemm_emits_row_stats(const me_gemm_desc* d) {
-    GemmParams p;
-    if (!d || d->op != ME_GEMM_NT || d->ab_dtype != ME_BF16 || !d->residual) return 0;
-    me_gemm_desc e = *d;
-    e.row_stats = nullptr;
-    if (fill_params(&e, p) != ME_OK) return 0;
-    const GemmPlan pl = plan_gemm(&e, p);
-    if (pl.family != 4 || pl.tail_rows > 0) return 0;
-    p.tiles_m = (int)((d->M + 255) / 256);
-    p.tiles_n = (int)((d->N + 255) / 256);
-    return g3_emits_row_stats(p) ? 1 : 0;
-}
-
-extern "C" int me_gemm_takes_a_wrap(const me_gemm_desc* d) {
-    GemmParams p;
-    if (!d || d->op != ME_GEMM_NT || d->ab_dtype != ME_BF16 || !d->a_wrap_k || fill_params(d, p) != ME_OK) return 0;
-    const GemmPlan pl = plan_gemm(d, p);
-    const int e = pick_epi_ex(p);
-    return (pl.family == 4 && (e == 0 || e == 4 || e == 8)) ? 1 : 0;
-}
-
-extern "C" int me_gemm_reserve_cus(int cus) {
-    const int c = cus < 0 ? 0 : (cus > 128 ? 128 : cus);
-    return g_reserved_cus.exchange(c);
-}
-
-extern "C" int me_gemm_takes_row_parts(const me_gemm_desc* d) {
-    GemmParams p;
-    if (!d || d->op != ME_GEMM_NT || d->ab_dtype != ME_BF16 || !d->row_parts || fill_params(d, p) != ME_OK) return 0;
-    const GemmPlan pl = plan_gemm(d, p);
-    if (pl.family != 4 || pl.tail_rows > 0) return 0;
-    return g3_takes_row_parts(p) ? 1 : 0;
-}
-
-extern "C" int me_gemm_takes_gg8(const me_gemm_desc* d) {
-    GemmParams p;
-    if (!d || d->op != ME_GEMM_NT || d->ab_dtype != ME_BF16 || fill_params(d, p) != ME_OK) return 0;
-    if (!((d->preact && d->preact_dtype == ME_GG8) || (d->aux && d->aux_dtype == ME_GG8))) return 0;
-    const GemmPlan pl = plan_gemm(d, p);
-    if (pl.family != 4 || pl.tail_rows > 0) return 0;
-    return g3_takes_gg8(p) ? 1 : 0;
-}
-
-namespace {
-// tn_launch: a replacement for launch_g3_tn (patch_embed.hip: the wgrad kernel that gathers its B operand from the image); with it,
-// a problem the planner does not give to the g3 wgrad family is refused (ME_ERR_UNSUPPORTED) instead of run
-typedef int (*TnLaunch)(const GemmParams& p, hipStream_t stream, const void* ctx);
-int gemm_impl(const me_gemm_desc* d, hipStream_t stream, int* plan_out, TnLaunch tn_launch = nullptr, const void* tn_ctx = nullptr);
-}
 
 extern "C" int me_gemm(const me_gemm_desc* d, void* stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -749,162 +843,51 @@ extern "C" int me_gemm(const me_gemm_desc* d, void* stream_) {
     return gemm_impl(d, stream, &prof.plan);
 }
 
-namespace {
-int gemm_impl(const me_gemm_desc* d, hipStream_t stream, int* plan_out, TnLaunch tn_launch, const void* tn_ctx) {
-    GemmParams p;
-    int rc = fill_params(d, p);
-    if (rc) return rc;
-    GemmPlan pl = plan_gemm(d, p, tn_launch == nullptr);      // (the custom wgrad launchers -- patch embed, three planes -- walk uniform splits)
-    if (tn_launch && !(pl.family == 4 && d->op == ME_GEMM_TN)) return ME_ERR_UNSUPPORTED;
-    {   // me_gemm_profile_rec.plan
-        const bool have_ws = pl.ws_bytes && d->workspace && (size_t)d->workspace_bytes >= pl.ws_bytes;
-        const int parts = pl.split_k > 1 ? pl.split_k : (pl.tail_rows > 0 ? pl.tail_split : 1);
-        *plan_out = (pl.family & 15) | ((have_ws && parts > 1) ? 16 : 0) | (pl.sk_wgs ? 32 : 0) | ((have_ws ? parts : 1) << 8);
-    }
-    if (d->colsum_a)
-        ME_CHECK_ARG(((pl.family == 2 && pl.split_k > 1) || pl.family == 4) && d->workspace && (size_t)d->workspace_bytes >= pl.ws_bytes,
-                     "me_gemm: colsum_a needs the split-K wgrad kernel and its workspace (see me_gemm_fuses_colsum)");
-    if (d->row_stats)
-        ME_CHECK_ARG(pl.family == 4 && d->op == ME_GEMM_NT && pl.tail_rows == 0, "me_gemm: row_stats is not available for this problem (see me_gemm_emits_row_stats)");
-    if (d->a_wrap_k)
-        ME_CHECK_ARG(pl.family == 4 && d->op == ME_GEMM_NT && (pick_epi_ex(p) == 0 || pick_epi_ex(p) == 4 || pick_epi_ex(p) == 8),
-                     "me_gemm: a_wrap_k is not available for this problem (see me_gemm_takes_a_wrap)");
-    if (d->row_parts)
-        ME_CHECK_ARG(pl.family == 4 && d->op == ME_GEMM_NT && pl.tail_rows == 0 && g3_takes_row_parts(p),
-                     "me_gemm: row_parts is not available for this problem (see me_gemm_takes_row_parts)");
-    if ((d->preact && d->preact_dtype == ME_GG8) || (d->aux && d->aux_dtype == ME_GG8))
-        ME_CHECK_ARG(pl.family == 4 && d->op == ME_GEMM_NT && pl.tail_rows == 0 && g3_takes_gg8(p),
-                     "me_gemm: ME_GG8 is not available for this problem (see me_gemm_takes_gg8)");
-    if (pl.family >= 1) {
-        if (pl.family == 4 && d->op == ME_GEMM_TN) {
-            ME_CHECK_ARG(d->workspace && (size_t)d->workspace_bytes >= pl.ws_bytes,
-                         "me_gemm(TN, g3): workspace of me_gemm_workspace_bytes() required");
-            p.tiles_m = (int)((d->M + 255) / 256);
-            p.tiles_n = (int)((d->N + 255) / 256);
-            GemmParams ps = p;
-            ps.C = d->workspace;
-            ps.split_k = pl.split_k;
-            ps.ksteps_per_split = pl.ksteps_per_split;
-            ps.slab_stride = g3_tn_slab_stride(d->M, d->N);
-            if (d->colsum_a) ps.colsum_ws = reinterpret_cast<float*>(d->workspace) + (size_t)pl.split_k * (size_t)ps.slab_stride;
-            if (pl.sk_wgs) {
-                ps.sk_wgs = pl.sk_wgs; ps.sk_upt = pl.sk_upt; ps.sk_levels = pl.sk_levels; ps.sk_l1 = pl.sk_l1;
-                rc = launch_g3_tn_sk(ps, stream);
-                p.sk_wgs = pl.sk_wgs; p.sk_upt = pl.sk_upt; p.sk_levels = pl.sk_levels; p.sk_l1 = pl.sk_l1;      // (the fold sums each tile's own number of slabs)
-            } else {
-                rc = tn_launch ? tn_launch(ps, stream, tn_ctx) : launch_g3_tn(ps, stream);
-            }
-            if (rc) return rc;
-            p.split_k = 1;
-            const int64_t quads = d->M * (d->N / 4);
-            int64_t nb = (quads + 255) / 256;
-            if (nb > 2048) nb = 2048;
-            launch_splitk_reduce(p, (unsigned)nb, stream, reinterpret_cast<const float*>(d->workspace), pl.split_k, ps.colsum_ws, pl.split_k * p.tiles_n,
-                               d->colsum_a, ps.slab_stride);
-            ME_CHECK_LAUNCH("me_gemm(g3 tn fold)");
-            return ME_OK;
-        }
-        if (pl.family == 4) {
-            p.tiles_m = (int)((d->M + 255) / 256);
-            p.tiles_n = (int)((d->N + 255) / 256);
-            p.split_k = 1;
-            const bool have_ws = pl.ws_bytes && d->workspace && (size_t)d->workspace_bytes >= pl.ws_bytes;
-            p.g3_full_tiles = p.tiles_m * p.tiles_n; p.g3_split = 1; p.g3_ktp = 0; p.g3_slabs = nullptr;
-            if (pl.tail_rows > 0 && have_ws) {
-                const int64_t m1 = d->M - pl.tail_rows;          // rows covered by whole tiles (a multiple of 256)
-                p.g3_full_tiles = (int)(m1 / 256) * p.tiles_n;
-                p.g3_split = pl.tail_split;
-                p.g3_ktp = pl.tail_ksteps;
-                p.g3_slabs = reinterpret_cast<float*>(d->workspace);
-                rc = launch_g3(p, pick_epi_ex(p), stream);
-                if (rc) return rc;
-                GemmParams pt = p;                               // the fold sees the tail rows as its own problem
-                pt.M = pl.tail_rows;
-                pt.split_k = 1;
-                pt.A = nullptr;
-                pt.C = reinterpret_cast<char*>(p.C) + (size_t)m1 * p.ldc * me_dtype_size(p.c_dtype);
-                if (p.preact) pt.preact = reinterpret_cast<char*>(p.preact) + (size_t)m1 * p.ldpre * me_dtype_size(p.preact_dtype);
-                if (p.aux) pt.aux = reinterpret_cast<const char*>(p.aux) + (size_t)m1 * p.ldaux * me_dtype_size(p.aux_dtype);
-                if (p.residual) pt.residual = reinterpret_cast<const char*>(p.residual) + (size_t)m1 * p.ldres * me_dtype_size(p.res_dtype);
-                if (p.row_affine) pt.row_affine = p.row_affine + 2 * m1;
-                const int64_t quads = pt.M * (d->N / 4);
-                int64_t nb = (quads + 255) / 256;
-                if (nb > 2048) nb = 2048;
-                launch_splitk_reduce(pt, (unsigned)nb, stream, reinterpret_cast<const float*>(d->workspace), pl.tail_split, nullptr, 0, nullptr);
-                ME_CHECK_LAUNCH("me_gemm(g3 tail fold)");
-                return ME_OK;
-            }
-            return launch_g3(p, pick_epi_ex(p), stream);
-        }
-        auto run = [&](const GemmParams& q) { return launch_g2b(q, d->op, pl.bm, pl.bn, stream); };
-        p.tiles_m = (int)((d->M + pl.bm - 1) / pl.bm);
-        p.tiles_n = (int)((d->N + pl.bn - 1) / pl.bn);
-        p.ksteps_per_split = pl.ksteps_per_split;
-        if (pl.split_k > 1 && d->workspace && (size_t)d->workspace_bytes >= pl.ws_bytes) {
-            GemmParams ps = p;
-            ps.C = d->workspace;
-            ps.split_k = pl.split_k;
-            const int n_part = pl.split_k * p.tiles_n;
-            if (d->colsum_a)
-                ps.colsum_ws = reinterpret_cast<float*>(d->workspace) + (size_t)pl.split_k * (size_t)d->M * (size_t)d->N;
-            rc = run(ps);
-            if (rc) return rc;
-            const int64_t quads = d->M * (d->N / 4);
-            int64_t nb = (quads + 255) / 256;
-            if (nb > 2048) nb = 2048;
-            launch_splitk_reduce(p, (unsigned)nb, stream, reinterpret_cast<const float*>(d->workspace), pl.split_k, ps.colsum_ws, n_part,
-                               d->colsum_a);
-            ME_CHECK_LAUNCH("me_gemm(splitk reduce)");
-            return ME_OK;
-        }
-        p.split_k = 1;
-        p.ksteps_per_split = (int)(d->K / pl.kstep);
-        if (pl.tail_rows > 0 && d->workspace && (size_t)d->workspace_bytes >= pl.ws_bytes) {
-            const int64_t m1 = d->M - pl.tail_rows;
-            if (m1 > 0) {
-                GemmParams pm = p;                   // main part: rows [0, m1), fused epilogue as usual
-                pm.M = m1;
-                pm.tiles_m = (int)(m1 / pl.bm);
-                rc = run(pm);
-                if (rc) return rc;
-            }
-            GemmParams pt = p;                       // tail: rows [m1, M) -- every row-indexed operand moves down by m1
-            pt.M = pl.tail_rows;
-            pt.tiles_m = (int)((pl.tail_rows + pl.bm - 1) / pl.bm);
-            pt.A = reinterpret_cast<const char*>(p.A) + (size_t)m1 * p.lda * me_dtype_size(d->ab_dtype);
-            pt.C = reinterpret_cast<char*>(p.C) + (size_t)m1 * p.ldc * me_dtype_size(p.c_dtype);
-            if (p.preact) pt.preact = reinterpret_cast<char*>(p.preact) + (size_t)m1 * p.ldpre * me_dtype_size(p.preact_dtype);
-            if (p.aux) pt.aux = reinterpret_cast<const char*>(p.aux) + (size_t)m1 * p.ldaux * me_dtype_size(p.aux_dtype);
-            if (p.residual) pt.residual = reinterpret_cast<const char*>(p.residual) + (size_t)m1 * p.ldres * me_dtype_size(p.res_dtype);
-            if (p.row_affine) pt.row_affine = p.row_affine + 2 * m1;
-            GemmParams ps = pt;                      // the split launch writes slabs [S][tail_rows][N]
-            ps.C = d->workspace;
-            ps.split_k = pl.tail_split;
-            ps.ksteps_per_split = pl.tail_ksteps;
-            rc = run(ps);
-            if (rc) return rc;
-            const int64_t quads = pt.M * (d->N / 4);
-            int64_t nb = (quads + 255) / 256;
-            if (nb > 2048) nb = 2048;
-            launch_splitk_reduce(pt, (unsigned)nb, stream, reinterpret_cast<const float*>(d->workspace), pl.tail_split, nullptr, 0, nullptr);
-            ME_CHECK_LAUNCH("me_gemm(tail fold)");
-            return ME_OK;
-        }
-        return run(p);
-    }
-    if (d->ab_dtype == ME_BF16)
-        return d->op == ME_GEMM_NT ? launch_g128<bf16_t, false>(p, stream) : launch_g128<bf16_t, true>(p, stream);
-    return d->op == ME_GEMM_NT ? launch_g128<float, false>(p, stream) : launch_g128<float, true>(p, stream);
-}
-}  // namespace
-
-// (patch_embed.hip) me_gemm for a g3 wgrad problem with the split-K kernel launch replaced; 1 / 0: would the planner take that route
-int gemm_tn_with_launcher(const me_gemm_desc* d, hipStream_t stream, int (*launch)(const GemmParams&, hipStream_t, const void*), const void* ctx) {
+int gemm_tn_with_launcher(const me_gemm_desc* d, hipStream_t stream, GemmTnLaunch launch, const void* ctx) {
     ProfScope prof(d ? d->op : 0, d ? d->ab_dtype : 0, d ? d->M : 0, d ? d->N : 0, d ? d->K : 0, stream);
     return gemm_impl(d, stream, &prof.plan, launch, ctx);
 }
+
+extern "C" int me_gemm_reserve_cus(int cus) {
+    const int c = cus < 0 ? 0 : (cus > 128 ? 128 : cus);
+    return g_reserved_cus.exchange(c);
+}
+
+// ---- the planning queries: each one answer of route_gemm
+extern "C" size_t me_gemm_workspace_bytes(const me_gemm_desc* d) {
+    GemmRoute r;
+    return route_gemm(d, r) == ME_OK ? r.pl.ws_bytes : 0;
+}
+
 int gemm_tn_is_g3(const me_gemm_desc* d) {
-    GemmParams p;
-    if (!d || d->op != ME_GEMM_TN || fill_params(d, p) != ME_OK) return 0;
-    return plan_gemm(d, p).family == 4 ? 1 : 0;
+    GemmRoute r;
+    return d && d->op == ME_GEMM_TN && route_gemm(d, r) == ME_OK && r.pl.family == GEMM_G3;
+}
+
+extern "C" int me_gemm_fuses_colsum(const me_gemm_desc* d) {
+    GemmRoute r;
+    return route_gemm(d, r) == ME_OK && r.colsum_a;
+}
+
+extern "C" int me_gemm_emits_row_stats(const me_gemm_desc* d) {
+    if (!d) return 0;
+    me_gemm_desc e = *d;
+    e.row_stats = nullptr;      // (asked before the buffer exists)
+    GemmRoute r;
+    return route_gemm(&e, r) == ME_OK && r.row_stats;
+}
+
+extern "C" int me_gemm_takes_a_wrap(const me_gemm_desc* d) {
+    GemmRoute r;
+    return route_gemm(d, r) == ME_OK && r.a_wrap;
+}
+
+extern "C" int me_gemm_takes_row_parts(const me_gemm_desc* d) {
+    GemmRoute r;
+    return route_gemm(d, r) == ME_OK && r.row_parts;
+}
+
+extern "C" int me_gemm_takes_gg8(const me_gemm_desc* d) {
+    GemmRoute r;
+    return route_gemm(d, r) == ME_OK && r.gg8;
 }

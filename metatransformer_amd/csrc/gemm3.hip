@@ -1021,76 +1021,31 @@ template <int EPI, int PRE> int launch3r(const GemmParams& q0, int G, hipStream_
 
 int launch3r_any(int epi, int pre, const GemmParams& q, int G, hipStream_t stream) {
     switch (epi) {
-        case 0: return pre == 5 ? launch3r<0, 5>(q, G, stream) : pre == 3 ? launch3r<0, 3>(q, G, stream) : launch3r<0, 0>(q, G, stream);
-        case 1: return pre == 6 ? launch3r<1, 6>(q, G, stream) : pre == 5 ? launch3r<1, 5>(q, G, stream) : pre == 3 ? launch3r<1, 3>(q, G, stream) : pre == 2 ? launch3r<1, 2>(q, G, stream) : pre ? launch3r<1, 1>(q, G, stream) : launch3r<1, 0>(q, G, stream);
-        case 2: return pre == 4 ? launch3r<2, 4>(q, G, stream) : launch3r<2, 0>(q, G, stream);
-        case 3: return launch3r<3, 0>(q, G, stream);
-        default: return pre == 6 ? launch3r<6, 6>(q, G, stream) : launch3r<6, 0>(q, G, stream);
+        case 0: return pre == G3_PRE_ROW_PARTS ? launch3r<0, G3_PRE_ROW_PARTS>(q, G, stream) : pre == G3_PRE_ROW_AFFINE ? launch3r<0, G3_PRE_ROW_AFFINE>(q, G, stream) : launch3r<0, G3_PRE_NONE>(q, G, stream);
+        case 1: return pre == G3_PRE_GG8 ? launch3r<1, G3_PRE_GG8>(q, G, stream) : pre == G3_PRE_ROW_PARTS ? launch3r<1, G3_PRE_ROW_PARTS>(q, G, stream) :
+                       pre == G3_PRE_ROW_AFFINE ? launch3r<1, G3_PRE_ROW_AFFINE>(q, G, stream) : pre == G3_PRE_SAVE_GELU_GRAD ? launch3r<1, G3_PRE_SAVE_GELU_GRAD>(q, G, stream) :
+                       pre ? launch3r<1, G3_PRE_SAVE_PREACT>(q, G, stream) : launch3r<1, G3_PRE_NONE>(q, G, stream);
+        case 2: return pre == G3_PRE_ROW_STATS ? launch3r<2, G3_PRE_ROW_STATS>(q, G, stream) : launch3r<2, G3_PRE_NONE>(q, G, stream);
+        case 3: return launch3r<3, G3_PRE_NONE>(q, G, stream);
+        default: return pre == G3_PRE_GG8 ? launch3r<6, G3_PRE_GG8>(q, G, stream) : launch3r<6, G3_PRE_NONE>(q, G, stream);
     }
 }
 
-template <int EPI> int launch3e(const GemmParams& p, hipStream_t stream) {
+// one tile (or one K-part of a split tail tile) per workgroup
+template <int EPI, bool WRAP> int launch3t(const GemmParams& q, int nwg, hipStream_t stream) {
     static OncePerDevice once;
-    if (once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g3_kernel<EPI>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
-    }
-    const int tiles = p.tiles_m * p.tiles_n;
-    GemmParams q = p;
-    if (q.g3_split <= 1 || q.g3_slabs == nullptr) { q.g3_full_tiles = tiles; q.g3_split = 1; q.g3_ktp = 0; q.g3_slabs = nullptr; }
-    const int nwg = q.g3_full_tiles + (tiles - q.g3_full_tiles) * q.g3_split;
-    // the resident form (one workgroup per CU, operand stream running through the epilogues) whenever every CU gets work
-    // and the output / row operands are bf16 with tile-local 32-bit offsets
-    if (p.a_wrap_kt) {
-        // A held as two planes [hi | lo], three reduction segments (me_gemm_desc.a_wrap_k): the one-tile kernel's WRAP instantiations only
-        if constexpr (EPI == 0 || EPI == 4 || EPI == 8) {
-            static OncePerDevice once_w;
-            if (once_w.need())
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g3_kernel<EPI, true>), hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
-            hipLaunchKernelGGL((gemm_g3_kernel<EPI, true>), dim3((unsigned)nwg), dim3(512), G3_LDS, stream, q);
-            ME_CHECK_LAUNCH("me_gemm(g3, wrapped A)");
-            return ME_OK;
-        } else {
-            me_set_error("me_gemm: a_wrap_k is served for plain / fp32-residual epilogues only (see me_gemm_takes_a_wrap)");
-            return ME_ERR_UNSUPPORTED;
-        }
-    }
-    int repi = EPI <= 3 ? EPI : -1, pre = (EPI == 1 && p.preact) ? 1 : 0;
-    const bool plain = p.beta == 0.0f && p.out_group_rows == 0 && p.res_row_mod == 0 && !p.colscale && !p.residual;
-    if (EPI == 4 && p.row_affine && !p.flags && plain && !p.preact && !p.aux) {       // folded LayerNorm (bias / GELU forms)
-        repi = p.act == ME_ACT_GELU ? 1 : 0;
-        pre = p.row_nparts ? 5 : 3;       // (5: row_affine holds the 64-column partials of the launch in front, see g3_epilogue_r)
-    }
-    if (EPI == 4 && p.flags && !p.row_affine) {
-        // the two halves of the "save gelu'" pair (pick_epi sends flagged descriptors to the generic epilogue)
-        if (plain && p.flags == ME_GEMM_SAVE_GELU_GRAD && p.act == ME_ACT_GELU && p.preact && !p.aux) { repi = 1; pre = 2; }
-        if (plain && p.flags == ME_GEMM_AUX_IS_FACTOR && p.act == ME_ACT_NONE && p.aux && (p.aux_dtype == ME_BF16 || p.aux_dtype == ME_GG8) && !p.preact) repi = 6;
-    }
-    if (EPI == 6) repi = 6;                                   // (pick_epi_ex has checked the same conditions)
-    if (EPI == 7) { repi = 1; pre = 2; }
-    if (repi == 1 && pre == 2 && p.preact_dtype == ME_GG8) pre = 6;       // gelu' in eight bits, both halves of the pair
-    if (repi == 6 && p.aux_dtype == ME_GG8) pre = 6;
-    if (EPI == 2 && p.row_stats) pre = 4;
-    const int G = g3_cus() & ~7;
-    const int64_t ldmax = std::max(std::max(p.ldc, p.preact ? p.ldpre : 0), std::max(p.residual ? p.ldres : 0, p.aux ? p.ldaux : 0));
-    if (repi >= 0 && !p.colscale && G >= 8 && nwg >= G && q.g3_split <= 1 && p.alpha == 1.0f && p.c_dtype == ME_BF16 && (!(pre == 1 || pre == 2) || p.preact_dtype == ME_BF16) && (pre != 6 || !p.preact || p.ldpre % 8 == 0) &&
-        256 * ldmax * 2 < (1ll << 31))
-        return launch3r_any(repi, pre, q, G, stream);
-    if (p.row_stats) {
-        me_set_error("me_gemm: row_stats needs the resident residual kernel (see me_gemm_emits_row_stats)");
-        return ME_ERR_UNSUPPORTED;
-    }
-    if (p.row_nparts) {
-        me_set_error("me_gemm: row_parts needs the resident kernel's folded-LayerNorm epilogue (see me_gemm_takes_row_parts)");
-        return ME_ERR_UNSUPPORTED;
-    }
-    if ((p.preact && p.preact_dtype == ME_GG8) || (p.aux && p.aux_dtype == ME_GG8)) {
-        me_set_error("me_gemm: ME_GG8 needs the resident kernel (see me_gemm_takes_gg8)");
-        return ME_ERR_UNSUPPORTED;
-    }
-    hipLaunchKernelGGL((gemm_g3_kernel<EPI>), dim3((unsigned)nwg), dim3(512), G3_LDS, stream, q);
-    ME_CHECK_LAUNCH("me_gemm(g3)");
+    if (once.need())
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g3_kernel<EPI, WRAP>), hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
+    hipLaunchKernelGGL((gemm_g3_kernel<EPI, WRAP>), dim3((unsigned)nwg), dim3(512), G3_LDS, stream, q);
+    ME_CHECK_LAUNCH(WRAP ? "me_gemm(g3, wrapped A)" : "me_gemm(g3)");
     return ME_OK;
+}
+
+template <int EPI> int launch3e(const GemmParams& q, const G3Form& f, hipStream_t stream) {
+    // (A held as two planes [hi | lo], three reduction segments: the plain / generic / fp32-residual epilogues only -- g3_form)
+    if constexpr (EPI == 0 || EPI == 4 || EPI == 8)
+        if (f.kernel == G3_ONE_TILE_WRAP) return launch3t<EPI, true>(q, f.nwg, stream);
+    return launch3t<EPI, false>(q, f.nwg, stream);
 }
 
 }  // namespace
@@ -1133,53 +1088,72 @@ bool g3_supported(const GemmParams& p, int op) {
     return true;
 }
 
-// Will launch_g3(p, 2, ..) run the resident residual kernel, i.e. can p.row_stats be served?  (the conditions of launch3e, restated
-// for a descriptor that has not been planned yet: whole tiles, every CU gets one, bf16 output and residual, plain epilogue)
-bool g3_emits_row_stats(const GemmParams& p) {
-    if (!g3_supported(p, ME_GEMM_NT) || pick_epi(p) != 2 || p.colscale) return false;
-    const int G = g3_cus() & ~7;
-    const int64_t tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-    const int64_t ldmax = std::max(p.ldc, p.ldres);
-    return G >= 8 && tiles >= G && p.alpha == 1.0f && p.c_dtype == ME_BF16 && p.res_dtype == ME_BF16 && p.N % 256 == 0 &&
-           256 * ldmax * 2 < (1ll << 31) && p.M * 8 < (1ll << 31);
+int g3_cu_count() { return g3_cus(); }
+
+// The one place that says which NT kernel a descriptor runs on.  The resident form (one workgroup per CU, operand stream running
+// through the epilogues) whenever one of its (EPI, PRE) instantiations covers the epilogue, every CU gets work and the output / row
+// operands are bf16 with tile-local 32-bit offsets; else the one-tile kernel -- which cannot emit row statistics, fold LayerNorm
+// partials or read / write ME_GG8.
+G3Form g3_form(const GemmParams& p, int cus) {
+    G3Form f;
+    const int e = pick_epi_ex(p);
+    // (the residual forms carry the column scale -- layer-scale Blocks; the others do not: generic epilogue)
+    f.epi = (p.colscale && e != 2 && e != 8) || !((e >= 0 && e <= 3) || (e >= 6 && e <= 10)) ? 4 : e;
+    const int EPI = f.epi, tiles = p.tiles_m * p.tiles_n;
+    const bool split = p.g3_split > 1 && p.g3_slabs != nullptr;      // tiles [g3_full_tiles, tiles) run as g3_split K-parts each
+    f.nwg = split ? p.g3_full_tiles + (tiles - p.g3_full_tiles) * p.g3_split : tiles;
+    f.G = cus & ~7;
+    if (p.a_wrap_kt) {      // A as two planes [hi | lo], three reduction segments: plain / generic / fp32-residual epilogues (asked of e: before the column-scale rule)
+        f.kernel = (e == 0 || e == 4 || e == 8) ? G3_ONE_TILE_WRAP : G3_UNSUPPORTED;
+        return f;
+    }
+    f.repi = EPI <= 3 ? EPI : -1;
+    f.pre = (EPI == 1 && p.preact) ? G3_PRE_SAVE_PREACT : G3_PRE_NONE;
+    const bool plain = p.beta == 0.0f && p.out_group_rows == 0 && p.res_row_mod == 0 && !p.colscale && !p.residual;
+    if (EPI == 4 && p.row_affine && !p.flags && plain && !p.preact && !p.aux) {       // folded LayerNorm (bias / GELU forms)
+        f.repi = p.act == ME_ACT_GELU ? 1 : 0;
+        f.pre = p.row_nparts ? G3_PRE_ROW_PARTS : G3_PRE_ROW_AFFINE;       // (parts: row_affine holds the 64-column partials of the launch in front, see g3_epilogue_r)
+    }
+    if (EPI == 4 && p.flags && !p.row_affine) {
+        // the two halves of the "save gelu'" pair (pick_epi sends flagged descriptors to the generic epilogue)
+        if (plain && p.flags == ME_GEMM_SAVE_GELU_GRAD && p.act == ME_ACT_GELU && p.preact && !p.aux) { f.repi = 1; f.pre = G3_PRE_SAVE_GELU_GRAD; }
+        if (plain && p.flags == ME_GEMM_AUX_IS_FACTOR && p.act == ME_ACT_NONE && p.aux && (p.aux_dtype == ME_BF16 || p.aux_dtype == ME_GG8) && !p.preact) f.repi = 6;
+    }
+    if (EPI == 6) f.repi = 6;                                   // (pick_epi_ex has checked the same conditions)
+    if (EPI == 7) { f.repi = 1; f.pre = G3_PRE_SAVE_GELU_GRAD; }
+    if (f.repi == 1 && f.pre == G3_PRE_SAVE_GELU_GRAD && p.preact_dtype == ME_GG8) f.pre = G3_PRE_GG8;       // gelu' in eight bits, both halves of the pair
+    if (f.repi == 6 && p.aux_dtype == ME_GG8) f.pre = G3_PRE_GG8;
+    if (EPI == 2 && p.row_stats) f.pre = G3_PRE_ROW_STATS;
+    const int64_t ldmax = std::max(std::max(p.ldc, p.preact ? p.ldpre : 0), std::max(p.residual ? p.ldres : 0, p.aux ? p.ldaux : 0));
+    const bool bf16_preact = !(f.pre == G3_PRE_SAVE_PREACT || f.pre == G3_PRE_SAVE_GELU_GRAD) || p.preact_dtype == ME_BF16;
+    const bool gg8_rows = f.pre != G3_PRE_GG8 || !p.preact || p.ldpre % 8 == 0;
+    const bool resident_only = p.row_stats || p.row_nparts || (p.preact && p.preact_dtype == ME_GG8) || (p.aux && p.aux_dtype == ME_GG8);
+    if (f.repi >= 0 && !p.colscale && f.G >= 8 && f.nwg >= f.G && !split && p.alpha == 1.0f && p.c_dtype == ME_BF16 && bf16_preact && gg8_rows &&
+        256 * ldmax * 2 < (1ll << 31))
+        f.kernel = G3_RESIDENT;
+    else
+        f.kernel = resident_only ? G3_UNSUPPORTED : G3_ONE_TILE;
+    return f;
 }
 
-// Will launch_g3 run the resident kernel's folded-LayerNorm epilogue on partials (PRE 5), i.e. can me_gemm_desc.row_parts be served?
-// (the conditions of launch3e restated, as above; p.row_affine / row_nparts / col_shift already set by fill_params)
-bool g3_takes_row_parts(const GemmParams& p) {
-    if (!g3_supported(p, ME_GEMM_NT) || !p.row_affine || !p.col_shift) return false;
-    if (p.row_nparts < 1 || p.row_nparts > 4 || (int64_t)p.row_nparts * 256 != p.K) return false;
-    if (p.flags || p.preact || p.aux || p.residual || p.colscale || p.beta != 0.0f || p.out_group_rows != 0 || p.res_row_mod != 0) return false;
-    const int G = g3_cus() & ~7;
-    const int64_t tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-    return G >= 8 && tiles >= G && p.alpha == 1.0f && p.c_dtype == ME_BF16 && 256 * p.ldc * 2 < (1ll << 31) && p.M * 8 * 16 < (1ll << 31);
-}
-
-// ME_GG8 (gelu' in eight bits): the two flagged descriptors of the training MLP, when launch3e sends them to the resident kernel
-bool g3_takes_gg8(const GemmParams& p) {
-    if (!g3_supported(p, ME_GEMM_NT)) return false;
-    if (p.row_affine || p.residual || p.colscale || p.beta != 0.0f || p.out_group_rows != 0 || p.res_row_mod != 0 || p.a_wrap_kt) return false;
-    const bool save = p.flags == ME_GEMM_SAVE_GELU_GRAD && p.act == ME_ACT_GELU && p.preact && p.preact_dtype == ME_GG8 && !p.aux;
-    const bool load = p.flags == ME_GEMM_AUX_IS_FACTOR && p.act == ME_ACT_NONE && p.aux && p.aux_dtype == ME_GG8 && !p.preact;
-    if (!save && !load) return false;
-    const int G = g3_cus() & ~7;
-    const int64_t tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-    const int64_t ldmax = std::max(p.ldc, save ? p.ldpre : p.ldaux);
-    return G >= 8 && tiles >= G && p.alpha == 1.0f && p.c_dtype == ME_BF16 && 256 * ldmax * 2 < (1ll << 31);
-}
-
-int launch_g3(const GemmParams& p, int epi, hipStream_t stream) {
-    if (p.colscale && epi != 2 && epi != 8) epi = 4;      // (the residual forms carry the column scale -- layer-scale Blocks; the others do not)
-    switch (epi) {
-        case 0: return launch3e<0>(p, stream);
-        case 1: return launch3e<1>(p, stream);
-        case 2: return launch3e<2>(p, stream);
-        case 3: return launch3e<3>(p, stream);
-        case 6: return launch3e<6>(p, stream);
-        case 7: return launch3e<7>(p, stream);
-        case 8: return launch3e<8>(p, stream);
-        case 9: return launch3e<9>(p, stream);
-        case 10: return launch3e<10>(p, stream);
-        default: return launch3e<4>(p, stream);
+int launch_g3(const GemmParams& p, const G3Form& f, hipStream_t stream) {
+    if (f.kernel == G3_UNSUPPORTED) {      // (me_gemm refuses these from the form, each with its own message, before it comes here)
+        me_set_error("me_gemm(g3): no kernel serves this descriptor");
+        return ME_ERR_UNSUPPORTED;
+    }
+    GemmParams q = p;
+    if (q.g3_split <= 1 || q.g3_slabs == nullptr) { q.g3_full_tiles = q.tiles_m * q.tiles_n; q.g3_split = 1; q.g3_ktp = 0; q.g3_slabs = nullptr; }
+    if (f.kernel == G3_RESIDENT) return launch3r_any(f.repi, f.pre, q, f.G, stream);
+    switch (f.epi) {
+        case 0: return launch3e<0>(q, f, stream);
+        case 1: return launch3e<1>(q, f, stream);
+        case 2: return launch3e<2>(q, f, stream);
+        case 3: return launch3e<3>(q, f, stream);
+        case 6: return launch3e<6>(q, f, stream);
+        case 7: return launch3e<7>(q, f, stream);
+        case 8: return launch3e<8>(q, f, stream);
+        case 9: return launch3e<9>(q, f, stream);
+        case 10: return launch3e<10>(q, f, stream);
+        default: return launch3e<4>(q, f, stream);
     }
 }

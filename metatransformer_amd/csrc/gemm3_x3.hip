@@ -11,8 +11,6 @@
 // (gemm_tn_with_launcher, gemm.hip).
 #include "gemm3_core.h"
 
-int gemm_tn_with_launcher(const me_gemm_desc* d, hipStream_t stream, int (*launch)(const GemmParams&, hipStream_t, const void*), const void* ctx);
-
 namespace {
 
 // operand columns [m0 + pa, ..) of A and [n0 + pb, ..) of B, all K rows (g3_make_src_tn with a plane offset)

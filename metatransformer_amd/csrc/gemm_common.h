@@ -1,6 +1,7 @@
 // gemm_common.h -- parameter block and fused epilogue shared by the GEMM kernel families.
 #pragma once
 #include "common.h"
+#include "gemm_host.h"
 
 struct GemmParams {
     const void* A; const void* B; void* C;
@@ -25,7 +26,7 @@ struct GemmParams {
     int64_t slab_stride;                    // g3 wgrad: floats between the split-K slabs in C (>= M * N, padded: see g3_tn_slab_stride)
     const float* row_affine;                // folded LayerNorm (me_gemm_desc.row_affine): [M][2] = (rstd, -rstd * mean), or null
     int row_nparts; float row_eps;          // row_nparts > 0 (me_gemm_desc.row_parts): row_affine holds [row_nparts][M] partial (mean, M2) pairs instead --
-                                            // resident kernel only (g3_takes_row_parts); the pairs are LayerNorm(K = 64 row_nparts, row_eps)'s
+                                            // resident kernel only (g3_form: G3_PRE_ROW_PARTS); the pairs are LayerNorm(K = 64 row_nparts, row_eps)'s
     const float* col_shift;                 // ... and s[n] = sum_k W'[n, k]
     int sk_wgs, sk_upt, sk_levels, sk_l1;   // g3 wgrad on sk_wgs > 0 workgroups that are NOT a multiple of the tile count (gemm3.hip: gemm_g3tn_sk_kernel): sk_levels
                                             // whole split levels of sk_l1 K-tile pairs per tile (one workgroup each, split-major as the uniform grid) + the rest of every
@@ -204,7 +205,7 @@ __device__ __forceinline__ void epilogue_oct(const GemmParams& p, int64_t m, int
 static inline int pick_epi(const GemmParams& p) {
     if (p.split_k > 1) return 5;
     if (me_is_planes(p.c_dtype)) return 4;  // (plane stores live in the generic epilogue only)
-    if (p.flags || p.row_affine) return 4;  // (the resident g3 kernel has its own forms of these: launch_g3)
+    if (p.flags || p.row_affine) return 4;  // (the resident g3 kernel has its own forms of these: g3_form)
     if (p.beta != 0.0f || p.out_group_rows != 0 || p.res_row_mod != 0) return 4;
     const int nrow = (p.residual ? 1 : 0) + (p.aux ? 1 : 0);
     if (nrow > 1) return 4;
@@ -239,14 +240,47 @@ static inline int pick_epi_ex(const GemmParams& p) {
     return e;
 }
 
-// kernel families (each in its own translation unit)
+// kernel families (each in its own translation unit).  The numbers are public: me_gemm_profile_rec.plan carries them.
+enum GemmFamily : int {
+    GEMM_G128 = 0,      // 128 x 128 tile, 4 waves: exact fp32, tiny and unaligned problems (gemm.hip)
+    GEMM_G2B = 2,       // two 4-wave workgroups per CU, K-step 32 (gemm2b.hip)
+    GEMM_G2W = 3,       // 8 waves, 256 x 256 tile, K-step 32 (gemm2b.hip)
+    GEMM_G3 = 4,        // 8 waves, 256 x 256 tile, K-tile 64 (gemm3.hip)
+};
 int launch_g2b(const GemmParams& p, int op, int bm, int bn, hipStream_t stream);
 bool g2b_supported(const GemmParams& p, int op);
-int launch_g3(const GemmParams& p, int epi, hipStream_t stream);
 bool g3_supported(const GemmParams& p, int op);
-bool g3_emits_row_stats(const GemmParams& p);          // will launch_g3 run the resident residual kernel that can emit p.row_stats?
-bool g3_takes_row_parts(const GemmParams& p);          // ... the resident folded-LayerNorm epilogue that consumes such partials directly (p.row_nparts)?
-bool g3_takes_gg8(const GemmParams& p);         // ME_GG8 preact / aux: the resident kernel's PRE 6 forms only
+
+// ---- the g3 form: which of gemm3.hip's NT kernels a planned launch runs, decided before the launch by g3_form -- the planning
+// queries (me_gemm_emits_row_stats, _takes_row_parts, _takes_a_wrap, _takes_gg8), me_gemm's argument checks and launch_g3 all read
+// the same value.
+enum G3Kernel : int {
+    G3_UNSUPPORTED = 0,     // the descriptor asks for what only a kernel it does not reach can do (row_stats, row_parts, ME_GG8, a_wrap_k)
+    G3_RESIDENT,            // gemm_g3r_kernel<repi, pre>: one workgroup per CU walks its tiles
+    G3_ONE_TILE,            // gemm_g3_kernel<epi>: one tile (or one K-part of a split tail tile) per workgroup
+    G3_ONE_TILE_WRAP,       // gemm_g3_kernel<epi, true>: the same with A's K-tile index wrapping (me_gemm_desc.a_wrap_k)
+};
+// PRE of gemm_g3r_kernel: what the resident epilogue does besides its EPI (the numbers are template arguments)
+enum G3Pre : int {
+    G3_PRE_NONE = 0,
+    G3_PRE_SAVE_PREACT = 1,     // EPI 1: store the pre-activation
+    G3_PRE_SAVE_GELU_GRAD = 2,  // EPI 1: store gelu'(pre-activation) instead (ME_GEMM_SAVE_GELU_GRAD)
+    G3_PRE_ROW_AFFINE = 3,      // folded LayerNorm from finished (rstd, -rstd * mean) pairs
+    G3_PRE_ROW_STATS = 4,       // EPI 2: emit the output's per-row partial statistics (p.row_stats)
+    G3_PRE_ROW_PARTS = 5,       // folded LayerNorm from the partials of the launch in front (p.row_nparts)
+    G3_PRE_GG8 = 6,             // gelu' in eight bits: saved (EPI 1) or read as the factor (EPI 6)
+};
+struct G3Form {
+    G3Kernel kernel = G3_UNSUPPORTED;
+    int epi = 4;                // EPI of the one-tile kernel (pick_epi_ex; a column scale outside the residual forms -> generic)
+    int repi = -1, pre = G3_PRE_NONE;      // EPI / PRE of the resident kernel that covers the descriptor; repi < 0: none does
+    int G = 0;                  // workgroups of a resident launch: the CUs, rounded down to whole XCD rounds of 8
+    int nwg = 0;                // workgroups of a one-tile launch
+};
+// p: filled and planned (tiles_m / tiles_n in 256 x 256 tiles, the g3_* tail-split fields); cus: g3_cu_count().  Pure host arithmetic.
+G3Form g3_form(const GemmParams& p, int cus);
+int g3_cu_count();              // CUs of the current device (256 when there is none to ask)
+int launch_g3(const GemmParams& p, const G3Form& f, hipStream_t stream);
 int launch_g3_tn(const GemmParams& p, hipStream_t stream);      // p.split_k slabs into p.C, p.ksteps_per_split K-tiles of 64 each
 int launch_g3_tn_sk(const GemmParams& p, hipStream_t stream);   // the balanced static partition (p.sk_wgs workgroups; p.split_k = the most slabs a tile gets)
 bool g3_tn_supported(const GemmParams& p);

@@ -19,12 +19,6 @@
 // me_gemm inside the same entry point, with the caller's workspace for the gathered matrix.
 #include "gemm3_core.h"
 
-// gemm.hip: validation + parameter block of a descriptor; me_gemm for a g3 wgrad problem with the kernel launch replaced (planning,
-// split-K slabs, the deterministic fold with alpha / beta / column sums stay me_gemm's); would the planner take that route
-int gemm_fill_params(const me_gemm_desc* d, GemmParams& p);
-int gemm_tn_with_launcher(const me_gemm_desc* d, hipStream_t stream, int (*launch)(const GemmParams&, hipStream_t, const void*), const void* ctx);
-int gemm_tn_is_g3(const me_gemm_desc* d);
-
 namespace {
 
 // n / d for n < 2^31 as a multiplication (Granlund & Montgomery): q = mulhi(n, ceil(2^(31 + l) / d)) >> (l - 1), l = ceil(log2 d) >= 1

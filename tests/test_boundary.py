@@ -119,6 +119,10 @@ def test_gemm_planning_queries_of_round_6(lib):
     d = desc(50432, 768, 9216, cdt=_capi.ME_F32, lda=6144)
     d.a_wrap_k = 6144 + 64                                                 # not a multiple of 128
     assert lib.me_gemm_takes_a_wrap(ctypes.byref(d)) == 0
+    d.a_wrap_k, d.act, d.colscale = 6144, _capi.ME_ACT_GELU, 32768          # GELU next to a column scale: no (GELU alone is no either)
+    assert lib.me_gemm_takes_a_wrap(ctypes.byref(d)) == 0
+    d.act = _capi.ME_ACT_NONE
+    assert lib.me_gemm_takes_a_wrap(ctypes.byref(d)) == 1
     # weight gradients: the workspace query with a reservation covers the default plan too (more slabs per tile, never fewer bytes)
     for Mo, No in ((2304, 768), (768, 3072), (768, 768)):
         d = desc(Mo, No, 50432, op=_capi.ME_GEMM_TN, cdt=_capi.ME_F32)

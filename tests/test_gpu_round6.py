@@ -311,6 +311,10 @@ def test_gemm_reads_two_plane_operand_with_wrapped_reduction(dev, M_rows, N_out,
     # small problems (another kernel family) say no instead of mis-reading the operand
     d.M = 512
     assert lib.me_gemm_takes_a_wrap(ctypes.byref(d)) == 0 and lib.me_gemm(ctypes.byref(d), _capi.stream_ptr()) != 0
+    # ... and so does GELU next to a column scale at the full size: the query reads the epilogue before the column scale turns it generic
+    cs = torch.ones(N_out, device=dev)
+    d.M, d.act, d.colscale, d.residual = M_rows, _capi.ME_ACT_GELU, cs.data_ptr(), None      # (GELU + a row operand is the generic epilogue, which is served)
+    assert lib.me_gemm_takes_a_wrap(ctypes.byref(d)) == 0 and lib.me_gemm(ctypes.byref(d), _capi.stream_ptr()) != 0
 
 
 def test_gemm_writes_two_plane_output(dev):
