@@ -613,6 +613,43 @@ enum { ME_RESIZE_BILINEAR = 0, ME_RESIZE_BICUBIC = 1 };
 int me_resize_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int h, int w, int H, int W, int cols,
                    int mode, void* stream);
 
+/* ------------------------------------------------------------------ image tensors as token rows (ViT-Adapter backbone)
+ * The dense convolutions, the pooling, the resizes and the up-sampling of SpatialPriorModule and ViTAdapter
+ * (Image/{detection,segmentation}/.../backbones/adapter_modules.py:194-246, vit_adapter.py:110-132) on the layout the rest of
+ * the library works on: an image tensor is rows [B*H*W, C], C contiguous, row order (b, y, x).  Tensors are ME_F32 or ME_BF16,
+ * 16-byte aligned; C must be a multiple of 4 except where stated.  Every backward is a gather that sums in a fixed order (no
+ * float atomics): two runs are bit-identical.  B = 0 is ME_OK with nothing written.
+ * me_conv3x3_gather: the unfold of a 3x3 convolution with padding 1 and stride 1 or 2: cols [B*Ho*Wo, Kpad] (same dtype as x),
+ *   Ho = (H - 1) / stride + 1, cols[(b, oy, ox), (dy * 3 + dx) * Cin + c] = x[(b, oy stride + dy - 1, ox stride + dx - 1), c], zero
+ *   for taps outside the image and for the columns 9 Cin .. Kpad (Kpad: a multiple of 8, the K granule of me_gemm, >= 9 Cin).
+ *   Any Cin > 0 (the RGB stem has 3).  The convolution is then me_gemm NT against the weight as [Cout, Kpad] rows in the same
+ *   (dy, dx, c) order, its weight gradient me_gemm TN.
+ * me_conv3x3_scatter: the adjoint: dx[(b, y, x), c] = the sum, in (dy, dx) order, of the at most nine dcols entries that were
+ *   gathered from that pixel; every element of dx is written.
+ * me_maxpool3x3s2_rows: MaxPool2d(3, 2, 1): y [B*Ho*Wo, C] and idx (int8, same shape) = the winning tap dy * 3 + dx; on ties the
+ *   first tap in (dy, dx) order wins, a NaN wins over numbers (ATen's rule).  _bwd: dx[(b, y, x), c] = the sum over the at most
+ *   four windows holding the pixel, in (oy, ox) order, of dy where idx names it.
+ * me_resize_rows_batched: bilinear F.interpolate(align_corners=False) of [B*h*w, cols] to [B*H*W, cols]; the source position of
+ *   output index o is scale (o + 0.5) - 0.5 with the scale an ARGUMENT: h / H for a call with size=, 1 / scale_factor for a
+ *   call with scale_factor= (where H = floor(h * scale_factor)), as PyTorch does.  _bwd: its adjoint, dsrc from ddst.
+ * me_upsample2x_rows: the row permutation behind ConvTranspose2d(C, C, 2, 2): y4 [B*h*w, 4 C] = the input rows times the weight
+ *   as [(ky, kx, cout), cin] (one me_gemm); out[(b, 2 y + ky, 2 x + kx), c] = y4[(b, y, x), (ky * 2 + kx) C + c] + bias[c] +
+ *   add[same row, c] (bias fp32 [C] and add [B*2h*2w, C] may each be NULL).  _bwd: dy4 from dout, the inverse permutation (the
+ *   bias gradient is me_colsum of dout, the gradient of add is dout itself). */
+int me_conv3x3_gather(const void* x, int dtype, void* cols, int B, int H, int W, int Cin, int stride, int Kpad, void* stream);
+int me_conv3x3_scatter(const void* dcols, int dtype, void* dx, int dx_dtype, int B, int H, int W, int Cin, int stride, int Kpad,
+                       void* stream);
+int me_maxpool3x3s2_rows(const void* x, int x_dtype, void* y, int y_dtype, int8_t* idx, int B, int H, int W, int C, void* stream);
+int me_maxpool3x3s2_rows_bwd(const void* dy, int dy_dtype, const int8_t* idx, void* dx, int dx_dtype, int B, int H, int W, int C,
+                             void* stream);
+int me_resize_rows_batched(const void* src, int src_dtype, void* dst, int dst_dtype, int B, int h, int w, int H, int W, int cols,
+                           float scale_y, float scale_x, void* stream);
+int me_resize_rows_batched_bwd(const void* ddst, int ddst_dtype, void* dsrc, int dsrc_dtype, int B, int h, int w, int H, int W,
+                               int cols, float scale_y, float scale_x, void* stream);
+int me_upsample2x_rows(const void* y4, int y4_dtype, const float* bias, const void* add, int add_dtype, void* out, int out_dtype,
+                       int B, int h, int w, int C, void* stream);
+int me_upsample2x_rows_bwd(const void* dout, int dout_dtype, void* dy4, int dy4_dtype, int B, int h, int w, int C, void* stream);
+
 /* ------------------------------------------------------------------ data-parallel gradient exchange
  * The ONE exchange step of batch-sharded data parallelism: a sum all-reduce per flat gradient bucket over RCCL (xGMI
  * inside a node).  Replaces _allreduce_coalesced (Image/segmentation/mmseg_custom/core/utils/dist_utils.py:14-35:

@@ -10,8 +10,9 @@ from .encoder import (Attention, Block, Mlp, build_encoder, set_fp32_mode, conve
 from .heads import (ClassifierHead, ClsHead, FeaturePropogation, P3Embed, PointPatchEmbed, PointViTDecoder, PointViTPartDecoder,  # noqa: F401
                     SegHead, furthest_point_sample, group_features, knn_indices, load_encoder_checkpoint, pack_encoder, pool_tokens,
                     save_encoder_checkpoint, three_interpolation, three_nn)
-from .adapter import (ConvFFN, DWConv, Extractor, Injector, InteractionBlock, MSDeformAttn, deform_inputs,  # noqa: F401
-                      get_reference_points, ms_deform_attn)
+from .adapter import (ConvFFN, DWConv, Extractor, Injector, InteractionBlock, MSDeformAttn, SpatialPriorModule, ViTAdapter,  # noqa: F401
+                      conv3x3_rows, conv_transpose2x2_rows, deform_inputs, get_reference_points, max_pool3x3s2_rows, ms_deform_attn,
+                      resize_rows_batched)
 from .data2seq import (AcousticPatchEmbed, Data2Seq, DataEmbedding, PatchEmbed, VideoPatchEmbed,  # noqa: F401
                        sinusoid_table, video_sinusoid_table)
 
@@ -20,4 +21,5 @@ __all__ = ["Block", "Attention", "Mlp", "build_encoder", "set_fp32_mode", "encod
            "convert_video_state_dict", "to_video_state_dict", "resize_pos_embed", "ClassifierHead", "ClsHead", "PointPatchEmbed", "P3Embed",
            "furthest_point_sample", "knn_indices", "group_features", "pool_tokens",
            "FeaturePropogation", "PointViTDecoder", "PointViTPartDecoder", "SegHead", "three_nn", "three_interpolation", "load_encoder_checkpoint", "save_encoder_checkpoint", "pack_encoder",
-           "ms_deform_attn", "MSDeformAttn", "Injector", "Extractor", "ConvFFN", "DWConv", "InteractionBlock", "deform_inputs", "get_reference_points"]
+           "ms_deform_attn", "MSDeformAttn", "Injector", "Extractor", "ConvFFN", "DWConv", "InteractionBlock", "deform_inputs", "get_reference_points",
+           "conv3x3_rows", "max_pool3x3s2_rows", "resize_rows_batched", "conv_transpose2x2_rows", "SpatialPriorModule", "ViTAdapter"]

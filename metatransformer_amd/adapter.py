@@ -10,6 +10,12 @@ The sampling core (forward, and the three gradients) is me_ms_deform_attn_fwd / 
 library's GEMMs (heads.linear) and every LayerNorm on its LayerNorm kernels.  Softmax, the location arithmetic, the depth-wise
 3x3 convolution, GELU behind it and DropPath are PyTorch glue.  ``InteractionBlock.forward`` takes ``blocks`` = a slice of this
 package's layer-scale / windowed ``Block``s, as vit_adapter.py:107 slices the encoder.
+
+The backbone around them -- ``SpatialPriorModule`` (adapter_modules.py:194-246) and ``ViTAdapter`` (vit_adapter.py:19-132) -- keeps
+every image tensor as token rows [B*H*W, C] (row order (b, y, x)): ``conv3x3_rows`` (me_conv3x3_gather + the GEMMs of heads.linear,
+me_conv3x3_scatter for the input gradient), ``max_pool3x3s2_rows``, ``resize_rows_batched`` and ``conv_transpose2x2_rows`` are
+the kernels of csrc/conv_rows.hip.  SyncBatchNorm (called on the [rows, C] tensor), ReLU, the level-embed adds and the one
+permute to channel-first at the very end are PyTorch glue.
 """
 from __future__ import annotations
 
@@ -23,8 +29,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.utils.checkpoint as cp
 
-from . import _capi
-from ._capi import MetaEncError, check, ptr, stream_ptr
+from . import _capi, ops
+from ._capi import MetaEncError, check, dtype_code, ptr, stream_ptr
+from .data2seq import PatchEmbed
+from .encoder import Block
 from .heads import _LayerNormFn, linear
 
 MAX_LEVELS = 8          # me_ms_deform_attn_*: levels per call
@@ -416,3 +424,611 @@ class InteractionBlock(nn.Module):
         for extractor in (self.extractor, *(self.extra_extractors or ())):
             c = extractor(c, deform_inputs2[0], x, deform_inputs2[1], deform_inputs2[2], H, W)
         return x, c
+
+
+# ----------------------------------------------------------------------------- image tensors as token rows (csrc/conv_rows.hip)
+def conv_out_size(n: int, stride: int = 1) -> int:
+    """output length of a 3-tap window with padding 1 over n positions (Conv2d(3, stride, 1), MaxPool2d(3, 2, 1))"""
+    return (int(n) - 1) // int(stride) + 1
+
+
+def interpolate_geometry(n: int, scale_factor: float) -> Tuple[int, float]:
+    """(output length, source scale) of F.interpolate(scale_factor=f, align_corners=False) without recompute_scale_factor:
+    floor(n * f) outputs sampled at (o + 0.5) / f - 0.5 -- 1 / f, not n / floor(n * f), which differs where n * f is not whole"""
+    if not scale_factor > 0:
+        raise MetaEncError(f"interpolate_geometry: scale_factor = {scale_factor} must be positive")
+    return int(math.floor(float(n) * float(scale_factor))), 1.0 / float(scale_factor)
+
+
+def _rows(who: str, x, B: int, H: int, W: int, multiple: int = 4) -> torch.Tensor:
+    """x as a contiguous fp32 / bf16 [B*H*W, C] CUDA tensor (fp16 is converted to fp32), or a MetaEncError"""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise MetaEncError(f"{who}: x must be token rows [B*H*W, C]" + (f" (got shape {tuple(x.shape)})" if isinstance(x, torch.Tensor) else ""))
+    if not x.is_cuda:
+        raise MetaEncError(f"{who}: x is a CPU tensor: CUDA tensors required (no CPU fallback)")
+    if min(int(B), int(H), int(W)) < 1 or x.shape[0] != int(B) * int(H) * int(W):
+        raise MetaEncError(f"{who}: x has {x.shape[0]} rows, B * H * W = {B} * {H} * {W} expected")
+    if x.dtype == torch.float16:
+        x = x.float()
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise MetaEncError(f"{who}: x must be float32, bfloat16 or float16 (got {x.dtype})")
+    if x.shape[1] % multiple:
+        raise MetaEncError(f"{who}: C = {x.shape[1]} must be a multiple of {multiple}")
+    return x.contiguous()
+
+
+def conv3x3_kpad(cin: int) -> int:
+    """columns of the unfolded matrix: 9 cin rounded up to the GEMM's K granule (8)"""
+    return (9 * int(cin) + 7) // 8 * 8
+
+
+class _Conv3x3UnfoldFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, B, H, W, stride):
+        Cin = x.shape[1]
+        Kpad = conv3x3_kpad(Cin)
+        cols = torch.empty(B * conv_out_size(H, stride) * conv_out_size(W, stride), Kpad, dtype=x.dtype, device=x.device)
+        check(_capi.load().me_conv3x3_gather(ptr(x), dtype_code(x.dtype), ptr(cols), B, H, W, Cin, stride, Kpad, stream_ptr()),
+              "me_conv3x3_gather")
+        ctx.geom = (B, H, W, Cin, stride, Kpad, x.dtype)
+        return cols
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dcols):
+        B, H, W, Cin, stride, Kpad, dt = ctx.geom
+        dcols = dcols.contiguous()
+        if dcols.dtype not in (torch.float32, torch.bfloat16):
+            dcols = dcols.float()
+        dx = torch.empty(B * H * W, Cin, dtype=dt, device=dcols.device)
+        check(_capi.load().me_conv3x3_scatter(ptr(dcols), dtype_code(dcols.dtype), ptr(dx), dtype_code(dt), B, H, W, Cin, stride, Kpad,
+                                              stream_ptr()), "me_conv3x3_scatter")
+        return dx, None, None, None, None
+
+
+CONV_K_CHUNK = 128      # fp32 contractions longer than this run as several me_gemm calls accumulating into the output
+
+
+def _gemm_nt_chunked(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """fp32 [M, N] = a [M, K] b [N, K]^T (+ bias) on me_gemm NT.  The exact-fp32 kernel adds all K products of an output into
+    one accumulator, so its rounding error grows like sqrt(K); a 3x3 convolution has K = 9 Cin up to 2304.  fp32 operands are
+    therefore contracted CONV_K_CHUNK columns at a time, each call adding its partial sum to the output (beta = 1): the long
+    chain becomes K / 128 short ones plus K / 128 additions of partial sums.  bf16 operands (whose own rounding is 2^-9) take
+    one call."""
+    lib = _capi.load()
+    M, K = a.shape
+    N = b.shape[0]
+    out = torch.empty(M, N, dtype=torch.float32, device=a.device)
+    step = CONV_K_CHUNK if a.dtype == torch.float32 else K
+    es = a.element_size()
+    bias = bias.detach().float().contiguous() if bias is not None else None
+    for k0 in range(0, K, step):
+        d = _capi.GemmDesc()
+        d.op, d.ab_dtype = _capi.ME_GEMM_NT, dtype_code(a.dtype)
+        d.M, d.N, d.K = M, N, min(step, K - k0)
+        d.A, d.lda = ptr(a) + k0 * es, K
+        d.B, d.ldb = ptr(b) + k0 * es, K
+        d.C, d.ldc, d.c_dtype = ptr(out), N, _capi.ME_F32
+        d.alpha, d.beta = 1.0, 0.0 if k0 == 0 else 1.0
+        if bias is not None and k0 == 0:
+            d.bias = ptr(bias)
+        ws = None
+        need = lib.me_gemm_workspace_bytes(ctypes.byref(d))
+        if need:
+            ws = torch.empty(need, dtype=torch.uint8, device=a.device)
+            d.workspace, d.workspace_bytes = ptr(ws), need
+        check(lib.me_gemm(ctypes.byref(d), stream_ptr()), "me_gemm (conv3x3_rows)")
+    return out
+
+
+class _ConvLinearFn(torch.autograd.Function):
+    """heads._LinearFn with its two NT products chunked along K (_gemm_nt_chunked): y = x W^T + b for the unfolded rows"""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        cdt = x.dtype
+        N, K = w.shape
+        Np = (N + 7) // 8 * 8
+        wc = w.detach().to(cdt)
+        bc = b.detach().float() if b is not None else None
+        if Np != N:
+            wc = torch.cat([wc, wc.new_zeros(Np - N, K)])
+            bc = torch.cat([bc, bc.new_zeros(Np - N)]) if bc is not None else None
+        wc = wc.contiguous()
+        y = _gemm_nt_chunked(x, wc, bc)
+        ctx.save_for_backward(x, wc)
+        ctx.meta = (N, Np, b is not None, w.dtype)
+        return y if Np == N else y[:, :N].contiguous()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, wc = ctx.saved_tensors
+        N, Np, has_b, wdt = ctx.meta
+        d2 = dy.to(x.dtype)
+        if Np != N:
+            d2 = torch.cat([d2, d2.new_zeros(d2.shape[0], Np - N)], dim=1)
+        d2 = d2.contiguous()
+        dx = _gemm_nt_chunked(d2, ops.transpose_cast(wc, wc.dtype), None).to(x.dtype) if ctx.needs_input_grad[0] else None
+        M = d2.shape[0]
+        if M % 8 == 0:
+            dw = ops.gemm(d2, x, op=_capi.ME_GEMM_TN, out_dtype=torch.float32)
+        else:       # the TN kernel wants 16-byte rows of the reduction-major operands: pad the batch with zero rows
+            pad = 8 - M % 8
+            dw = ops.gemm(torch.cat([d2, d2.new_zeros(pad, Np)]), torch.cat([x, x.new_zeros(pad, x.shape[1])]),
+                          op=_capi.ME_GEMM_TN, out_dtype=torch.float32)
+        db = ops.colsum(d2)[:N].to(wdt) if has_b else None
+        return dx, dw[:N].to(wdt), db
+
+
+def conv3x3_rows(x: torch.Tensor, weight: torch.Tensor, B: int, H: int, W: int, stride: int = 1,
+                 bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Conv2d(Cin, Cout, 3, stride, padding=1) on rows: x [B*H*W, Cin] -> fp32 [B*Ho*Wo, Cout], Ho = conv_out_size(H, stride).
+    ``weight`` keeps its checkpoint shape [Cout, Cin, 3, 3].  The rows are unfolded by me_conv3x3_gather into (dy, dx, c) columns
+    and contracted on me_gemm with the dtype policy of heads.linear (fp32 rows: exact fp32 GEMM, K taken 128 columns at a time to
+    keep the accumulation chains short; bf16 rows: bf16 GEMM; weight gradient on the split-K TN kernel);
+    the input gradient is me_conv3x3_scatter, deterministic.  Any Cin (the RGB stem has 3); Cout as heads.linear takes it."""
+    if stride not in (1, 2):
+        raise MetaEncError(f"conv3x3_rows: stride = {stride} (1 or 2)")
+    x = _rows("conv3x3_rows", x, B, H, W, multiple=1)
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 4 or tuple(weight.shape[1:]) != (x.shape[1], 3, 3):
+        raise MetaEncError(f"conv3x3_rows: weight must be [Cout, {x.shape[1]}, 3, 3]"
+                           + (f" (got {tuple(weight.shape)})" if isinstance(weight, torch.Tensor) else ""))
+    _require_one_gpu("conv3x3_rows", x=x, weight=weight, bias=bias)
+    Cout, Cin = weight.shape[:2]
+    cols = _Conv3x3UnfoldFn.apply(x, int(B), int(H), int(W), int(stride))
+    w2 = F.pad(weight.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin), (0, cols.shape[1] - 9 * Cin))
+    return _ConvLinearFn.apply(cols, w2, bias)
+
+
+class _MaxPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, B, H, W):
+        C = x.shape[1]
+        rows = B * conv_out_size(H, 2) * conv_out_size(W, 2)
+        y = torch.empty(rows, C, dtype=x.dtype, device=x.device)
+        idx = torch.empty(rows, C, dtype=torch.int8, device=x.device)
+        check(_capi.load().me_maxpool3x3s2_rows(ptr(x), dtype_code(x.dtype), ptr(y), dtype_code(y.dtype), ptr(idx), B, H, W, C,
+                                                stream_ptr()), "me_maxpool3x3s2_rows")
+        ctx.save_for_backward(idx)
+        ctx.geom = (B, H, W, C, x.dtype)
+        ctx.mark_non_differentiable(idx)
+        return y, idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, _didx):
+        (idx,) = ctx.saved_tensors
+        B, H, W, C, dt = ctx.geom
+        dy = dy.contiguous()
+        if dy.dtype not in (torch.float32, torch.bfloat16):
+            dy = dy.float()
+        dx = torch.empty(B * H * W, C, dtype=dt, device=dy.device)
+        check(_capi.load().me_maxpool3x3s2_rows_bwd(ptr(dy), dtype_code(dy.dtype), ptr(idx), ptr(dx), dtype_code(dt), B, H, W, C,
+                                                    stream_ptr()), "me_maxpool3x3s2_rows_bwd")
+        return dx, None, None, None
+
+
+def max_pool3x3s2_rows(x: torch.Tensor, B: int, H: int, W: int, return_indices: bool = False):
+    """MaxPool2d(3, 2, 1) on rows: x [B*H*W, C] -> [B*Ho*Wo, C] of x's dtype, Ho = conv_out_size(H, 2).  With return_indices also
+    the winning tap dy * 3 + dx per element (int8; the first tap in (dy, dx) order on ties).  C a multiple of 4."""
+    x = _rows("max_pool3x3s2_rows", x, B, H, W)
+    y, idx = _MaxPoolFn.apply(x, int(B), int(H), int(W))
+    return (y, idx) if return_indices else y
+
+
+class _ResizeRowsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, B, h, w, H, W, sy, sx):
+        C = x.shape[1]
+        y = torch.empty(B * H * W, C, dtype=x.dtype, device=x.device)
+        check(_capi.load().me_resize_rows_batched(ptr(x), dtype_code(x.dtype), ptr(y), dtype_code(y.dtype), B, h, w, H, W, C, sy, sx,
+                                                  stream_ptr()), "me_resize_rows_batched")
+        ctx.geom = (B, h, w, H, W, C, sy, sx, x.dtype)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        B, h, w, H, W, C, sy, sx, dt = ctx.geom
+        dy = dy.contiguous()
+        if dy.dtype not in (torch.float32, torch.bfloat16):
+            dy = dy.float()
+        dx = torch.empty(B * h * w, C, dtype=dt, device=dy.device)
+        check(_capi.load().me_resize_rows_batched_bwd(ptr(dy), dtype_code(dy.dtype), ptr(dx), dtype_code(dt), B, h, w, H, W, C, sy, sx,
+                                                      stream_ptr()), "me_resize_rows_batched_bwd")
+        return dx, None, None, None, None, None, None, None
+
+
+def resize_rows_batched(x: torch.Tensor, B: int, h: int, w: int, scale_factor: Optional[float] = None, size=None) -> torch.Tensor:
+    """Bilinear F.interpolate(align_corners=False) on rows: x [B*h*w, C] -> [B*H*W, C] of x's dtype.  Exactly one of
+    ``scale_factor`` (H = floor(h * f), sampled with 1 / f: interpolate_geometry) and ``size`` = (H, W) (sampled with h / H).
+    C a multiple of 4; the gradient is me_resize_rows_batched_bwd, deterministic."""
+    if (scale_factor is None) == (size is None):
+        raise MetaEncError("resize_rows_batched: give exactly one of scale_factor and size")
+    x = _rows("resize_rows_batched", x, B, h, w)
+    if size is not None:
+        try:
+            H, W = (int(v) for v in size)
+        except (TypeError, ValueError) as e:
+            raise MetaEncError("resize_rows_batched: size must be (H, W)") from e
+        if H < 1 or W < 1:
+            raise MetaEncError(f"resize_rows_batched: size = ({H}, {W}) must be positive")
+        sy, sx = h / H, w / W
+    else:
+        (H, sy), (W, sx) = interpolate_geometry(h, scale_factor), interpolate_geometry(w, scale_factor)
+        if H < 1 or W < 1:
+            raise MetaEncError(f"resize_rows_batched: scale_factor = {scale_factor} leaves no output for a {h} x {w} grid")
+    return _ResizeRowsFn.apply(x, int(B), int(h), int(w), H, W, float(sy), float(sx))
+
+
+class _Upsample2xFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y4, bias, add, B, h, w):
+        C = y4.shape[1] // 4
+        out = torch.empty(B * 4 * h * w, C, dtype=torch.float32, device=y4.device)
+        b32 = bias.detach().float().contiguous() if bias is not None else None
+        check(_capi.load().me_upsample2x_rows(ptr(y4), dtype_code(y4.dtype), ptr(b32), ptr(add), dtype_code(add.dtype) if add is not None else 0,
+                                              ptr(out), _capi.ME_F32, B, h, w, C, stream_ptr()), "me_upsample2x_rows")
+        ctx.geom = (B, h, w, C, y4.dtype, bias.dtype if bias is not None else None, add.dtype if add is not None else None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        B, h, w, C, ydt, bdt, adt = ctx.geom
+        dout = dout.float().contiguous()
+        dy4 = None
+        if ctx.needs_input_grad[0]:
+            dy4 = torch.empty(B * h * w, 4 * C, dtype=ydt, device=dout.device)
+            check(_capi.load().me_upsample2x_rows_bwd(ptr(dout), _capi.ME_F32, ptr(dy4), dtype_code(ydt), B, h, w, C, stream_ptr()),
+                  "me_upsample2x_rows_bwd")
+        db = ops.colsum(dout).to(bdt) if bdt is not None and ctx.needs_input_grad[1] else None
+        da = dout.to(adt) if adt is not None and ctx.needs_input_grad[2] else None
+        return dy4, db, da, None, None, None
+
+
+def conv_transpose2x2_rows(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], B: int, h: int, w: int,
+                           add: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ConvTranspose2d(Cin, Cout, 2, 2) on rows, plus an optional second operand: x [B*h*w, Cin] -> fp32 [B*2h*2w, Cout] =
+    up(x) + bias (+ add, [B*2h*2w, Cout]).  ``weight`` keeps its checkpoint shape [Cin, Cout, 2, 2].  One GEMM (heads.linear
+    against the weight as [(ky, kx, cout), cin]), then me_upsample2x_rows moves every row's four Cout-wide segments to its four
+    children; backward is the inverse permutation, me_colsum for the bias and the GEMMs of heads.linear."""
+    x = _rows("conv_transpose2x2_rows", x, B, h, w, multiple=8)
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 4 or weight.shape[0] != x.shape[1] or tuple(weight.shape[2:]) != (2, 2):
+        raise MetaEncError(f"conv_transpose2x2_rows: weight must be [{x.shape[1]}, Cout, 2, 2]"
+                           + (f" (got {tuple(weight.shape)})" if isinstance(weight, torch.Tensor) else ""))
+    Cin, Cout = weight.shape[:2]
+    if Cout % 4:
+        raise MetaEncError(f"conv_transpose2x2_rows: Cout = {Cout} must be a multiple of 4")
+    if bias is not None and tuple(bias.shape) != (Cout,):
+        raise MetaEncError(f"conv_transpose2x2_rows: bias must be [{Cout}] (got {tuple(bias.shape)})")
+    if add is not None:
+        if not isinstance(add, torch.Tensor) or tuple(add.shape) != (4 * x.shape[0], Cout):
+            raise MetaEncError(f"conv_transpose2x2_rows: add must be [{4 * x.shape[0]}, {Cout}] rows of the 2h x 2w grid")
+        add = (add.float() if add.dtype not in (torch.float32, torch.bfloat16) else add).contiguous()
+    _require_one_gpu("conv_transpose2x2_rows", x=x, weight=weight, bias=bias, add=add)
+    y4 = linear(x, weight.permute(2, 3, 1, 0).reshape(4 * Cout, Cin), None)
+    return _Upsample2xFn.apply(y4, bias, add, int(B), int(h), int(w))
+
+
+def _autocast_rows(rows: torch.Tensor) -> torch.Tensor:
+    """under torch.autocast the convolutions and their Linears compute in bf16, as Block and PatchEmbed do (fp16 autocast runs on
+    the bf16 kernels too); outside it the rows' own dtype decides"""
+    if torch.is_autocast_enabled() and rows.dtype != torch.bfloat16:
+        return rows.to(torch.bfloat16)
+    return rows
+
+
+def _check_image(who: str, x) -> None:
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise MetaEncError(f"{who}: expected an image batch [B, C, H, W]" + (f", got shape {tuple(x.shape)}" if isinstance(x, torch.Tensor) else ""))
+    if not x.is_cuda:
+        raise MetaEncError(f"{who}: input is a CPU tensor: CUDA tensors required (no CPU fallback)")
+    if not x.is_floating_point():
+        raise MetaEncError(f"{who}: input must be a floating-point tensor (got {x.dtype})")
+
+
+def _image_rows(who: str, x) -> torch.Tensor:
+    """a channel-first image batch [B, C, H, W] as rows [B*H*W, C] (the one layout change on the way in)"""
+    _check_image(who, x)
+    return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1])
+
+
+def _rows_to_image(rows: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+    return rows.view(B, H, W, rows.shape[-1]).permute(0, 3, 1, 2).contiguous()
+
+
+class SpatialPriorModule(nn.Module):
+    """The convolutional stem that gives the adapter its 1/4 .. 1/32 pyramid (adapter_modules.SpatialPriorModule by interface:
+    constructor, state-dict keys ``stem.{0,1,3,4,6,7}``, ``conv{2,3,4}.{0,1}``, ``fc{1..4}`` with the convolution weights in their
+    [Cout, Cin, k, k] checkpoint shape, and the return values).  Everything between the input image and the results stays in
+    rows: the 3x3 convolutions are conv3x3_rows, the pool max_pool3x3s2_rows, the four 1x1 convolutions heads.linear.  The norms
+    are the nn.SyncBatchNorm modules themselves, called on [rows, C] (channel at dim 1): batch statistics, running-statistic
+    updates and the cross-rank synchronisation are PyTorch's; ReLU is PyTorch glue.  Under torch.autocast every convolution
+    reads bf16 rows (bf16 GEMM, fp32 result), so the norms and the pool stay fp32."""
+
+    def __init__(self, inplanes=64, embed_dim=384):
+        super().__init__()
+        def conv(cin, cout, stride):
+            return [nn.Conv2d(cin, cout, kernel_size=3, stride=stride, padding=1, bias=False), nn.SyncBatchNorm(cout), nn.ReLU(inplace=True)]
+        self.stem = nn.Sequential(*conv(3, inplanes, 2), *conv(inplanes, inplanes, 1), *conv(inplanes, inplanes, 1),
+                                  nn.MaxPool2d(kernel_size=3, stride=2, padding=1))
+        self.conv2 = nn.Sequential(*conv(inplanes, 2 * inplanes, 2))
+        self.conv3 = nn.Sequential(*conv(2 * inplanes, 4 * inplanes, 2))
+        self.conv4 = nn.Sequential(*conv(4 * inplanes, 4 * inplanes, 2))
+        self.fc1 = nn.Conv2d(inplanes, embed_dim, kernel_size=1, stride=1, padding=0, bias=True)
+        self.fc2 = nn.Conv2d(2 * inplanes, embed_dim, kernel_size=1, stride=1, padding=0, bias=True)
+        self.fc3 = nn.Conv2d(4 * inplanes, embed_dim, kernel_size=1, stride=1, padding=0, bias=True)
+        self.fc4 = nn.Conv2d(4 * inplanes, embed_dim, kernel_size=1, stride=1, padding=0, bias=True)
+
+    @staticmethod
+    def _unit(seq, at, rows, B, H, W):
+        """convolution seq[at], norm seq[at + 1], ReLU -> (rows, Ho, Wo)"""
+        s = seq[at].stride[0]
+        y = F.relu(seq[at + 1](conv3x3_rows(_autocast_rows(rows), seq[at].weight, B, H, W, s)))
+        return y, conv_out_size(H, s), conv_out_size(W, s)
+
+    @staticmethod
+    def _fc(fc, rows):
+        return linear(_autocast_rows(rows), fc.weight.reshape(fc.weight.shape[0], -1), fc.bias)
+
+    def forward_rows(self, x):
+        """x [B, 3, H, W] -> (c1 rows [B*H1*W1, D], c2 [B, H2 W2, D], c3, c4, (H1, W1)): forward() with c1 left as rows of the
+        stride-4 grid"""
+        rows = _image_rows("SpatialPriorModule", x)
+        if rows.dtype == torch.float16:
+            rows = rows.float()
+        B, _, H, W = x.shape
+        y, H, W = self._unit(self.stem, 0, rows.contiguous(), B, H, W)
+        y, H, W = self._unit(self.stem, 3, y, B, H, W)
+        y, H, W = self._unit(self.stem, 6, y, B, H, W)
+        c1 = max_pool3x3s2_rows(y, B, H, W)
+        H1, W1 = conv_out_size(H, 2), conv_out_size(W, 2)
+        c2, H2, W2 = self._unit(self.conv2, 0, c1, B, H1, W1)
+        c3, H3, W3 = self._unit(self.conv3, 0, c2, B, H2, W2)
+        c4, _, _ = self._unit(self.conv4, 0, c3, B, H3, W3)
+        D = self.fc1.weight.shape[0]
+        return (self._fc(self.fc1, c1), self._fc(self.fc2, c2).view(B, -1, D), self._fc(self.fc3, c3).view(B, -1, D),
+                self._fc(self.fc4, c4).view(B, -1, D), (H1, W1))
+
+    def forward(self, x):
+        """-> (c1 [B, D, H/4, W/4] channel-first, c2 [B, H/8 W/8, D], c3 [B, H/16 W/16, D], c4 [B, H/32 W/32, D] tokens)"""
+        c1, c2, c3, c4, (H1, W1) = self.forward_rows(x)
+        return _rows_to_image(c1, x.shape[0], H1, W1), c2, c3, c4
+
+
+class _PosResizeFn(torch.autograd.Function):
+    """the bicubic resize of the pos-embed grid (me_resize_rows) with a gradient: the resize is a fixed linear map R, so
+    d table = R^T d pos, with R itself read off the kernel (the identity table resized) and the product on me_gemm TN"""
+
+    _matrices = {}      # (h, w, H, W, device) -> R, zero-padded to multiples of 8 both ways
+
+    @staticmethod
+    def forward(ctx, table, hw, HW):
+        ctx.geom = (hw, HW, table.dtype)
+        return ops.resize_rows(table.detach().float().contiguous(), hw, HW, "bicubic")
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dpos):
+        (h, w), (H, W), dt = ctx.geom
+        n, N = h * w, H * W
+        npad, Npad = (n + 7) // 8 * 8, (N + 7) // 8 * 8
+        key = (h, w, H, W, dpos.device)
+        R = _PosResizeFn._matrices.get(key)
+        if R is None:
+            eye = torch.zeros(n, npad, dtype=torch.float32, device=dpos.device)
+            eye.fill_diagonal_(1.0)
+            R = torch.zeros(Npad, npad, dtype=torch.float32, device=dpos.device)
+            R[:N] = ops.resize_rows(eye, (h, w), (H, W), "bicubic")
+            if len(_PosResizeFn._matrices) >= 8:          # a training run sees a handful of image sizes; keep the cache small
+                _PosResizeFn._matrices.clear()
+            _PosResizeFn._matrices[key] = R
+        d = torch.zeros(Npad, dpos.shape[1], dtype=torch.float32, device=dpos.device)
+        d[:N] = dpos
+        return ops.gemm(R, d, op=_capi.ME_GEMM_TN, out_dtype=torch.float32)[:n].to(dt), None, None
+
+
+class _AdapterPatchEmbed(PatchEmbed):
+    """PatchEmbed for images of any size that the patch divides (the backbone runs at the data pipeline's sizes)"""
+
+    def _check_input(self, x):
+        p = self.patch_size[0]
+        if x.shape[-2] % p or x.shape[-1] % p:
+            raise MetaEncError(f"ViTAdapter: image {x.shape[-2]} x {x.shape[-1]} is not a multiple of the patch size {p}")
+
+
+class _Checkpointed:
+    """blk(x, H, W) recomputed in backward (the with_cp of the reference's Block); a plain callable, not a registered module"""
+
+    def __init__(self, blk):
+        self.blk = blk
+
+    def __call__(self, x, H, W):
+        if x.requires_grad:
+            return cp.checkpoint(self.blk, x, H, W, use_reentrant=False)
+        return self.blk(x, H, W)
+
+
+class ViTAdapter(nn.Module):
+    """The ViT-Adapter backbone of the Image detection and segmentation recipes (vit_adapter.ViTAdapter on TIMMVisionTransformer,
+    by interface): constructor arguments, state-dict keys (``pos_embed``, ``patch_embed.proj.*``, ``blocks.*``, ``level_embed``,
+    ``spm.*``, ``interactions.*``, ``up.*``, ``norm{1..4}.*``; no ``cls_token``), initial distributions and the forward:
+    image [B, 3, H, W] (H and W multiples of 32) -> [f1, f2, f3, f4], channel-first fp32 maps of ``embed_dim`` channels at
+    strides 4, 8, 16 and 32.
+
+    The spatial prior module, the up-sampling ``up`` (conv_transpose2x2_rows, with the ``+ c1`` fused), the three bilinear
+    resizes of the ViT tokens (resize_rows_batched) and the four output norms all work on token rows; the four results are
+    permuted to channel-first once, at the end.  The encoder blocks are this package's ``Block``s, the interactions its
+    ``InteractionBlock``s.  The SyncBatchNorm modules run as they are, on [rows, C].
+
+    ``pretrained`` is a state dict (or an object with one under ``state_dict`` / ``model``) or a path for torch.load; it is
+    loaded non-strict, a ``pos_embed`` of another grid size resized first, as TIMMVisionTransformer.init_weights does.
+    As in the reference the position grid is ``pretrain_size // 16`` squared and the pyramid strides assume ``patch_size`` 16.
+
+    The two reference copies differ in three places.  The segmentation copy (mmseg_custom) takes ``pretrained`` and ``with_cp``
+    explicitly and hands ``with_cp`` to the interaction blocks too (here: always).  And with ``add_vit_feature`` it adds, to
+    f1 .. f4, the ViT tokens as they stand after interaction 1 .. 4 (so it needs exactly four interactions), where the
+    detection copy adds the final tokens to all four: ``vit_feature_per_interaction=True`` selects the segmentation form."""
+
+    def __init__(self, pretrain_size=224, num_heads=12, conv_inplane=64, n_points=4, deform_num_heads=6, init_values=0.,
+                 interaction_indexes=None, with_cffn=True, cffn_ratio=0.25, deform_ratio=1.0, add_vit_feature=True, pretrained=None,
+                 use_extra_extractor=True, with_cp=False, img_size=None, patch_size=16, in_chans=3, residual_indices=(), embed_dim=768,
+                 depth=12, mlp_ratio=4., qkv_bias=True, drop_rate=0., attn_drop_rate=0., drop_path_rate=0., layer_scale=True,
+                 norm_layer=None, act_layer=None, window_attn=False, window_size=14, vit_feature_per_interaction=False):
+        super().__init__()
+        if patch_size != 16:
+            raise MetaEncError(f"ViTAdapter: patch_size = {patch_size}: the pyramid strides and the position grid assume 16, as the reference's do")
+        if in_chans != 3:
+            raise MetaEncError(f"ViTAdapter: in_chans = {in_chans}: the spatial prior module reads 3 channels")
+        if residual_indices:
+            raise MetaEncError("ViTAdapter: residual_indices (ResBottleneckBlock in the encoder) is not implemented")
+        if not interaction_indexes:
+            raise MetaEncError("ViTAdapter: interaction_indexes = [[first block, last block], ...] is required")
+        img_size = pretrain_size if img_size is None else img_size
+        if img_size != pretrain_size:
+            raise MetaEncError(f"ViTAdapter: img_size = {img_size} and pretrain_size = {pretrain_size} must agree (one position table)")
+        for first, last in interaction_indexes:
+            if not 0 <= first <= last < depth:
+                raise MetaEncError(f"ViTAdapter: interaction_indexes entry [{first}, {last}] is not a block range of depth {depth}")
+        if vit_feature_per_interaction and add_vit_feature and len(interaction_indexes) != 4:
+            raise MetaEncError("ViTAdapter: vit_feature_per_interaction needs exactly four interactions")
+        norm_layer = norm_layer or _ADAPTER_NORM
+        act_layer = act_layer or nn.GELU
+        self.num_features = self.embed_dim = embed_dim
+        self.num_tokens = 1
+        self.norm_layer, self.act_layer = norm_layer, act_layer
+        self.drop_path_rate, self.drop_rate = drop_path_rate, drop_rate
+        self.img_size, self.patch_size = (img_size, img_size), patch_size
+        self.interpolate_mode = "bicubic"
+        self.pretrain_size = (pretrain_size, pretrain_size)
+        self.interaction_indexes = [list(p) for p in interaction_indexes]
+        self.add_vit_feature = bool(add_vit_feature)
+        self.vit_feature_per_interaction = bool(vit_feature_per_interaction)
+        self.with_cp = bool(with_cp)
+        self.cls_token = None
+        windowed = list(window_attn) if isinstance(window_attn, (list, tuple)) else [window_attn] * depth
+        sizes = list(window_size) if isinstance(window_size, (list, tuple)) else [window_size] * depth
+        if len(windowed) != depth or len(sizes) != depth:
+            raise MetaEncError(f"ViTAdapter: window_attn / window_size lists must have depth = {depth} entries")
+        self.patch_embed = _AdapterPatchEmbed(img_size=img_size, patch_size=patch_size, in_c=in_chans, embed_dim=embed_dim)
+        self.pos_embed = nn.Parameter(torch.zeros(1, self.patch_embed.num_patches + self.num_tokens, embed_dim))
+        self.pos_drop = nn.Dropout(p=drop_rate)
+        dpr = [v.item() for v in torch.linspace(0, drop_path_rate, depth)]
+        self.blocks = nn.Sequential(*[Block(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, drop=drop_rate,
+                                            attn_drop=attn_drop_rate, drop_path=dpr[i], norm_layer=norm_layer, act_layer=act_layer,
+                                            windowed=bool(windowed[i]), window_size=sizes[i] if sizes[i] else 14, layer_scale=layer_scale)
+                                      for i in range(depth)])
+        self.num_block = depth
+        self._cp_blocks = [_Checkpointed(b) for b in self.blocks] if self.with_cp else None
+        self.level_embed = nn.Parameter(torch.zeros(3, embed_dim))
+        self.spm = SpatialPriorModule(inplanes=conv_inplane, embed_dim=embed_dim)
+        n = len(self.interaction_indexes)
+        self.interactions = nn.Sequential(*[
+            InteractionBlock(dim=embed_dim, num_heads=deform_num_heads, n_points=n_points, init_values=init_values,
+                             drop_path=drop_path_rate, norm_layer=norm_layer, with_cffn=with_cffn, cffn_ratio=cffn_ratio,
+                             deform_ratio=deform_ratio, extra_extractor=(i == n - 1 and bool(use_extra_extractor)), with_cp=with_cp)
+            for i in range(n)])
+        self.up = nn.ConvTranspose2d(embed_dim, embed_dim, 2, 2)
+        self.norm1, self.norm2 = nn.SyncBatchNorm(embed_dim), nn.SyncBatchNorm(embed_dim)
+        self.norm3, self.norm4 = nn.SyncBatchNorm(embed_dim), nn.SyncBatchNorm(embed_dim)
+        self.up.apply(self._init_weights)
+        self.spm.apply(self._init_weights)
+        self.interactions.apply(self._init_weights)
+        self.apply(self._init_deform_weights)
+        nn.init.normal_(self.level_embed)
+        self.init_weights(pretrained)
+
+    def _init_weights(self, m):
+        """Linear: truncated normal(std 0.02), zero bias; LayerNorm / BatchNorm2d: one and zero; Conv2d / ConvTranspose2d:
+        normal(0, sqrt(2 / fan_out)) with fan_out = k k out_channels / groups, zero bias (vit_adapter.py:58-71)"""
+        if isinstance(m, nn.Linear):
+            nn.init.trunc_normal_(m.weight, std=.02)
+            if m.bias is not None:
+                nn.init.constant_(m.bias, 0)
+        elif isinstance(m, (nn.LayerNorm, nn.BatchNorm2d)):
+            nn.init.constant_(m.bias, 0)
+            nn.init.constant_(m.weight, 1.0)
+        elif isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
+            fan_out = m.kernel_size[0] * m.kernel_size[1] * m.out_channels // m.groups
+            m.weight.data.normal_(0, math.sqrt(2.0 / fan_out))
+            if m.bias is not None:
+                m.bias.data.zero_()
+
+    def _init_deform_weights(self, m):
+        if isinstance(m, MSDeformAttn):
+            m._reset_parameters()
+
+    def init_weights(self, pretrained=None):
+        """load ``pretrained`` (None: nothing) non-strict; returns load_state_dict's (missing, unexpected) report"""
+        if pretrained is None:
+            return None
+        if isinstance(pretrained, (str, bytes)) or hasattr(pretrained, "__fspath__"):
+            pretrained = torch.load(pretrained, map_location="cpu", weights_only=True)
+        if isinstance(pretrained, nn.Module):
+            pretrained = pretrained.state_dict()
+        if not isinstance(pretrained, dict):
+            raise MetaEncError(f"ViTAdapter: pretrained must be a state dict or a path (got {type(pretrained).__name__})")
+        for key in ("state_dict", "model"):
+            if key in pretrained and isinstance(pretrained[key], dict):
+                pretrained = pretrained[key]
+        sd = dict(pretrained)
+        pe = sd.get("pos_embed")
+        if pe is not None and pe.shape != self.pos_embed.shape:
+            side = int(math.sqrt(pe.shape[1] - 1))
+            if side * side != pe.shape[1] - 1 or pe.shape[-1] != self.embed_dim:
+                raise MetaEncError(f"ViTAdapter: pretrained pos_embed {tuple(pe.shape)} is not a cls row plus a square grid of width {self.embed_dim}")
+            g = self.img_size[0] // self.patch_size
+            grid = pe[:, 1:].float().reshape(1, side, side, -1).permute(0, 3, 1, 2)
+            grid = F.interpolate(grid, size=(g, g), mode="bicubic", align_corners=False)      # (a one-off at load time, on the CPU)
+            sd["pos_embed"] = torch.cat([pe[:, :1].float(), grid.flatten(2).transpose(1, 2)], dim=1)
+        return self.load_state_dict(sd, strict=False)
+
+    def _get_pos_embed(self, H, W):
+        """the position table without its cls row, resampled (bicubic) from the pretrain grid to H x W: [1, H W, D]"""
+        g = (self.pretrain_size[0] // 16, self.pretrain_size[1] // 16)
+        table = self.pos_embed[0, 1:]
+        if g == (H, W):
+            return table.unsqueeze(0)
+        return _PosResizeFn.apply(table, g, (H, W)).unsqueeze(0)
+
+    def _add_level_embed(self, c2, c3, c4):
+        return c2 + self.level_embed[0], c3 + self.level_embed[1], c4 + self.level_embed[2]
+
+    def forward(self, x):
+        _check_image("ViTAdapter", x)
+        B, Cimg, Himg, Wimg = x.shape
+        if Cimg != 3:
+            raise MetaEncError(f"ViTAdapter: the image has {Cimg} channels, 3 expected")
+        if Himg % 32 or Wimg % 32 or min(Himg, Wimg) < 32:
+            raise MetaEncError(f"ViTAdapter: image {Himg} x {Wimg}: height and width must be multiples of 32")
+        d1, d2 = deform_inputs(x)
+        c1, c2, c3, c4, _ = self.spm.forward_rows(x)
+        c2, c3, c4 = self._add_level_embed(c2, c3, c4)
+        n2, n3 = c2.shape[1], c3.shape[1]
+        c = torch.cat([c2, c3, c4], dim=1)
+        H, W = Himg // 16, Wimg // 16
+        tok = self.patch_embed(x)
+        D = tok.shape[-1]
+        tok = self.pos_drop(tok.float() + self._get_pos_embed(H, W))
+        outs = []
+        for layer, (first, last) in zip(self.interactions, self.interaction_indexes):
+            blocks = self._cp_blocks[first:last + 1] if self.with_cp and torch.is_grad_enabled() else self.blocks[first:last + 1]
+            tok, c = layer(tok, c, blocks, d1, d2, H, W)
+            outs.append(tok)
+        c2 = c[:, :n2].reshape(-1, D)
+        c3 = c[:, n2:n2 + n3].reshape(-1, D)
+        c4 = c[:, n2 + n3:].reshape(-1, D)
+        c1 = conv_transpose2x2_rows(_autocast_rows(c2), self.up.weight, self.up.bias, B, 2 * H, 2 * W, add=c1)
+        if self.add_vit_feature:
+            x1, x2, x3, x4 = (t.reshape(-1, D).float() for t in (outs if self.vit_feature_per_interaction else [tok] * 4))
+            c1 = c1 + resize_rows_batched(x1, B, H, W, scale_factor=4)
+            c2 = c2 + resize_rows_batched(x2, B, H, W, scale_factor=2)
+            c3 = c3 + x3
+            c4 = c4 + resize_rows_batched(x4, B, H, W, scale_factor=0.5)
+        f1 = _rows_to_image(self.norm1(c1), B, 4 * H, 4 * W)
+        f2 = _rows_to_image(self.norm2(c2), B, 2 * H, 2 * W)
+        f3 = _rows_to_image(self.norm3(c3), B, H, W)
+        f4 = _rows_to_image(self.norm4(c4), B, H // 2, W // 2)
+        return [f1, f2, f3, f4]
