@@ -604,6 +604,49 @@ int me_ms_deform_attn_bwd(const float* value, const int32_t* spatial_shapes, con
                           const float* attn, const float* dout, float* dvalue, float* dloc, float* dattn, int N, int S, int M, int D,
                           int Lq, int L, int P, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ graph tokenizer (TokenGT GraphFeatureTokenizer)
+ * Data2Seq/Graph.py:43-305 behind its node-identifier Linears: one launch assembles padded_feature [B, 2 + T, C] (ME_F32 or
+ * ME_BF16), padded_index [B, T, 2] int64 and padding_mask [B, 2 + T] bool from the collated batch.  All pointers of the descriptor
+ * are DEVICE pointers; tables, token rows, Z and perturb are fp32, 16-byte aligned, C a multiple of 4.
+ *   node_data [Sn, Fn], edge_data [Se, Fe] int64 rows into atom [atom_rows, C] / edge [edge_rows, C]; edge_index [2, Se] int64,
+ *   node numbers local to each graph; offsets int32 [2 (B + 1)]: the exclusive prefix sums of node_num, then those of edge_num;
+ *   T = max_b (node_num[b] + edge_num[b]), max_n = max_b node_num[b].  order [2, C] (type id), Z [Sn, 2 C] (Z_a | Z_b: the
+ *   node identifiers projected through the two halves of the identifier Linears) and perturb [B, max_n, C] may each be NULL.
+ * Row (b, r) of padded_feature: r = 0 graph_token, r = 1 null_token; node i of graph b: sum_f atom[node_data[i, f]]
+ *   (+ perturb[b, i]) + Z_a[i] + Z_b[i] + order[1]; edge (u, v): sum_f edge[edge_data[e, f]] + Z_a[u] + Z_b[v] + order[u == v];
+ *   rows behind a graph's last edge are exact zeros (and padding_mask true there).  Row 0 of the tables is read like any other.
+ *   Index VALUES are a precondition (as for nn.Embedding / gather): a table index or a node number out of range is clamped for
+ *   the read (no fault) and the row's content is then unspecified.
+ * me_graph_tokens_bwd: from dout [B, 2 + T, C] fp32 the gradients d_atom [atom_rows, C], d_edge [edge_rows, C], d_graph [C],
+ *   d_null [C], d_order [2, C], dZ [Sn, 2 C], d_perturb [B, max_n, C]; any may be NULL.  Every element of what is asked for is
+ *   written: table rows no token references and row 0 of both tables (padding_idx = 0) get exact zeros.  Deterministic (no float
+ *   atomics): the index lists are inverted by a counting sort (table indices in chunks of 512 positions, so that a value shared by
+ *   every node costs no more than a rare one), a table row sums its list in segments of 64 entries and then the segments, both in
+ *   ascending position; the column sums run per graph, then over the graphs in order.  Two runs are bit-identical.
+ *   parts: ME_GRAPH_BWD_INDEX builds the inverted lists into the workspace, ME_GRAPH_BWD_GATHER forms the gradients from them;
+ *   pass both unless the same batch structure is reused.  workspace: me_graph_tokens_bwd_workspace(d) bytes, 16-byte aligned. */
+typedef struct me_graph_desc {
+    const int64_t* node_data;
+    const int64_t* edge_data;
+    const int64_t* edge_index;
+    const int32_t* offsets;
+    const float* atom;
+    const float* edge;
+    const float* graph_token;
+    const float* null_token;
+    const float* order;
+    const float* Z;
+    const float* perturb;
+    int32_t B, T, C, Fn, Fe, Sn, Se, max_n, atom_rows, edge_rows;
+} me_graph_desc;
+enum { ME_GRAPH_BWD_INDEX = 1, ME_GRAPH_BWD_GATHER = 2 };
+int me_graph_tokens_fwd(const me_graph_desc* d, void* padded_feature, int out_dtype, int64_t* padded_index,
+                        uint8_t* padding_mask, void* stream);
+size_t me_graph_tokens_bwd_workspace(const me_graph_desc* d);
+int me_graph_tokens_bwd(const me_graph_desc* d, const float* dout, float* d_atom, float* d_edge, float* d_graph,
+                        float* d_null, float* d_order, float* dZ, float* d_perturb, int parts, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ position-embedding table resize
  * Replaces TIMMVisionTransformer.resize_pos_embed (Image/detection/mmdet_custom/models/backbones/base/vit.py:459-486,
  * also vit_adapter.py:73-78): the [h*w, cols] grid part of a pos-embed table resampled to [H*W, cols] with

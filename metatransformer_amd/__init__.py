@@ -13,7 +13,7 @@ from .heads import (ClassifierHead, ClsHead, FeaturePropogation, P3Embed, PointP
 from .adapter import (ConvFFN, DWConv, Extractor, Injector, InteractionBlock, MSDeformAttn, SpatialPriorModule, ViTAdapter,  # noqa: F401
                       conv3x3_rows, conv_transpose2x2_rows, deform_inputs, get_reference_points, max_pool3x3s2_rows, ms_deform_attn,
                       resize_rows_batched)
-from .data2seq import (AcousticPatchEmbed, Data2Seq, DataEmbedding, PatchEmbed, VideoPatchEmbed,  # noqa: F401
+from .data2seq import (AcousticPatchEmbed, Data2Seq, DataEmbedding, GraphFeatureTokenizer, PatchEmbed, VideoPatchEmbed,  # noqa: F401
                        sinusoid_table, video_sinusoid_table)
 
 __all__ = ["Block", "Attention", "Mlp", "build_encoder", "set_fp32_mode", "encoder_flops_per_sample", "encoder_forward_inference", "Data2Seq", "PatchEmbed",
@@ -22,4 +22,5 @@ __all__ = ["Block", "Attention", "Mlp", "build_encoder", "set_fp32_mode", "encod
            "furthest_point_sample", "knn_indices", "group_features", "pool_tokens",
            "FeaturePropogation", "PointViTDecoder", "PointViTPartDecoder", "SegHead", "three_nn", "three_interpolation", "load_encoder_checkpoint", "save_encoder_checkpoint", "pack_encoder",
            "ms_deform_attn", "MSDeformAttn", "Injector", "Extractor", "ConvFFN", "DWConv", "InteractionBlock", "deform_inputs", "get_reference_points",
-           "conv3x3_rows", "max_pool3x3s2_rows", "resize_rows_batched", "conv_transpose2x2_rows", "SpatialPriorModule", "ViTAdapter"]
+           "conv3x3_rows", "max_pool3x3s2_rows", "resize_rows_batched", "conv_transpose2x2_rows", "SpatialPriorModule", "ViTAdapter",
+           "GraphFeatureTokenizer"]

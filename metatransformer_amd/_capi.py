@@ -29,6 +29,7 @@ ME_COMM_ID_BYTES = 128
 ME_RESIZE_BILINEAR, ME_RESIZE_BICUBIC = 0, 1
 ME_POOL_MEAN, ME_POOL_MAX, ME_POOL_FIRST = 0, 1, 2
 ME_GROUP_DP, ME_GROUP_DP_FJ, ME_GROUP_DP_DF, ME_GROUP_DP_FJ_DF = 0, 1, 2, 3
+ME_GRAPH_BWD_INDEX, ME_GRAPH_BWD_GATHER = 1, 2
 
 
 class MetaEncError(RuntimeError):
@@ -71,6 +72,13 @@ class PatchEmbedDesc(ctypes.Structure):
                    ("pos", c_void_p), ("pos_dtype", c_int32), ("ld_pos", c_int64), ("prefix_rows", c_int32),
                    ("out", c_void_p), ("out_dtype", c_int32), ("ld_out", c_int64),
                    ("workspace", c_void_p), ("workspace_bytes", c_int64)])
+
+
+class GraphDesc(ctypes.Structure):
+    """Mirror of ``struct me_graph_desc`` (include/metaenc.h)."""
+    _fields_ = ([(n, c_void_p) for n in ("node_data", "edge_data", "edge_index", "offsets", "atom", "edge", "graph_token", "null_token",
+                                         "order", "Z", "perturb")]
+                + [(n, c_int32) for n in ("B", "T", "C", "Fn", "Fe", "Sn", "Se", "max_n", "atom_rows", "edge_rows")])
 
 
 class GemmProfileRec(ctypes.Structure):
@@ -216,6 +224,10 @@ SIGNATURES = {
     "me_ms_deform_attn_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "me_ms_deform_attn_bwd": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "me_graph_tokens_fwd": (c_int, [POINTER(GraphDesc), c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "me_graph_tokens_bwd_workspace": (c_size_t, [POINTER(GraphDesc)]),
+    "me_graph_tokens_bwd": (c_int, [POINTER(GraphDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_size_t, c_void_p]),
     "me_pool_tokens": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "me_pool_tokens_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "me_resize_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -10,10 +10,13 @@ modalities whose tokenizers are on the north-star path (SURVEY.md 8a rows a12-a1
   video        Video/models/modeling_finetune.py:263-297  Conv3d(3, C, k=s=(2,16,16)) tubelets
                (Data2Seq/Video.py is broken in the reference)
   time-series  Data2Seq/Time_Series.py:109-126  Conv1d k3 circular + sinusoid PE + temporal-embedding gathers
+  graph        Data2Seq/Graph.py:43-305      TokenGT GraphFeatureTokenizer: node / edge embedding sums, node identifiers, type id
+               -> one GEMM over the node rows + one assembly kernel (graph preprocessing -- Laplacian eigenvectors, the
+               collator -- stays with the caller)
 
 Parameter names follow the reference modules (``proj.weight`` / ``proj.bias``;
-``value_embedding.tokenConv.weight`` ...), so their state_dicts interchange.  The text / graph / hyper-spectral
-tokenizers of the reference are CLIP / eigen-decomposition / broken glue and are out of scope.
+``value_embedding.tokenConv.weight``; ``atom_encoder.weight`` ...), so their state_dicts interchange.  The text and
+hyper-spectral tokenizers of the reference are CLIP / broken glue and are out of scope.
 """
 from __future__ import annotations
 
@@ -23,6 +26,7 @@ from typing import Optional
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _capi, ops
 from ._capi import ME_GEMM_TN, MetaEncError, check, dtype_code, ptr, stream_ptr
@@ -326,6 +330,292 @@ class _TSEmbedFn(torch.autograd.Function):
         return (None, dw, None, None, None, None, None, None)
 
 
+class _NodeIdProjFn(torch.autograd.Function):
+    """Z [rows, 2C] = P [rows, K] W^T on me_gemm, the dtype policy of heads.linear (fp32 rows -> the exact fp32 MFMA, bf16 rows ->
+    bf16 MFMA, fp32 result either way).  The identifiers carry no gradient: backward is the one TN GEMM dW = dZ^T P.  rows is a
+    multiple of 8 (the caller pads with zero rows), K a multiple of 8."""
+
+    @staticmethod
+    def forward(ctx, p, w):
+        wc = w.detach().to(p.dtype).contiguous()
+        ctx.save_for_backward(p)
+        ctx.wdt = w.dtype
+        return ops.gemm(p, wc, out_dtype=torch.float32)
+
+    @staticmethod
+    def backward(ctx, dz):
+        (p,) = ctx.saved_tensors
+        dw = ops.gemm(dz.to(p.dtype).contiguous(), p, op=ME_GEMM_TN, out_dtype=torch.float32)      # [2C, K]
+        return None, dw.to(ctx.wdt)
+
+
+def _graph_desc(node_data, edge_data, edge_index, offsets, atom, edge, graph_token, null_token, order, Z, perturb, dims):
+    d = _capi.GraphDesc()
+    d.node_data, d.edge_data, d.edge_index, d.offsets = ptr(node_data), ptr(edge_data), ptr(edge_index), ptr(offsets)
+    d.atom, d.edge, d.graph_token, d.null_token = ptr(atom), ptr(edge), ptr(graph_token), ptr(null_token)
+    d.order, d.Z, d.perturb = ptr(order), ptr(Z), ptr(perturb)
+    d.B, d.T, d.C, d.Fn, d.Fe, d.Sn, d.Se, d.max_n = dims
+    d.atom_rows, d.edge_rows = atom.shape[0], edge.shape[0]
+    return d
+
+
+def _f32c(t):
+    return None if t is None else t.detach().float().contiguous()
+
+
+class _GraphTokensFn(torch.autograd.Function):
+    """me_graph_tokens_fwd / _bwd (include/metaenc.h): the whole padded batch in one launch; backward gathers along inverted
+    index lists (deterministic).  Z has its rows padded to a multiple of 8 for the weight-gradient GEMM that follows."""
+
+    @staticmethod
+    def forward(ctx, atom, edge, graph_token, null_token, order, Z, perturb, node_data, edge_data, edge_index, offsets, dims, out_dtype):
+        lib = _capi.load()
+        B, T, C = dims[:3]
+        par = [_f32c(t) for t in (atom, edge, graph_token, null_token, order, Z, perturb)]
+        d = _graph_desc(node_data, edge_data, edge_index, offsets, *par, dims)
+        dev = node_data.device
+        out = torch.empty((B, T + 2, C), dtype=out_dtype, device=dev)
+        pidx = torch.empty((B, T, 2), dtype=torch.int64, device=dev)
+        pmask = torch.empty((B, T + 2), dtype=torch.bool, device=dev)
+        check(lib.me_graph_tokens_fwd(ctypes.byref(d), ptr(out), dtype_code(out_dtype), ptr(pidx), ptr(pmask), stream_ptr()),
+              "me_graph_tokens_fwd")
+        ctx.save_for_backward(node_data, edge_data, edge_index, offsets, par[0], par[1], par[2], par[3])
+        ctx.meta = (dims, tuple(None if t is None else (t.dtype, tuple(t.shape)) for t in (atom, edge, graph_token, null_token, order, Z, perturb)))
+        ctx.mark_non_differentiable(pidx, pmask)
+        return out, pmask, pidx
+
+    @staticmethod
+    def backward(ctx, dout, _dmask, _didx):
+        lib = _capi.load()
+        node_data, edge_data, edge_index, offsets, atom, edge, graph_token, null_token = ctx.saved_tensors
+        dims, meta = ctx.meta
+        dev = dout.device
+        dout = dout.contiguous()
+        if dout.dtype != torch.float32:
+            dout = ops.cast(dout, torch.float32)
+        grads = []
+        for need, m in zip(ctx.needs_input_grad[:7], meta):
+            grads.append(torch.empty(m[1], dtype=torch.float32, device=dev) if need and m is not None else None)
+        dZ = grads[5]
+        if dZ is not None and dZ.shape[0] > dims[5]:
+            dZ[dims[5]:].zero_()                                  # the zero rows Z was padded with
+        d = _graph_desc(node_data, edge_data, edge_index, offsets, atom, edge, graph_token, null_token, None, None, None, dims)
+        nbytes = lib.me_graph_tokens_bwd_workspace(ctypes.byref(d))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        check(lib.me_graph_tokens_bwd(ctypes.byref(d), ptr(dout), *[ptr(g) for g in grads],
+                                      _capi.ME_GRAPH_BWD_INDEX | _capi.ME_GRAPH_BWD_GATHER, ptr(ws), nbytes, stream_ptr()),
+              "me_graph_tokens_bwd")
+        grads = [g if g is None or g.dtype == m[0] else g.to(m[0]) for g, m in zip(grads, meta)]
+        return (*grads, None, None, None, None, None, None)
+
+
+def _init_graph_params(module, n_layers):
+    """Data2Seq/Graph.py:34-40: Linear weights N(0, 0.02 / sqrt(n_layers)), Embedding tables N(0, 0.02) -- row 0 included: the
+    padding rows are overwritten with noise, and read like any other row."""
+    if isinstance(module, nn.Linear):
+        module.weight.data.normal_(mean=0.0, std=0.02 / math.sqrt(n_layers))
+        if module.bias is not None:
+            module.bias.data.zero_()
+    if isinstance(module, nn.Embedding):
+        module.weight.data.normal_(mean=0.0, std=0.02)
+
+
+class GraphFeatureTokenizer(nn.Module):
+    """TokenGT graph tokenizer -- Data2Seq/Graph.py:43-305 (= Graph/metatransformer/modules/tokenizer.py): same constructor,
+    same state-dict keys, same initialisation.  ``forward(batched_data, perturb=None)`` takes the collator's dict (``node_data
+    [Sn, Fn]``, ``edge_data [Se, Fe]``, ``edge_index [2, Se]`` int64, ``node_num`` / ``edge_num`` Python lists, ``lap_eigvec
+    [Sn, k']``; ``in_degree`` / ``out_degree`` / ``lap_eigval`` are accepted and unused, as in the reference) and returns
+    ``(padded_feature [B, 2+T, C], padding_mask [B, 2+T] bool, padded_index [B, T, 2] int64)``.
+
+    The identifier Linears act on cat(P[u], P[v]), so W cat(P[u], P[v]) = W_a P[u] + W_b P[v]: all identifier kinds go through ONE
+    GEMM over the Sn node rows (Z = [P_rand | P_orf | P_lap] [W_a ; W_b]^T, [Sn, 2C]) and a token gathers two projected rows; the
+    [B, T, 2D] index embeddings are never built.  The rest -- embedding sums, perturbation, type id, special tokens, padding, index
+    and mask -- is one kernel (me_graph_tokens_fwd).  Backward is deterministic (me_graph_tokens_bwd).  Under torch.autocast the
+    GEMM takes bf16 operands (fp32 result); the tokens are fp32, or bf16 for bf16 parameters.
+
+    ``node_ids={"rand": [Sn, rand_node_id_dim], "orf": [Sn, orf_node_id_dim]}`` replaces the random draws (reproducible tokens).
+    Still PyTorch glue, on the input's device: the uniform draw and F.normalize of the rand identifiers, the batched QR of the orf
+    identifiers, pad / truncate to the configured widths, the training-mode eigenvector Dropout2d and random sign flip.
+    Preconditions, as in the reference: table indices inside their tables, edge_index inside each graph's node range."""
+
+    def __init__(self, num_atoms=1, num_edges=1, rand_node_id=1, rand_node_id_dim=768, orf_node_id=1, orf_node_id_dim=768,
+                 lap_node_id=1, lap_node_id_k=1, lap_node_id_sign_flip=1, lap_node_id_eig_dropout=1, type_id=1, hidden_dim=1,
+                 n_layers=1):
+        super().__init__()
+        self.encoder_embed_dim = hidden_dim
+        self.atom_encoder = nn.Embedding(num_atoms, hidden_dim, padding_idx=0)
+        self.edge_encoder = nn.Embedding(num_edges, hidden_dim, padding_idx=0)
+        self.graph_token = nn.Embedding(1, hidden_dim)
+        self.null_token = nn.Embedding(1, hidden_dim)
+        self.rand_node_id, self.rand_node_id_dim = rand_node_id, rand_node_id_dim
+        self.orf_node_id, self.orf_node_id_dim = orf_node_id, orf_node_id_dim
+        self.lap_node_id, self.lap_node_id_k, self.lap_node_id_sign_flip = lap_node_id, lap_node_id_k, lap_node_id_sign_flip
+        self.type_id = type_id
+        if rand_node_id:
+            self.rand_encoder = nn.Linear(2 * rand_node_id_dim, hidden_dim, bias=False)
+        if lap_node_id:
+            self.lap_encoder = nn.Linear(2 * lap_node_id_k, hidden_dim, bias=False)
+            self.lap_eig_dropout = nn.Dropout2d(p=lap_node_id_eig_dropout) if lap_node_id_eig_dropout > 0 else None
+        if orf_node_id:
+            self.orf_encoder = nn.Linear(2 * orf_node_id_dim, hidden_dim, bias=False)
+        if type_id:
+            self.order_encoder = nn.Embedding(2, hidden_dim)
+        self.apply(lambda m: _init_graph_params(m, n_layers=n_layers))
+
+    # ---- host-side checks and index arrays (Python lists and shapes only: no device synchronisation)
+    def _check(self, bd, perturb, node_ids):
+        who = "GraphFeatureTokenizer"
+        for k in ("node_data", "edge_data", "edge_index", "node_num", "edge_num"):
+            if k not in bd:
+                raise MetaEncError(f"{who}: batched_data has no '{k}'")
+        node_data, edge_data, edge_index = bd["node_data"], bd["edge_data"], bd["edge_index"]
+        for k in ("node_data", "edge_data", "edge_index"):
+            t = bd[k]
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise MetaEncError(f"{who}: {k} must be a CUDA tensor (no CPU fallback)")
+            if t.dtype != torch.int64:
+                raise MetaEncError(f"{who}: {k} must be int64 (got {t.dtype})")
+            if t.device != node_data.device:
+                raise MetaEncError(f"{who}: {k} is on {t.device}, node_data on {node_data.device}")
+        if self.atom_encoder.weight.device != node_data.device:
+            raise MetaEncError(f"{who}: parameters are on {self.atom_encoder.weight.device}, node_data on {node_data.device}")
+        node_num, edge_num = [int(v) for v in bd["node_num"]], [int(v) for v in bd["edge_num"]]
+        if len(node_num) == 0 or len(node_num) != len(edge_num):
+            raise MetaEncError(f"{who}: node_num / edge_num must be non-empty lists of one length (got {len(node_num)}, {len(edge_num)})")
+        if min(node_num) < 0 or min(edge_num) < 0:
+            raise MetaEncError(f"{who}: node_num / edge_num hold a negative count")
+        if node_data.dim() != 2 or sum(node_num) != node_data.size(0):
+            raise MetaEncError(f"{who}: node_data {tuple(node_data.shape)} must be [sum(node_num) = {sum(node_num)}, features]")
+        if edge_index.dim() != 2 or edge_index.size(0) != 2 or sum(edge_num) != edge_index.size(1):
+            raise MetaEncError(f"{who}: edge_index {tuple(edge_index.shape)} must be [2, sum(edge_num) = {sum(edge_num)}]")
+        if edge_data.dim() != 2 or sum(edge_num) != edge_data.size(0):
+            raise MetaEncError(f"{who}: edge_data {tuple(edge_data.shape)} must be [sum(edge_num) = {sum(edge_num)}, features]")
+        Sn, max_n, B = sum(node_num), max(node_num), len(node_num)
+        if self.lap_node_id:
+            lap = bd.get("lap_eigvec")
+            if not isinstance(lap, torch.Tensor) or not lap.is_cuda:
+                raise MetaEncError(f"{who}: lap_eigvec must be a CUDA tensor (no CPU fallback)")
+            if not lap.is_floating_point():
+                raise MetaEncError(f"{who}: lap_eigvec must be a floating-point tensor (got {lap.dtype})")
+            if lap.dim() != 2 or lap.size(0) != Sn:
+                raise MetaEncError(f"{who}: lap_eigvec {tuple(lap.shape)} must have one row per node ({Sn})")
+        if perturb is not None:
+            if not isinstance(perturb, torch.Tensor) or not perturb.is_cuda:
+                raise MetaEncError(f"{who}: perturb must be a CUDA tensor (no CPU fallback)")
+            if tuple(perturb.shape) != (B, max_n, self.encoder_embed_dim):
+                raise MetaEncError(f"{who}: perturb {tuple(perturb.shape)} must be [B, max(node_num), C] = "
+                                   f"({B}, {max_n}, {self.encoder_embed_dim})")
+        for kind, width in (("rand", self.rand_node_id_dim), ("orf", self.orf_node_id_dim)):
+            t = (node_ids or {}).get(kind)
+            if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or tuple(t.shape) != (Sn, width)):
+                raise MetaEncError(f"{who}: node_ids['{kind}'] must be a CUDA tensor [{Sn}, {width}]")
+        unknown = set(node_ids or {}) - {"rand", "orf"}
+        if unknown:
+            raise MetaEncError(f"{who}: node_ids has unknown kinds {sorted(unknown)} (rand, orf)")
+        return node_num, edge_num
+
+    @staticmethod
+    def _node_places(node_num, device):
+        """(graph of node [Sn], b * max_n + local number [Sn]) built on the host"""
+        max_n = max(node_num)
+        graph, flat = [], []
+        for b, n in enumerate(node_num):
+            graph.extend([b] * n)
+            flat.extend(range(b * max_n, b * max_n + n))
+        both = torch.tensor([graph, flat], dtype=torch.int64).to(device, non_blocking=True)
+        return both[0], both[1]
+
+    def _identifiers(self, bd, node_num, node_ids):
+        """[(kind, P [Sn, D] fp32, Linear weight [C, 2D])] in the reference's order of addition"""
+        node_ids = node_ids or {}
+        dev = bd["node_data"].device
+        Sn, B, max_n = sum(node_num), len(node_num), max(node_num)
+        places = None
+        out = []
+        if self.rand_node_id:
+            p = node_ids.get("rand")
+            if p is None:
+                p = F.normalize(torch.rand(Sn, self.rand_node_id_dim, device=dev, dtype=torch.float32), p=2, dim=1)
+            out.append(("rand", p.float(), self.rand_encoder.weight))
+        if self.orf_node_id:
+            p = node_ids.get("orf")
+            if p is None:
+                places = places or self._node_places(node_num, dev)
+                q, _ = torch.linalg.qr(torch.randn(B, max_n, max_n, device=dev), mode="reduced")
+                orf = F.normalize(q.transpose(2, 1), p=2, dim=2).reshape(B * max_n, max_n).index_select(0, places[1])
+                if self.orf_node_id_dim > max_n:
+                    orf = F.pad(orf, (0, self.orf_node_id_dim - max_n), value=0.0)
+                else:
+                    orf = orf[..., :self.orf_node_id_dim]
+                p = F.normalize(orf, p=2, dim=1)
+            out.append(("orf", p.float(), self.orf_encoder.weight))
+        if self.lap_node_id:
+            eig = bd["lap_eigvec"].float()
+            k = eig.size(-1)
+            eig = F.pad(eig, (0, self.lap_node_id_k - k), value=0.0) if self.lap_node_id_k > k else eig[:, :self.lap_node_id_k]
+            if self.lap_eig_dropout is not None:
+                eig = self.lap_eig_dropout(eig[..., None, None]).view(eig.size())
+            if self.lap_node_id_sign_flip and self.training:
+                places = places or self._node_places(node_num, dev)
+                sign = torch.rand(B, eig.size(1), device=dev, dtype=eig.dtype)
+                sign = torch.where(sign >= 0.5, 1.0, -1.0).to(eig.dtype)
+                eig = eig * sign.index_select(0, places[0])
+            out.append(("lap", eig, self.lap_encoder.weight))
+        return out
+
+    @torch.no_grad()
+    def node_identifiers(self, batched_data, node_ids=None):
+        """the [Sn, D] node identifiers a forward would use, by kind (fresh draws where node_ids gives none)"""
+        node_num, _ = self._check(batched_data, None, node_ids)
+        return {kind: p for kind, p, _ in self._identifiers(batched_data, node_num, node_ids)}
+
+    def _project(self, ids, Sn):
+        """Z [Sn padded to 8, 2C]: one GEMM for every identifier kind, K = the widths side by side (padded to a multiple of 8)"""
+        C = self.encoder_embed_dim
+        dev = ids[0][1].device
+        cdt = torch.bfloat16 if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") in (torch.bfloat16, torch.float16) \
+            else torch.float32
+        K = sum(p.shape[1] for _, p, _ in ids)
+        Kp, rows = (K + 7) // 8 * 8, (Sn + 7) // 8 * 8
+        P = torch.zeros((rows, Kp), dtype=cdt, device=dev)
+        ws, at = [], 0
+        for _, p, w in ids:
+            D = p.shape[1]
+            P[:Sn, at:at + D] = p
+            ws.append(w.view(C, 2, D).permute(1, 0, 2).reshape(2 * C, D))          # [W_a ; W_b]
+            at += D
+        if Kp != K:
+            ws.append(ws[0].new_zeros(2 * C, Kp - K))
+        W = ws[0] if len(ws) == 1 else torch.cat(ws, dim=1)
+        return _NodeIdProjFn.apply(P, W)
+
+    def forward(self, batched_data, perturb=None, node_ids=None):
+        node_num, edge_num = self._check(batched_data, perturb, node_ids)
+        node_data, edge_data, edge_index = (batched_data[k].contiguous() for k in ("node_data", "edge_data", "edge_index"))
+        dev = node_data.device
+        B, Sn, Se, max_n = len(node_num), sum(node_num), sum(edge_num), max(node_num)
+        T = max(n + e for n, e in zip(node_num, edge_num))
+        C = self.encoder_embed_dim
+        if C % 4 != 0:
+            raise MetaEncError(f"GraphFeatureTokenizer: hidden_dim {C} must be a multiple of 4")
+        offs = [0]
+        for n in node_num:
+            offs.append(offs[-1] + n)
+        offs.append(0)
+        for e in edge_num:
+            offs.append(offs[-1] + e)
+        offsets = torch.tensor(offs, dtype=torch.int32).to(dev, non_blocking=True)
+        ids = self._identifiers(batched_data, node_num, node_ids)
+        Z = self._project(ids, Sn) if ids and Sn > 0 else None
+        wdt = self.atom_encoder.weight.dtype
+        if wdt not in (torch.float32, torch.bfloat16):
+            raise MetaEncError(f"GraphFeatureTokenizer: parameter dtype {wdt} unsupported (fp32, bf16)")
+        dims = (B, T, C, node_data.shape[1], edge_data.shape[1], Sn, Se, max_n)
+        order = self.order_encoder.weight if self.type_id else None
+        return _GraphTokensFn.apply(self.atom_encoder.weight, self.edge_encoder.weight, self.graph_token.weight, self.null_token.weight,
+                                    order, Z, perturb, node_data, edge_data, edge_index, offsets, dims, wdt)
+
+
 class Data2Seq(nn.Module):
     """``Data2Seq(modality, dim)`` dispatcher -- API shape of Data2Seq/Data2Seq.py:19-55 (which itself does not run
     as written: SURVEY.md appendix A).  Multi-modal use concatenates along tokens exactly as README.md:118-122:
@@ -342,8 +632,10 @@ class Data2Seq(nn.Module):
             self.embed = VideoPatchEmbed(embed_dim=dim, **kw)
         elif modality == "time-series":
             self.embed = DataEmbedding(c_in=kw.pop("c_in", 1), d_model=dim, **kw)
+        elif modality == "graph":       # Data2Seq/Data2Seq.py:32: both identifier widths follow dim, everything else default
+            self.embed = GraphFeatureTokenizer(rand_node_id_dim=dim, orf_node_id_dim=dim, **kw)
         else:
-            raise MetaEncError(f"modality '{modality}' has no HIP tokenizer (in scope: image, audio, video, time-series)")
+            raise MetaEncError(f"modality '{modality}' has no HIP tokenizer (in scope: image, audio, video, time-series, graph)")
 
     def forward(self, data, *args, **kw):
         return self.embed(data, *args, **kw)
