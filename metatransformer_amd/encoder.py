@@ -271,6 +271,13 @@ class _WeightCache:
         return mine
 
 
+# seed offsets of the stochastic ops of one training-mode Block call (Block.forward draws ONE int64 seed per call; every mask is
+# u01_hash(seed + offset, index) of csrc/common.h, regenerated in backward -- the contract restated by tests/stoch_cases.py)
+SEED_BRANCH1 = 1         # proj_drop + drop-path of the attention branch (me_dropout_add)
+SEED_MLP_HIDDEN = 2      # Mlp.drop on the hidden activation behind GELU
+SEED_BRANCH2 = 3         # Mlp.drop + drop-path of the MLP branch
+SEED_ATTN_DROP = 4       # attn_drop on the attention probabilities (me_attention_fwd / _bwd)
+
 _exact_notes = set()
 
 
@@ -336,7 +343,7 @@ class _BlockFn(torch.autograd.Function):
         p_attn = stoch[3] if stoch is not None else 0.0      # training-mode attn_drop (attention.py:33)
         if win is None:
             o, lse = ops.attention_fwd(qkv, B, N, H, hd, blk.attn.scale, need_lse=need_grad, p_drop=p_attn, fp8=fp8,
-                                       seed=stoch[2] + 4 if stoch is not None else 0)
+                                       seed=stoch[2] + SEED_ATTN_DROP if stoch is not None else 0)
             o_att = o
         else:
             # windowed attention (Image/detection/.../base/vit.py:160-190): qkv rows regrouped into ws x ws windows
@@ -345,7 +352,7 @@ class _BlockFn(torch.autograd.Function):
             nwin = -(-gh_ // ws) * -(-gw_ // ws)
             qkv = ops.window_rows(qkv, B, gh_, gw_, ws, merge=False)
             o_att, lse = ops.attention_fwd(qkv, B * nwin, ws * ws, H, hd, blk.attn.scale, need_lse=need_grad, p_drop=p_attn,
-                                           seed=stoch[2] + 4 if stoch is not None else 0)
+                                           seed=stoch[2] + SEED_ATTN_DROP if stoch is not None else 0)
             o = ops.window_rows(o_att, B, gh_, gw_, ws, merge=True)
         # layer-scale with gradients: d gamma = colsum(dy * UNSCALED branch output), so the branch output is kept and
         # gamma is applied by the residual kernel instead of the GEMM epilogue
@@ -356,7 +363,7 @@ class _BlockFn(torch.autograd.Function):
             x1 = ops.gemm(o, cache.fwd("proj", projw, cdt), bias=projb, residual=x2, out_dtype=rdt, colscale=g1)
         else:                 # training-mode proj_drop / drop_path: x1 = x + drop_path(gamma1 * dropout(proj(o)))
             t1 = ops.gemm(o, cache.fwd("proj", projw, cdt), bias=projb, out_dtype=rdt, colscale=None if ls_grad else g1)
-            x1 = ops.dropout_add(t1, x2, N, p_drop, p_path, seed + 1, colscale=g1 if ls_grad else None)
+            x1 = ops.dropout_add(t1, x2, N, p_drop, p_path, seed + SEED_BRANCH1, colscale=g1 if ls_grad else None)
         xn2, mean2, rstd2 = ops.layernorm_fwd(x1, n2w, n2b, blk.eps, cdt, save_stats=need_grad)
         hpre = torch.empty((M, fc1w.shape[0]), dtype=cdt, device=x.device) if need_grad else None
         a = ops.gemm(xn2, cache.fwd("fc1", fc1w, cdt), bias=fc1b, act=ME_ACT_GELU, preact=hpre,
@@ -365,9 +372,9 @@ class _BlockFn(torch.autograd.Function):
             y = ops.gemm(a, cache.fwd("fc2", fc2w, cdt), bias=fc2b, residual=x1, out_dtype=rdt, colscale=g2)
         else:                 # Mlp: fc1 -> act -> drop -> fc2 -> drop (mlp.py:29-35), then drop_path + residual
             if p_drop > 0:
-                a = ops.dropout_add(a, None, N, p_drop, 0.0, seed + 2)
+                a = ops.dropout_add(a, None, N, p_drop, 0.0, seed + SEED_MLP_HIDDEN)
             t2 = ops.gemm(a, cache.fwd("fc2", fc2w, cdt), bias=fc2b, out_dtype=rdt, colscale=None if ls_grad else g2)
-            y = ops.dropout_add(t2, x1, N, p_drop, p_path, seed + 3, colscale=g2 if ls_grad else None)
+            y = ops.dropout_add(t2, x1, N, p_drop, p_path, seed + SEED_BRANCH2, colscale=g2 if ls_grad else None)
         if not ls_grad:
             t1 = t2 = None
 
@@ -528,27 +535,27 @@ class _BlockFn(torch.autograd.Function):
             return ops.dropout_add(dm, None, N, 0.0, 0.0, 0, out_dtype=cdt, colscale=g), dg
 
         # ---- MLP branch: y = x1 + gamma2 * fc2(gelu(fc1(LN2(x1))))
-        dy_c, d_g2 = branch_grad(dy2, t2, g2, seed + 3)
+        dy_c, d_g2 = branch_grad(dy2, t2, g2, seed + SEED_BRANCH2)
         dh = ops.gemm(dy_c, cache.transposed("fc2", fc2w, cdt), aux=hpre, flags=ME_GEMM_AUX_IS_FACTOR)   # dA * gelu'(h)
         if stoch is not None and p_drop > 0:
-            dh = ops.dropout_add(dh, None, N, p_drop, 0.0, seed + 2)
+            dh = ops.dropout_add(dh, None, N, p_drop, 0.0, seed + SEED_MLP_HIDDEN)
         d_fc2w, d_fc2b = wgrad(dy_c, a, blk.mlp.fc2, ng[11], ng[12] and ctx.has_bias[3])
         dxn2 = ops.gemm(dh, cache.transposed("fc1", fc1w, cdt))
         d_fc1w, d_fc1b = wgrad(dh, xn2, blk.mlp.fc1, ng[9], ng[10] and ctx.has_bias[2])
         dx1, d_n2w, d_n2b = ln_bwd(dxn2, x1, mean2, rstd2, blk.norm2, dy2, ng[7] or ng[8])
 
         # ---- attention branch: x1 = x + proj(attn(qkv(LN1(x))))
-        dx1_c, d_g1 = branch_grad(dx1, t1, g1, seed + 1)
+        dx1_c, d_g1 = branch_grad(dx1, t1, g1, seed + SEED_BRANCH1)
         do = ops.gemm(dx1_c, cache.transposed("proj", projw, cdt))
         d_projw, d_projb = wgrad(dx1_c, o, blk.attn.proj, ng[5], ng[6] and ctx.has_bias[1])
         if ctx.win is None:
-            dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, H, hd, blk.attn.scale, p_drop=p_attn, seed=seed + 4)
+            dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, H, hd, blk.attn.scale, p_drop=p_attn, seed=seed + SEED_ATTN_DROP)
         else:                 # the same regrouping on the gradient; padded rows are constants (no gradient leaves them)
             gh_, gw_, ws = ctx.win
             nwin = -(-gh_ // ws) * -(-gw_ // ws)
             do_w = ops.window_rows(do, B, gh_, gw_, ws, merge=False)
             dqkv_w = ops.attention_bwd(qkv, o_att, do_w, lse, B * nwin, ws * ws, H, hd, blk.attn.scale, p_drop=p_attn,
-                                       seed=seed + 4)
+                                       seed=seed + SEED_ATTN_DROP)
             dqkv = ops.window_rows(dqkv_w, B, gh_, gw_, ws, merge=True)
         dxn1 = ops.gemm(dqkv, cache.transposed("qkv", qkvw, cdt))
         d_qkvw, d_qkvb = wgrad(dqkv, xn1, blk.attn.qkv, ng[3], ng[4] and ctx.has_bias[0])
