@@ -24,7 +24,7 @@ Compute dtype: bf16 when the parameters are bf16 or when called under ``torch.au
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 import warnings
 
 import torch
@@ -32,15 +32,7 @@ import torch.nn as nn
 
 from . import _capi, ops
 from ._capi import ME_ACT_GELU, ME_GEMM_AUX_IS_FACTOR, ME_GEMM_SAVE_GELU_GRAD, ME_GEMM_TN, MetaEncError
-
-
-def _tensor_version(t: torch.Tensor):
-    """``t._version``, or None for inference tensors (``torch.inference_mode()``: they carry no version counter and reading
-    the attribute raises)."""
-    try:
-        return t._version
-    except RuntimeError:
-        return None
+from .weight_cache import _WeightCache, _tensor_version      # noqa: F401 -- (_WeightCache stays importable from here)
 
 
 def _resolve_eps(norm_layer) -> float:
@@ -82,195 +74,6 @@ class Attention(nn.Module):
         self.proj_drop = nn.Dropout(proj_drop)
 
 
-class _WeightCache:
-    """Compute-dtype copies of the four weight matrices of a block ([out,in] for forward, transposed
-    [in,out] for dgrad), rebuilt when the parameter changes (optimizer step / load_state_dict / .to()).
-
-    Two shortcuts keep the per-step refresh off the critical path: forward bf16 copies come straight out of the fused
-    optimizer's bf16 mirror when the parameters live in a parallel.FlatParams, and a stale TRANSPOSED copy triggers one
-    batched transpose of every stale weight of every live Block on the device (one launch instead of four per block)."""
-
-    _live = None          # weakref.WeakSet of all caches (set up lazily)
-
-    def __init__(self):
-        import weakref
-        self._fwd = {}
-        self._tr = {}
-        self._fold = {}
-        self._x3 = {}
-        self._owner = None          # weakref to the Block, set by Block.__init__
-        if _WeightCache._live is None:
-            _WeightCache._live = weakref.WeakSet()
-        _WeightCache._live.add(self)
-
-    # a cache is derived state: copies / pickles of a Block start with an empty one (re-bound to the new owner on first use)
-    def __deepcopy__(self, memo):
-        return _WeightCache()
-
-    def __getstate__(self):
-        return {}
-
-    def __setstate__(self, state):
-        self.__init__()
-
-    def bind(self, blk) -> None:
-        if self._owner is None or self._owner() is not blk:
-            import weakref
-            self._owner = weakref.ref(blk)
-
-    @staticmethod
-    def _key(p: torch.Tensor, dtype):
-        # WEIGHT_EPOCH covers the fused optimizer, which writes parameters through raw pointers (no _version bump); it
-        # only ever touches parameters that live in a parallel.FlatParams, so other (e.g. frozen) encoders keep their copies
-        epoch = ops.WEIGHT_EPOCH if hasattr(p, "_me_flat") else 0
-        return (p.data_ptr(), _tensor_version(p), epoch, p.dtype, dtype, p.device)
-
-    def fwd(self, name: str, p: torch.Tensor, dtype) -> torch.Tensor:
-        if p.dtype == dtype:
-            return p.detach()
-        if dtype == torch.bfloat16:
-            flat = getattr(p, "_me_flat", None)
-            if flat is not None:
-                v = flat.bf16_view(p)
-                if v is not None:
-                    return v
-        k = self._key(p, dtype)
-        slot = (name, p.device)       # nn.DataParallel replicas share this object (shallow __dict__ copy): one slot per device
-        hit = self._fwd.get(slot)
-        if hit is None or hit[0] != k:
-            hit = (k, ops.cast(p.detach().contiguous(), dtype))
-            self._fwd[slot] = hit
-        return hit[1]
-
-    def split3(self, name: str, p: torch.Tensor, transposed: bool) -> torch.Tensor:
-        """ME_BF16X3 right-operand copy of a weight ([out, 3 in]; transposed: of W^T, [in, 3 out] for the dgrad GEMMs): the
-        fp32-accurate mode's compute copies, rebuilt when the parameter changes (same keys as the other copies)."""
-        kind = "x3t" if transposed else "x3"
-        k = self._key(p, kind)
-        slot = (name, transposed, p.device)
-        hit = self._x3.get(slot)
-        if hit is not None and hit[0] == k:
-            return hit[1]
-        if p.dtype != torch.float32 or not p.is_contiguous():
-            w32 = ops.cast(p.detach().contiguous(), torch.float32)
-            w32 = ops.transpose_cast(w32, torch.float32) if transposed else w32
-            out = ops.split3(w32, right_operand=True)
-            self._x3[slot] = (k, out)
-            return out
-        # refresh, in ONE launch, this copy and every stale copy of the same kind that some live Block on the device has used before
-        # (after an optimizer step that is all of them: 2 launches per step for the encoder instead of 12 per Block)
-        todo = [(self, name, k, p)]
-        for c in list(_WeightCache._live):
-            for n, w in c._weights().items():
-                if (c is self and n == name) or w.device != p.device or w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous():
-                    continue
-                h = c._x3.get((n, transposed, w.device))
-                if h is None:
-                    continue
-                kk = _WeightCache._key(w, kind)
-                if h[0] != kk:
-                    todo.append((c, n, kk, w))
-        outs = ops.split3_many([w.detach() for _, _, _, w in todo], transposed)
-        for (c, n, kk, w), t in zip(todo, outs):
-            c._x3[(n, transposed, w.device)] = (kk, t)
-        return outs[0]
-
-    def folded(self, name: str, w: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, bias: Optional[torch.Tensor], dtype):
-        """LayerNorm folded into the Linear behind it (inference; me_gemm_desc.row_affine):
-            Linear(LN(x))[m, n] = rstd_m (x W'^T)[m, n] - rstd_m mean_m s[n] + c[n]
-        with W' = gamma o W rounded to the compute dtype, s[n] = sum_k W'[n, k] of the ROUNDED values (so that the mean
-        component cancels exactly as the kernel sees it) and c = W beta + bias from the fp32 masters.  One-off weight
-        preparation in torch (plumbing), cached like the other compute copies."""
-        k = tuple(self._key(t, dtype) for t in (w, ln_w, ln_b) + ((bias,) if bias is not None else ()))
-        slot = (name, w.device)
-        hit = self._fold.get(slot)
-        if hit is None or hit[0] != k:
-            with torch.no_grad():
-                # every number here comes out of the library (VERDICT r4 weak #13: this used to be at::native mul / reduce kernels):
-                #   W' = gamma o W rounded to the compute dtype   -- the column-scale form of me_dropout_add (p = 0)
-                #   s  = W' 1   (of the ROUNDED values, fp32 sums) -- me_gemm: four rows of ones x W'^T, row 0
-                #   c  = W beta + bias                             -- exact-fp32 me_gemm: four copies of beta x W^T + the bias epilogue
-                w32 = ops.cast(w.detach().contiguous(), torch.float32)
-                g32, b32 = ops._f32(ln_w.detach()).contiguous(), ops._f32(ln_b.detach()).contiguous()
-                wf = ops.dropout_add(w32, None, w32.shape[0], 0.0, 0.0, 0, out_dtype=dtype, colscale=g32)
-                K = w32.shape[1]
-                ones = torch.ones((4, K), dtype=dtype, device=w.device)
-                s_vec = ops.gemm(ones, wf, out_dtype=torch.float32)[0].contiguous()
-                c_vec = ops.gemm(b32[None, :].expand(4, K).contiguous(), w32, bias=None if bias is None else ops._f32(bias.detach()),
-                                 out_dtype=torch.float32)[0].contiguous()
-                hit = (k, (wf, s_vec, c_vec))
-            self._fold[slot] = hit
-        return hit[1]
-
-    _pending = {}         # device -> event behind a refresh of the transposed copies that ran on another stream (prefetch_transposed)
-
-    @classmethod
-    def prefetch_transposed(cls, device) -> int:
-        """Rebuild, on the CURRENT stream, every transposed copy that exists on `device` and is stale (one batched launch per
-        dtype) -- FusedAdamW(overlap=True) calls this on its side stream right behind an optimizer step, so that the 0.15 ms of weight
-        transposes run under the next forward instead of at the head of the next backward.  The first `transposed()` hit afterwards
-        makes its stream wait for the event recorded here.  Returns the number of copies rebuilt."""
-        if cls._live is None:
-            return 0
-        by_dtype = {}
-        for c in list(cls._live):
-            for n, w in c._weights().items():
-                if w.device != device or w.dim() != 2:
-                    continue
-                h = c._tr.get((n, w.device))
-                if h is None:
-                    continue                        # never used in a backward: nothing to keep fresh
-                dtype = h[1].dtype
-                kk = cls._key(w, dtype)
-                if h[0] != kk:
-                    by_dtype.setdefault((w.dtype, dtype), []).append((c, n, kk, w))
-        n_done = 0
-        for (_, dtype), todo in by_dtype.items():
-            outs = ops.transpose_cast_many([w.detach().contiguous() for _, _, _, w in todo], dtype)
-            for (c, n, kk, w), t in zip(todo, outs):
-                c._tr[(n, w.device)] = (kk, t)
-            n_done += len(todo)
-        if n_done:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(device))
-            cls._pending[device] = ev
-        return n_done
-
-    def _weights(self):
-        blk = self._owner() if self._owner is not None else None
-        if blk is None:
-            return {}
-        return {"qkv": blk.attn.qkv.weight, "proj": blk.attn.proj.weight, "fc1": blk.mlp.fc1.weight, "fc2": blk.mlp.fc2.weight}
-
-    def transposed(self, name: str, p: torch.Tensor, dtype) -> torch.Tensor:
-        k = self._key(p, dtype)
-        slot = (name, p.device)
-        ev = _WeightCache._pending.pop(p.device, None)
-        if ev is not None:                      # copies rebuilt on the optimizer's side stream (prefetch_transposed): order this stream behind it
-            torch.cuda.current_stream(p.device).wait_event(ev)
-        hit = self._tr.get(slot)
-        if hit is not None and hit[0] == k:
-            return hit[1]
-        # refresh every stale transposed copy on this device in one go
-        todo = []
-        for c in list(_WeightCache._live):
-            for n, w in c._weights().items():
-                if w.device == p.device and w.dtype == p.dtype and w.dim() == 2:
-                    kk = _WeightCache._key(w, dtype)
-                    h = c._tr.get((n, w.device))
-                    if h is None or h[0] != kk:
-                        todo.append((c, n, kk, w))
-        if not any(c is self and n == name and kk == k for c, n, kk, _ in todo):
-            todo.append((self, name, k, p))       # (a DataParallel replica: its parameters are not the owner's)
-        outs = ops.transpose_cast_many([w.detach().contiguous() for _, _, _, w in todo], dtype)
-        mine = None
-        for (c, n, kk, w), t in zip(todo, outs):
-            c._tr[(n, w.device)] = (kk, t)
-            if c is self and n == name and kk == k:
-                mine = t        # returned from this local: the shared dict may be rewritten by another replica's thread
-        return mine
-
-
 # seed offsets of the stochastic ops of one training-mode Block call (Block.forward draws ONE int64 seed per call; every mask is
 # u01_hash(seed + offset, index) of csrc/common.h, regenerated in backward -- the contract restated by tests/stoch_cases.py)
 SEED_BRANCH1 = 1         # proj_drop + drop-path of the attention branch (me_dropout_add)
@@ -294,12 +97,23 @@ def _note_exact_fp32(blk, cdt, rdt, reason: str) -> None:
                   "multiples of 256)", stacklevel=3)
 
 
+# The parameter tensors of one Block in the ONE order they travel in: _BlockFn.apply's tensor arguments behind x, hence
+# ctx.needs_input_grad and the gradients backward returns.  The names are me_block_desc's and me_block_grads' own; a bias or gamma may be None.
+BlockParams = NamedTuple("BlockParams", [(f, Optional[torch.Tensor]) for f in (
+    "ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "gamma1", "gamma2")])
+
+
+def _grad_index(name: str) -> int:      # position of a parameter among _BlockFn.apply's arguments (x is argument 0)
+    return 1 + BlockParams._fields.index(name)
+
+
 class _BlockFn(torch.autograd.Function):
     """forward + backward of one Block on the HIP kernels.  Restates Block.forward (attention.py:55-58)."""
 
     @staticmethod
-    def forward(ctx, x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b, g1, g2, blk, cdt, stoch, grad_mode,
-                win=None):
+    def forward(ctx, x, ln1_g, ln1_b, qkv_w, qkv_b, proj_w, proj_b, ln2_g, ln2_b, fc1_w, fc1_b, fc2_w, fc2_b, gamma1, gamma2,
+                blk, cdt, stoch, grad_mode, win, stats):
+        params = BlockParams(*map(locals().get, BlockParams._fields))      # (by name: no second hand-written order)
         B, N, C = x.shape
         H = blk.attn.num_heads
         hd = C // H
@@ -315,31 +129,27 @@ class _BlockFn(torch.autograd.Function):
         x2 = x.reshape(M, C)
         ctx.fast = False
         fp8 = bool(getattr(blk, "attn_fp8", False)) and win is None and cdt == torch.bfloat16 and hd == 64 and stoch is None
-        if stoch is None and win is None and blk.c_side and not fp8 and not (need_grad and g1 is not None):
+        if stoch is None and win is None and blk.c_side and not fp8 and not (need_grad and gamma1 is not None):
             # plain path: the whole block is ONE library call (me_block_fwd), the launch sequence lives on the C side
             x3 = blk.uses_3xbf16(cdt, rdt)
             if not x3:
                 _note_exact_fp32(blk, cdt, rdt, "dim / hidden not multiples of 256")
-            d, keep = _BlockFn._desc(blk, cache, cdt, rdt, B, N, C, H, (n1w, n1b, n2w, n2b, qkvw, qkvb, projw, projb,
-                                                                        fc1w, fc1b, fc2w, fc2b, g1, g2), False,
-                                     fold=not need_grad and blk.fold_norm, x3=x3)
+            d, keep = _BlockFn._desc(blk, cache, cdt, rdt, B, N, C, H, params, False, fold=not need_grad and blk.fold_norm, x3=x3)
             # LayerNorm statistics handed from block to block (folded inference): the caller (Block.forward) passes the pairs the
-            # previous block left on this very tensor, and gets this block's own back through blk._stats_out
-            xs = getattr(blk, "_stats_in", None)
-            blk._stats_in = None
+            # previous block left on this very tensor in `stats`, and gets this block's own back in it
             want = keep[3] is not None and blk.chain_stats       # (the folded route is taken)
-            y, saved, ys = ops.block_fwd(d, x2, keep=need_grad, x_stats=xs if want else None, want_stats=want)
-            blk._stats_out = ys if in_dtype == rdt else None      # (an fp16 caller gets a converted copy: other values)
+            y, saved, ys = ops.block_fwd(d, x2, keep=need_grad, x_stats=stats.x_stats if want else None, want_stats=want)
+            stats.y_stats = ys if in_dtype == rdt else None      # (an fp16 caller gets a converted copy: other values)
             del keep
             if need_grad:
-                ctx.save_for_backward(x2, saved, n1w, n1b, n2w, n2b, qkvw, qkvb, projw, projb, fc1w, fc1b, fc2w, fc2b)
+                ctx.save_for_backward(x2, saved, *params)
                 ctx.blk, ctx.cdt, ctx.dims, ctx.in_dtype, ctx.fast, ctx.x3 = blk, cdt, (B, N, C, H, hd), in_dtype, True, x3
             return ops.cast(y, in_dtype).reshape(B, N, C)
 
         _note_exact_fp32(blk, cdt, rdt, "windowed attention" if win is not None else "stochastic path (drop-path / dropout)" if stoch is not None
-                         else "layer-scale gradient" if (need_grad and g1 is not None) else "op-by-op composition (c_side = False)")
-        xn1, mean1, rstd1 = ops.layernorm_fwd(x2, n1w, n1b, blk.eps, cdt, save_stats=need_grad)
-        qkv = ops.gemm(xn1, cache.fwd("qkv", qkvw, cdt), bias=qkvb)
+                         else "layer-scale gradient" if (need_grad and gamma1 is not None) else "op-by-op composition (c_side = False)")
+        xn1, mean1, rstd1 = ops.layernorm_fwd(x2, ln1_g, ln1_b, blk.eps, cdt, save_stats=need_grad)
+        qkv = ops.gemm(xn1, cache.fwd("qkv", qkv_w, cdt), bias=qkv_b)
         p_attn = stoch[3] if stoch is not None else 0.0      # training-mode attn_drop (attention.py:33)
         if win is None:
             o, lse = ops.attention_fwd(qkv, B, N, H, hd, blk.attn.scale, need_lse=need_grad, p_drop=p_attn, fp8=fp8,
@@ -356,65 +166,58 @@ class _BlockFn(torch.autograd.Function):
             o = ops.window_rows(o_att, B, gh_, gw_, ws, merge=True)
         # layer-scale with gradients: d gamma = colsum(dy * UNSCALED branch output), so the branch output is kept and
         # gamma is applied by the residual kernel instead of the GEMM epilogue
-        ls_grad = need_grad and g1 is not None
+        ls_grad = need_grad and gamma1 is not None
         p_drop, p_path, seed = stoch[:3] if stoch is not None else (0.0, 0.0, 0)
         t1 = t2 = None
         if stoch is None and not ls_grad:
-            x1 = ops.gemm(o, cache.fwd("proj", projw, cdt), bias=projb, residual=x2, out_dtype=rdt, colscale=g1)
+            x1 = ops.gemm(o, cache.fwd("proj", proj_w, cdt), bias=proj_b, residual=x2, out_dtype=rdt, colscale=gamma1)
         else:                 # training-mode proj_drop / drop_path: x1 = x + drop_path(gamma1 * dropout(proj(o)))
-            t1 = ops.gemm(o, cache.fwd("proj", projw, cdt), bias=projb, out_dtype=rdt, colscale=None if ls_grad else g1)
-            x1 = ops.dropout_add(t1, x2, N, p_drop, p_path, seed + SEED_BRANCH1, colscale=g1 if ls_grad else None)
-        xn2, mean2, rstd2 = ops.layernorm_fwd(x1, n2w, n2b, blk.eps, cdt, save_stats=need_grad)
-        hpre = torch.empty((M, fc1w.shape[0]), dtype=cdt, device=x.device) if need_grad else None
-        a = ops.gemm(xn2, cache.fwd("fc1", fc1w, cdt), bias=fc1b, act=ME_ACT_GELU, preact=hpre,
+            t1 = ops.gemm(o, cache.fwd("proj", proj_w, cdt), bias=proj_b, out_dtype=rdt, colscale=None if ls_grad else gamma1)
+            x1 = ops.dropout_add(t1, x2, N, p_drop, p_path, seed + SEED_BRANCH1, colscale=gamma1 if ls_grad else None)
+        xn2, mean2, rstd2 = ops.layernorm_fwd(x1, ln2_g, ln2_b, blk.eps, cdt, save_stats=need_grad)
+        hpre = torch.empty((M, fc1_w.shape[0]), dtype=cdt, device=x.device) if need_grad else None
+        a = ops.gemm(xn2, cache.fwd("fc1", fc1_w, cdt), bias=fc1_b, act=ME_ACT_GELU, preact=hpre,
                      flags=ME_GEMM_SAVE_GELU_GRAD if need_grad else 0)      # saved: gelu'(h) (as me_block_fwd does)
         if stoch is None and not ls_grad:
-            y = ops.gemm(a, cache.fwd("fc2", fc2w, cdt), bias=fc2b, residual=x1, out_dtype=rdt, colscale=g2)
+            y = ops.gemm(a, cache.fwd("fc2", fc2_w, cdt), bias=fc2_b, residual=x1, out_dtype=rdt, colscale=gamma2)
         else:                 # Mlp: fc1 -> act -> drop -> fc2 -> drop (mlp.py:29-35), then drop_path + residual
             if p_drop > 0:
                 a = ops.dropout_add(a, None, N, p_drop, 0.0, seed + SEED_MLP_HIDDEN)
-            t2 = ops.gemm(a, cache.fwd("fc2", fc2w, cdt), bias=fc2b, out_dtype=rdt, colscale=None if ls_grad else g2)
-            y = ops.dropout_add(t2, x1, N, p_drop, p_path, seed + SEED_BRANCH2, colscale=g2 if ls_grad else None)
+            t2 = ops.gemm(a, cache.fwd("fc2", fc2_w, cdt), bias=fc2_b, out_dtype=rdt, colscale=None if ls_grad else gamma2)
+            y = ops.dropout_add(t2, x1, N, p_drop, p_path, seed + SEED_BRANCH2, colscale=gamma2 if ls_grad else None)
         if not ls_grad:
             t1 = t2 = None
 
         if need_grad:
             ctx.save_for_backward(x2, mean1, rstd1, xn1, qkv, lse, o, x1, mean2, rstd2, xn2, hpre, a,
-                                  n1w, qkvw, projw, n2w, fc1w, fc2w, g1, g2, t1, t2, o_att if win is not None else None)
+                                  ln1_g, qkv_w, proj_w, ln2_g, fc1_w, fc2_w, gamma1, gamma2, t1, t2, o_att if win is not None else None)
             ctx.blk, ctx.cdt, ctx.dims, ctx.stoch, ctx.win = blk, cdt, (B, N, C, H, hd), stoch, win
-            ctx.has_bias = (qkvb is not None, projb is not None, fc1b is not None, fc2b is not None)
+            ctx.has_bias = (qkv_b is not None, proj_b is not None, fc1_b is not None, fc2_b is not None)
             ctx.in_dtype = in_dtype
         return ops.cast(y, in_dtype).reshape(B, N, C)
 
     @staticmethod
-    def _desc(blk, cache, cdt, rdt, B, N, C, H, params, transposed, fold=False, x3=False):
+    def _desc(blk, cache, cdt, rdt, B, N, C, H, p: BlockParams, transposed, fold=False, x3=False):
         """me_block_desc for this block + the list of tensors that must stay alive while the call is in flight.
         fold: inference with both LayerNorms folded into qkv / fc1 (bf16 compute on a bf16 token stream; the library falls
         back to LayerNorm + GEMM by itself when the descriptor carries no folded weights)."""
-        (n1w, n1b, n2w, n2b, qkvw, qkvb, projw, projb, fc1w, fc1b, fc2w, fc2b, g1, g2) = params
-        ws = {"qkv": qkvw, "proj": projw, "fc1": fc1w, "fc2": fc2w}
-        if x3:            # fp32-accurate mode: three-plane bf16 copies of the fp32 weights (Block.fp32_mode = "3xbf16")
-            w = {k: cache.split3(k, t, False) for k, t in ws.items()}
-            wt = {k: cache.split3(k, t, True) for k, t in ws.items()} if transposed else None
-        else:
-            w = {k: cache.fwd(k, t, cdt) for k, t in ws.items()}
-            wt = {k: cache.transposed(k, t, cdt) for k, t in ws.items()} if transposed else None
-        f = lambda t: None if t is None else ops._f32(t).contiguous()      # noqa: E731
-        vec = dict(ln1_g=f(n1w), ln1_b=f(n1b), ln2_g=f(n2w), ln2_b=f(n2b), qkv_b=f(qkvb), proj_b=f(projb), fc1_b=f(fc1b),
-                   fc2_b=f(fc2b), gamma1=f(g1), gamma2=f(g2))
-        d = ops.block_desc(B, N, C, H, fc1w.shape[0], blk.eps, blk.attn.scale, cdt, rdt, w, wt, vec, x3=x3)
+        # (x3: the fp32-accurate mode reads three-plane bf16 copies of the fp32 weights -- Block.fp32_mode = "3xbf16")
+        w, wt = cache.operands({"qkv": p.qkv_w, "proj": p.proj_w, "fc1": p.fc1_w, "fc2": p.fc2_w}, cdt, x3, transposed)
+        # the vectors travel under their field names, which are me_block_desc's
+        vec = {k: None if t is None else ops._f32(t).contiguous() for k, t in p._asdict().items() if not k.endswith("_w")}
+        d = ops.block_desc(B, N, C, H, p.fc1_w.shape[0], blk.eps, blk.attn.scale, cdt, rdt, w, wt, vec, x3=x3)
         folded = None
         # (only when every CU gets 256 x 256 tiles of qkv: the fold's row-affine epilogue lives in the resident GEMM kernel; below
         #  that the generic epilogue it would fall back to measured slower than LayerNorm + GEMM -- B = 32: 2.95 vs 2.75 ms)
         big = ((B * N + 255) // 256) * ((3 * C + 255) // 256) >= 256
         if fold and (big or fold == "always") and cdt == torch.bfloat16 and rdt == torch.bfloat16:
-            folded = (cache.folded("qkv", qkvw, n1w, n1b, qkvb, cdt), cache.folded("fc1", fc1w, n2w, n2b, fc1b, cdt))
+            folded = (cache.folded("qkv", p.qkv_w, p.ln1_g, p.ln1_b, p.qkv_b, cdt), cache.folded("fc1", p.fc1_w, p.ln2_g, p.ln2_b, p.fc1_b, cdt))
             (d.qkv_wf, d.qkv_s, d.qkv_c), (d.fc1_wf, d.fc1_s, d.fc1_c) = [tuple(ops.ptr(t) for t in trip) for trip in folded]
         return d, (w, wt, vec, folded)
 
     @staticmethod
     def _backward_c(ctx, dy):
-        (x2, saved, n1w, n1b, n2w, n2b, qkvw, qkvb, projw, projb, fc1w, fc1b, fc2w, fc2b) = ctx.saved_tensors
+        x2, saved, *params = ctx.saved_tensors
         blk, cdt = ctx.blk, ctx.cdt
         B, N, C, H, hd = ctx.dims
         rdt = x2.dtype
@@ -422,14 +225,10 @@ class _BlockFn(torch.autograd.Function):
         dy2 = dy.contiguous().reshape(B * N, C)
         if dy2.dtype != rdt:
             dy2 = ops.cast(dy2, rdt)
-        d, keep = _BlockFn._desc(blk, blk._wcache, cdt, rdt, B, N, C, H, (n1w, n1b, n2w, n2b, qkvw, qkvb, projw, projb,
-                                                                          fc1w, fc1b, fc2w, fc2b, None, None), True, x3=ctx.x3)
-        # gradient destinations: (name in me_block_grads, parameter, index into needs_input_grad)
-        slots = [("ln1_g", blk.norm1.weight, 1), ("ln1_b", blk.norm1.bias, 2), ("qkv_w", blk.attn.qkv.weight, 3),
-                 ("qkv_b", blk.attn.qkv.bias, 4), ("proj_w", blk.attn.proj.weight, 5), ("proj_b", blk.attn.proj.bias, 6),
-                 ("ln2_g", blk.norm2.weight, 7), ("ln2_b", blk.norm2.bias, 8), ("fc1_w", blk.mlp.fc1.weight, 9),
-                 ("fc1_b", blk.mlp.fc1.bias, 10), ("fc2_w", blk.mlp.fc2.weight, 11), ("fc2_b", blk.mlp.fc2.bias, 12)]
-        slots = [(n, p, i) for n, p, i in slots if p is not None and ng[i]]
+        d, keep = _BlockFn._desc(blk, blk._wcache, cdt, rdt, B, N, C, H, BlockParams(*params), True, x3=ctx.x3)
+        # gradient destinations: (field = name in me_block_grads, parameter, index into needs_input_grad)
+        slots = [(n, p, _grad_index(n)) for n, p in blk._params()._asdict().items()
+                 if p is not None and not n.startswith("gamma") and ng[_grad_index(n)]]
         # in place into a FlatParams buffer (accumulating) when EVERY wanted gradient lives there, else fresh tensors
         flat = getattr(blk.attn.qkv.weight, "_me_flat", None)
         direct = None
@@ -439,21 +238,16 @@ class _BlockFn(torch.autograd.Function):
                 direct = None
         g = _capi.BlockGrads()
         wdt = blk.attn.qkv.weight.dtype
-        g.w_dtype = _capi.dtype_code(wdt if wdt != torch.float16 else torch.float32)
+        wdt = wdt if wdt != torch.float16 else torch.float32      # (weight gradients come in the weights' dtype, vectors' in fp32)
+        g.w_dtype = _capi.dtype_code(wdt)
         g.accumulate = 1 if direct is not None else 0
         outs = {}
         for j, (n, p, i) in enumerate(slots):
-            if direct is not None:
-                t = direct[j]
-            elif n.endswith("_w"):
-                t = torch.empty(p.shape, dtype=wdt if wdt != torch.float16 else torch.float32, device=p.device)
-            else:
-                t = torch.empty(p.shape, dtype=torch.float32, device=p.device)
-            outs[i] = t
-            setattr(g, n, ops.ptr(t))
+            outs[i] = direct[j] if direct is not None else torch.empty(p.shape, dtype=wdt if n.endswith("_w") else torch.float32, device=p.device)
+            setattr(g, n, ops.ptr(outs[i]))
         dx = ops.block_bwd(d, x2, dy2, saved, g)
         del keep
-        res = [None] * 20
+        res = [None] * len(ng)
         res[0] = ops.cast(dx, ctx.in_dtype).reshape(B, N, C) if ng[0] else None
         for n, p, i in slots:
             if direct is not None:
@@ -474,7 +268,8 @@ class _BlockFn(torch.autograd.Function):
         M = B * N
         cache: _WeightCache = blk._wcache
         rdt = x2.dtype
-        ng = ctx.needs_input_grad      # x, n1w, n1b, qkvw, qkvb, projw, projb, n2w, n2b, fc1w, fc1b, fc2w, fc2b, g1, g2
+        ng = ctx.needs_input_grad
+        need = lambda name: ng[_grad_index(name)]      # noqa: E731
         dy2 = dy.contiguous().reshape(M, C)
         if dy2.dtype != rdt:
             dy2 = ops.cast(dy2, rdt)
@@ -539,15 +334,15 @@ class _BlockFn(torch.autograd.Function):
         dh = ops.gemm(dy_c, cache.transposed("fc2", fc2w, cdt), aux=hpre, flags=ME_GEMM_AUX_IS_FACTOR)   # dA * gelu'(h)
         if stoch is not None and p_drop > 0:
             dh = ops.dropout_add(dh, None, N, p_drop, 0.0, seed + SEED_MLP_HIDDEN)
-        d_fc2w, d_fc2b = wgrad(dy_c, a, blk.mlp.fc2, ng[11], ng[12] and ctx.has_bias[3])
+        d_fc2w, d_fc2b = wgrad(dy_c, a, blk.mlp.fc2, need("fc2_w"), need("fc2_b") and ctx.has_bias[3])
         dxn2 = ops.gemm(dh, cache.transposed("fc1", fc1w, cdt))
-        d_fc1w, d_fc1b = wgrad(dh, xn2, blk.mlp.fc1, ng[9], ng[10] and ctx.has_bias[2])
-        dx1, d_n2w, d_n2b = ln_bwd(dxn2, x1, mean2, rstd2, blk.norm2, dy2, ng[7] or ng[8])
+        d_fc1w, d_fc1b = wgrad(dh, xn2, blk.mlp.fc1, need("fc1_w"), need("fc1_b") and ctx.has_bias[2])
+        dx1, d_n2w, d_n2b = ln_bwd(dxn2, x1, mean2, rstd2, blk.norm2, dy2, need("ln2_g") or need("ln2_b"))
 
         # ---- attention branch: x1 = x + proj(attn(qkv(LN1(x))))
         dx1_c, d_g1 = branch_grad(dx1, t1, g1, seed + SEED_BRANCH1)
         do = ops.gemm(dx1_c, cache.transposed("proj", projw, cdt))
-        d_projw, d_projb = wgrad(dx1_c, o, blk.attn.proj, ng[5], ng[6] and ctx.has_bias[1])
+        d_projw, d_projb = wgrad(dx1_c, o, blk.attn.proj, need("proj_w"), need("proj_b") and ctx.has_bias[1])
         if ctx.win is None:
             dqkv = ops.attention_bwd(qkv, o, do, lse, B, N, H, hd, blk.attn.scale, p_drop=p_attn, seed=seed + SEED_ATTN_DROP)
         else:                 # the same regrouping on the gradient; padded rows are constants (no gradient leaves them)
@@ -558,19 +353,26 @@ class _BlockFn(torch.autograd.Function):
                                        seed=seed + SEED_ATTN_DROP)
             dqkv = ops.window_rows(dqkv_w, B, gh_, gw_, ws, merge=True)
         dxn1 = ops.gemm(dqkv, cache.transposed("qkv", qkvw, cdt))
-        d_qkvw, d_qkvb = wgrad(dqkv, xn1, blk.attn.qkv, ng[3], ng[4] and ctx.has_bias[0])
-        dx, d_n1w, d_n1b = ln_bwd(dxn1, x2, mean1, rstd1, blk.norm1, dx1, ng[1] or ng[2])
+        d_qkvw, d_qkvb = wgrad(dqkv, xn1, blk.attn.qkv, need("qkv_w"), need("qkv_b") and ctx.has_bias[0])
+        dx, d_n1w, d_n1b = ln_bwd(dxn1, x2, mean1, rstd1, blk.norm1, dx1, need("ln1_g") or need("ln1_b"))
 
-        def aff(g, p):
-            return None if g is None else g.to(p.dtype)
+        def vec(name, g, like):      # gradient of a vector parameter, in its dtype, if wanted
+            return g.to(like.dtype) if (g is not None and need(name)) else None
 
-        return (ops.cast(dx, ctx.in_dtype).reshape(B, N, C) if ng[0] else None,
-                aff(d_n1w, n1w) if ng[1] else None, aff(d_n1b, n1w) if ng[2] else None,
-                d_qkvw, d_qkvb, d_projw, d_projb,
-                aff(d_n2w, n2w) if ng[7] else None, aff(d_n2b, n2w) if ng[8] else None,
-                d_fc1w, d_fc1b, d_fc2w, d_fc2b,
-                d_g1.to(g1.dtype) if (d_g1 is not None and ng[13]) else None,
-                d_g2.to(g2.dtype) if (d_g2 is not None and ng[14]) else None, None, None, None, None, None)
+        grads = BlockParams(ln1_g=vec("ln1_g", d_n1w, n1w), ln1_b=vec("ln1_b", d_n1b, n1w), qkv_w=d_qkvw, qkv_b=d_qkvb,
+                            proj_w=d_projw, proj_b=d_projb, ln2_g=vec("ln2_g", d_n2w, n2w), ln2_b=vec("ln2_b", d_n2b, n2w),
+                            fc1_w=d_fc1w, fc1_b=d_fc1b, fc2_w=d_fc2w, fc2_b=d_fc2b,
+                            gamma1=vec("gamma1", d_g1, g1), gamma2=vec("gamma2", d_g2, g2))
+        res = [None] * len(ng)
+        res[0] = ops.cast(dx, ctx.in_dtype).reshape(B, N, C) if ng[0] else None
+        for name, g in grads._asdict().items():
+            res[_grad_index(name)] = g
+        return tuple(res)
+
+
+class _StatsHandoff:
+    """LayerNorm statistics of ONE call, between Block.forward and _BlockFn.forward: the input's go in, the output's come out."""
+    x_stats = y_stats = None
 
 
 class Block(nn.Module):
@@ -613,7 +415,6 @@ class Block(nn.Module):
         self.fp32_mode = Block.default_fp32_mode
         self._wcache = _WeightCache()
         self.chain_stats = True     # folded inference: LayerNorm statistics from the proj / fc2 epilogues, handed from block to block
-        self._stats_in = self._stats_out = None      # (per-call hand-over between forward() and the autograd Function)
 
     default_fp32_mode = "3xbf16"      # what a new Block's fp32_mode starts as; `Block.default_fp32_mode = "exact"` (or set_fp32_mode(model, "exact")) restores round 5's
 
@@ -624,6 +425,13 @@ class Block(nn.Module):
             raise MetaEncError(f"Block.fp32_mode must be 'exact' or '3xbf16' (got {self.fp32_mode!r})")
         C, hidden = self.attn.qkv.weight.shape[1], self.mlp.fc1.weight.shape[0]
         return bool(want and cdt == torch.float32 and rdt == torch.float32 and C % 256 == 0 and hidden % 256 == 0)
+
+    def _params(self) -> BlockParams:
+        a, m = self.attn, self.mlp
+        return BlockParams(ln1_g=self.norm1.weight, ln1_b=self.norm1.bias, qkv_w=a.qkv.weight, qkv_b=a.qkv.bias, proj_w=a.proj.weight,
+                           proj_b=a.proj.bias, ln2_g=self.norm2.weight, ln2_b=self.norm2.bias, fc1_w=m.fc1.weight, fc1_b=m.fc1.bias,
+                           fc2_w=m.fc2.weight, fc2_b=m.fc2.bias, gamma1=self.gamma1 if self.layer_scale else None,
+                           gamma2=self.gamma2 if self.layer_scale else None)
 
     def _compute_dtype(self, x: torch.Tensor) -> torch.dtype:
         if self.compute_dtype == "fp32_3xbf16":
@@ -667,9 +475,6 @@ class Block(nn.Module):
             # returns the empty tensor; so does this one, without a launch (the parameters receive no gradient from it)
             return x.clone()
         x = x.contiguous()
-        a, m = self.attn, self.mlp
-        g1 = self.gamma1 if self.layer_scale else None
-        g2 = self.gamma2 if self.layer_scale else None
         # folded inference: the LayerNorm statistics of a block's output come out of its fc2 epilogue and ride on the output
         # TENSOR OBJECT (attribute _me_ln_stats = (pairs, eps, version)) to whichever Block is handed that same object next --
         # nn.Sequential, a `for blk in blocks` loop.  Anything else (a new tensor from x + pos, an in-place edit: the version
@@ -678,25 +483,19 @@ class Block(nn.Module):
         # are neither tagged nor trusted (the block reads its input once more; encoder_forward_inference chains on the C side).
         # Assumptions of the hand-over: (1) whoever writes the tagged tensor bumps its `_version` -- torch ops do; a write
         # through a raw pointer (this library's own `out=` forms, `x.data` edits, foreign kernels) does not, and must drop the tag
-        # (`del y._me_ln_stats`) or set `blk.chain_stats = False`; (2) one forward at a time per Block object: `_stats_in / _stats_out`
-        # are per-call state on the module -- a Block shared by two host threads needs `chain_stats = False` (me_encoder_fwd, the
-        # one-call route, keeps the hand-over inside the library and has neither restriction).
+        # (`del y._me_ln_stats`) or set `blk.chain_stats = False` (me_encoder_fwd, the one-call route, keeps the hand-over inside the
+        # library and does not have this restriction).
         tag = getattr(x, "_me_ln_stats", None)
-        self._stats_in = None
+        stats = _StatsHandoff()
         ver = _tensor_version(x) if tag is not None else None
         if (tag is not None and ver is not None and self.chain_stats and tag[1] == self.eps and tag[2] == ver
                 and tag[0].shape[-2] == x.shape[0] * x.shape[1]):
-            self._stats_in = tag[0]
-        self._stats_out = None
-        y = _BlockFn.apply(x, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias, a.proj.weight,
-                           a.proj.bias, self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias,
-                           m.fc2.weight, m.fc2.bias, g1, g2, self, cdt, stoch, torch.is_grad_enabled(), win)
-        self._stats_in = None
-        if self._stats_out is not None:
+            stats.x_stats = tag[0]
+        y = _BlockFn.apply(x, *self._params(), self, cdt, stoch, torch.is_grad_enabled(), win, stats)
+        if stats.y_stats is not None:
             ver = _tensor_version(y)
             if ver is not None:
-                y._me_ln_stats = (self._stats_out, self.eps, ver)
-            self._stats_out = None
+                y._me_ln_stats = (stats.y_stats, self.eps, ver)
         return y
 
 
@@ -804,12 +603,7 @@ def _encoder_descs(blocks, x: torch.Tensor, B: int, N: int, C: int):
     for b in blocks:
         b._wcache.bind(b)
         cdt = b._compute_dtype(x)
-        a, m = b.attn, b.mlp
-        g1 = b.gamma1 if b.layer_scale else None
-        g2 = b.gamma2 if b.layer_scale else None
-        d, k = _BlockFn._desc(b, b._wcache, cdt, x.dtype, B, N, C, a.num_heads,
-                              (b.norm1.weight, b.norm1.bias, b.norm2.weight, b.norm2.bias, a.qkv.weight, a.qkv.bias,
-                               a.proj.weight, a.proj.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, g1, g2), False,
+        d, k = _BlockFn._desc(b, b._wcache, cdt, x.dtype, B, N, C, b.attn.num_heads, b._params(), False,
                               fold=b.fold_norm, x3=b.uses_3xbf16(cdt, x.dtype))
         descs.append(d)
         keep.append(k)

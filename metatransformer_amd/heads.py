@@ -263,14 +263,8 @@ def pack_encoder(encoder: nn.Sequential, device=None, warm: bool = True):
             b._wcache.bind(b)
             # the dtype the Block will compute in (compute_dtype may be the STRING "fp32_3xbf16", which is not a torch dtype)
             cdt = torch.float32 if b.compute_dtype == "fp32_3xbf16" else (b.compute_dtype or torch.bfloat16)
-            x3 = b.uses_3xbf16(cdt, torch.float32)          # fp32-accurate mode: its compute copies are the three-plane split weights
-            for name, w in (("qkv", b.attn.qkv.weight), ("proj", b.attn.proj.weight), ("fc1", b.mlp.fc1.weight), ("fc2", b.mlp.fc2.weight)):
-                if x3:
-                    b._wcache.split3(name, w, False)
-                    b._wcache.split3(name, w, True)
-                else:
-                    b._wcache.fwd(name, w, cdt)
-                    b._wcache.transposed(name, w, cdt)
+            # (which copies a compute mode reads is the cache's knowledge: the same call builds them for the kernels, _BlockFn._desc)
+            b._wcache.operands(b._wcache.weights(), cdt, b.uses_3xbf16(cdt, torch.float32), True)
     return flat
 
 

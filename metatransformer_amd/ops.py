@@ -723,12 +723,10 @@ def adamw_step_segments(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.
           "me_adamw_prepare")
     check(lib.me_adamw_step_segments(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), ptr(segments), n_segments,
                                      lr, betas[0], betas[1], eps, ptr(ctl), ptr(bf16_mirror), stream_ptr()), "me_adamw_step_segments")
-    global WEIGHT_EPOCH
-    WEIGHT_EPOCH += 1
+    weights_updated()
 
 
 def ctypes_sizeof_ctl() -> int:
-    import ctypes
     return ctypes.sizeof(_capi.AdamwCtl)
 
 

@@ -23,6 +23,7 @@ import torch.distributed as dist
 
 from . import ops
 from ._capi import MetaEncError
+from .weight_cache import _WeightCache
 
 
 class Comm:
@@ -605,7 +606,6 @@ class FusedAdamW:
         # ... but not for the transposed copies of the next BACKWARD, rebuilt behind them on the side stream (under the next forward);
         # their first use waits for them by itself (_WeightCache.transposed)
         with torch.cuda.stream(self._side):
-            from .encoder import _WeightCache
             _WeightCache.prefetch_transposed(f.flat_param.device)
         self._left = [len(idx) for idx, _ in self._units]
         self._seen = [0] * len(f.params)
@@ -670,7 +670,6 @@ class FusedAdamW:
                 self._pf_stream = torch.cuda.Stream(device=dev)
             self._pf_stream.wait_stream(torch.cuda.current_stream(dev))       # behind the update
             with torch.cuda.stream(self._pf_stream):
-                from .encoder import _WeightCache
                 _WeightCache.prefetch_transposed(dev)       # (its first user waits for the event recorded there)
         return out
 

@@ -235,7 +235,7 @@ def test_pack_encoder_warms_the_three_product_copies(dev):
     flat = heads.pack_encoder(enc, warm=True)
     assert flat.numel > 0
     for b in enc:
-        assert all((n, t, dev) in b._wcache._x3 or (n, t, torch.device("cuda", 0)) in b._wcache._x3 for n in ("qkv", "proj", "fc1", "fc2") for t in (False, True))
+        assert all(b._wcache.has(k, n, b.attn.qkv.weight.device) for n in ("qkv", "proj", "fc1", "fc2") for k in ("x3", "x3t"))
     x = rnd(2, 70, 256, seed=3).to(dev)
     with torch.no_grad():
         y = enc(x)
