@@ -209,8 +209,19 @@ typedef struct me_gemm_profile_rec {
     int32_t plan;      /* GEMM records: which kernel plan ran -- bits 0-3 the family (0 = exact-fp32 / generic 128 x 128 "g128", 2 = "g2b"
                         * 128 x 256 two workgroups per CU, 3 = "g2w" 256 x 256 K-step 32, 4 = "g3" 256 x 256 K-tile 64, resident when every
                         * CU gets a tile), bit 4 = a split-K tail / whole-problem split ran with a fold, bit 5 = the balanced static partition of a weight
-                        * gradient (me_gemm_reserve_cus), bits 8-15 = split-K parts (bit 5: the most a tile gets); else 0 */
+                        * gradient (me_gemm_reserve_cus), bits 8-15 = split-K parts (bit 5: the most a tile gets).
+                        * Attention records (ME_PROF_ATTN_FWD / _BWD): the kernel form, one of ME_ATTN_* below.  Other records: 0 */
 } me_gemm_profile_rec;
+/* me_gemm_profile_rec.plan of an attention record: which kernel family ran the call (csrc/attention.hip: attn_route) */
+enum { ME_ATTN_GENERIC = 1,    /* tiled 128-query x 64-key kernels: fp32, head_dim > 64, dropout, and whatever no other form takes */
+       ME_ATTN_TINY = 2,       /* N <= 64: one small workgroup per (batch, head), attention_tiny.hip (bf16 and fp32) */
+       ME_ATTN_RING16 = 3,     /* 64 < N <= 224: the sequence resident in LDS, 16 waves of 16 rows */
+       ME_ATTN_RESIDENT = 4,   /* up to N = 256: the sequence resident in LDS, 32 rows per wave (launch label "small") */
+       ME_ATTN_STREAM16 = 5,   /* head_dim 64, longer sequences: K / V streamed through the ring */
+       ME_ATTN_MID = 6,        /* 256 < N <= 512: one workgroup per (batch, head) */
+       ME_ATTN_CHUNK = 7,      /* N > 512: 256-row chunks */
+       ME_ATTN_X3 = 8,         /* me_attention_fwd_x3 / _bwd_x3 */
+       ME_ATTN_DKDV32 = 16     /* bit 4, on an ME_ATTN_STREAM16 backward record: dK / dV ran on the 32-key kernel */ };
 int me_gemm_profile_enable(int on);
 int me_gemm_profile_read(me_gemm_profile_rec* out, int max);
 
@@ -289,7 +300,7 @@ typedef struct me_block_desc {
                            * res_dtype must be ME_F32, every weight pointer is the ME_BF16X3 right-operand form of the fp32 matrix --
                            * [out, 3 * in], and [in, 3 * out] for the *_wt copies; the stash and scratch layouts are the library's own (the two [tokens,
                            * hidden] tensors of the MLP are ME_BF16X2 where the GEMMs that read them can wrap their A operand); attention runs as three-product bf16 MFMA too
-                           * (me_attention_fwd_x3 / _bwd_x3, ~1e-5) for head_dim 64 and N > 64, on the exact-fp32 kernels otherwise) */
+                           * (me_attention_fwd_x3 / _bwd_x3, ~1e-5) for head_dim 64 and N > 64 -- the rule is csrc/attention_host.h: attn_x3_takes -- on the exact-fp32 kernels otherwise) */
     int32_t res_dtype;    /* dtype of x, y, dx, dy */
     int32_t B, N, C, heads, hidden;
     float eps, scale;     /* LayerNorm eps; attention scale (head_dim^-0.5 unless qk_scale was given) */

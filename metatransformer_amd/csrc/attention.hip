@@ -13,16 +13,10 @@
 // per-lane scalar.  The reduction-index permutation the accumulator layout imposes on P is absorbed by reading
 // V^T with the same permutation (common.h: any assignment works if A and B agree).
 // fp32 runs the same code on the exact-fp32 MFMA (parity mode); bf16 is the performance mode.
-#include "common.h"
+#include "attention_host.h"
 #include <math.h>
 #include <stdlib.h>
-
-// attention_tiny.hip: N <= 64, one wave per (batch, head)
-bool attn_tiny_ok(int dtype, int64_t ld_qkv, int64_t ld_out, int B, int N, int H, int hd);
-int launch_attn_tiny_fwd(int dtype, const void* qkv, int64_t ld, void* out, int64_t ldo, float* lse, int B, int N, int H, int hd, float scale,
-                         hipStream_t stream);
-int launch_attn_tiny_bwd(int dtype, const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dout, int64_t lddo, const float* lse,
-                         float* delta, void* dqkv, int64_t lddq, int B, int N, int H, int hd, float scale, hipStream_t stream);
+#include <type_traits>
 
 namespace {
 
@@ -3020,266 +3014,213 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_dkdv_chunk_kernel(const b
         }
 }
 
-template <typename K> void set_smem(K kernel, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-int device_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    }
-    return n;
-}
 constexpr size_t LDS_PER_CU = 160 * 1024;
+template <int V> using Int = std::integral_constant<int, V>;
 
-template <int HD>
-int launch_fwd_small(const void* qkv, int64_t ld, void* out, int64_t ldo, float* lse, int B, int N, int H, int hd, float scale,
-                     hipStream_t stream) {
+// ---- the route: which kernel family takes a call, and the launch geometry that depends on more than (B, H).  The one place that
+// decides by SM_MINN / SM_MAXN / RS_MAXN / MD_MAXN / ST_BWD_MINN, the 31-bit offset guard, the stride alignments and the row-block
+// split; DESIGN 4.4 has the same conditions as a table.  No HIP calls.  Where the two directions differ the term says `backward`.
+AttnRoute attn_route(const AttnCall& c, bool backward) {
+    AttnRoute r = {};
+    const int N = c.N, E = c.dtype == ME_BF16 ? 8 : 4;
+    r.hd = c.hd <= 32 ? 32 : c.hd <= 64 ? 64 : 128;
+    const bool no_drop = c.p_drop == 0.f;
+    // very short sequences (the Tabular / Graph recipes): one wave per 16 tokens, attention_tiny.hip, bf16 and fp32.
+    // SM_MINN: at or below one 64-key tile the tiled kernels (more workgroups per CU) win over the resident ones.
+    // backward: dout and dqkv rows 16-byte aligned as well (the entry point only asks 4 elements of ld_dqkv)
+    if (no_drop && N <= SM_MINN && attn_tiny_ok(c) && (!backward || (c.lddo % E == 0 && c.lddq % E == 0))) {
+        r.form = ME_ATTN_TINY;
+        return r;
+    }
+    // every other special form: bf16, no dropout, head_dim <= 64.
+    // backward: all of them want ld_out % 8 (forward asks that of stream16 only, below; the entry point guarantees % 4)
+    const bool bf16_form = no_drop && c.dtype == ME_BF16 && c.hd <= 64 && (!backward || c.ldo % 8 == 0);
+    // ring16 / stream16 address rows with 31-bit byte offsets: of qkv, and of dout in backward
+    auto off31 = [N](int64_t ld) { return (int64_t)N * ld * 2 < (int64_t)0x7e000000; };
+    const bool offs_ok = off31(c.ld) && (!backward || off31(c.lddo));
+    if (bf16_form && N > SM_MINN && N <= SM_MAXN) {
+        if (N <= RS_MAXN && offs_ok) {
+            r.form = ME_ATTN_RING16;
+            r.ns = (N + 31) / 32;                 // 3 .. 7 (SM_MINN < N <= RS_MAXN)
+        } else {
+            r.form = ME_ATTN_RESIDENT;
+        }
+        return r;
+    }
+    // streaming form: row blocks of (at most) 14 x 16 rows, evened out over the sequence (queries; in the backward's second kernel, keys).
+    // (head_dim <= 32: half the MFMA work per key for the same softmax arithmetic -- the 32-row kernels below measured faster there.)
+    // Forward takes it from SM_MAXN + 1, backward from ST_BWD_MINN: up to MD_MAXN the mid backward kernel measured faster.
+    // backward: ld_dqkv % 8 as well
+    const int nblk = (N + 223) / 224;
+    if (bf16_form && c.hd > 32 && N >= (backward ? ST_BWD_MINN : SM_MAXN + 1) && offs_ok && (int64_t)c.B * c.H * nblk < (int64_t)0x7fffffff &&
+        c.ldo % 8 == 0 && (!backward || c.lddq % 8 == 0)) {
+        r.form = ME_ATTN_STREAM16;
+        r.nblk = nblk;
+        r.rows = ((N + nblk - 1) / nblk + 15) / 16 * 16;
+        // dK / dV: 32-key waves when the key blocks fill seven of them (see attn_bwd_dkdv_stream32_kernel)
+        const int rows32 = (r.rows + 31) / 32 * 32;
+        r.dkdv32 = backward && rows32 == 7 * 32;
+        r.krows = r.dkdv32 ? rows32 : r.rows;
+        return r;
+    }
+    // (the forward chunk arm used to test B <= 65535 as well: check_attn_args has rejected a larger B before any route is asked for)
+    if (bf16_form && N > SM_MAXN) {
+        r.form = N <= MD_MAXN ? ME_ATTN_MID : ME_ATTN_CHUNK;
+        return r;
+    }
+    r.form = ME_ATTN_GENERIC;
+    return r;
+}
+
+// ---- launches: one per form and direction
+// grid of a persistent kernel: one workgroup per item up to per_cu workgroups on every CU
+unsigned persistent_grid(int64_t items, int per_cu = 1) {
+    const int64_t slots = (int64_t)device_cus() * per_cu;
+    return (unsigned)(items < slots ? items : slots);
+}
+// f(Int<HD>) for the route's head width (MAXHD: the widest instantiation the form has), f(Int<NS>) for the ring's sub-tile count
+template <int MAXHD, typename F> int by_hd(const AttnRoute& r, F f) {
+    if (r.hd <= 32) return f(Int<32>());
+    if constexpr (MAXHD <= 64) return f(Int<64>());
+    else return r.hd <= 64 ? f(Int<64>()) : f(Int<128>());
+}
+template <typename F> int by_ns(const AttnRoute& r, F f) {
+    switch (r.ns) {
+        case 3: return f(Int<3>());
+        case 4: return f(Int<4>());
+        case 5: return f(Int<5>());
+        case 6: return f(Int<6>());
+        default: return f(Int<7>());
+    }
+}
+
+template <int HD> int launch_fwd_small(const AttnCall& c) {
     typedef Cfg<bf16_t, HD> C;
-    const size_t smem = (size_t)(2 * ((N + 31) / 32 * 32) + SM_THREADS / 2) * C::RROW;      // {K, V} + per-wave [32][HD] scratch
-    static OncePerDevice once;
-    if (once.need()) { set_smem(attn_fwd_small_kernel<HD>, (size_t)(2 * SM_MAXN + SM_THREADS / 2) * C::RROW); }
-    const int64_t items = (int64_t)B * H;
+    const auto p = c.as<bf16_t>();
+    const size_t smem = (size_t)(2 * ((c.N + 31) / 32 * 32) + SM_THREADS / 2) * C::RROW;      // {K, V} + per-wave [32][HD] scratch
+    const int64_t items = (int64_t)c.B * c.H;
     int per_cu = (int)(LDS_PER_CU / smem);
     per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    const int64_t slots = (int64_t)device_cus() * per_cu;
-    const unsigned grid = (unsigned)(items < slots ? items : slots);
-    hipLaunchKernelGGL((attn_fwd_small_kernel<HD>), dim3(grid), dim3(SM_THREADS), smem, stream,
-                       reinterpret_cast<const bf16_t*>(qkv), ld, reinterpret_cast<bf16_t*>(out), ldo, lse, N, H, hd, scale,
-                       (int)items);
-    ME_CHECK_LAUNCH("me_attention_fwd(small)");
-    return ME_OK;
+    return attn_launch<attn_fwd_small_kernel<HD>>("me_attention_fwd(small)", dim3(persistent_grid(items, per_cu)), SM_THREADS, smem,
+                                                  (size_t)(2 * SM_MAXN + SM_THREADS / 2) * C::RROW, c.stream, p.qkv, c.ld, p.out, c.ldo, c.lse, c.N, c.H,
+                                                  c.hd, c.scale, (int)items);
 }
-template <int HD, int NS>
-int launch_fwd_ring16_ns(const void* qkv, int64_t ld, void* out, int64_t ldo, float* lse, int B, int N, int H, int hd, float scale,
-                         hipStream_t stream) {
-    typedef RCfg<HD> R;
-    constexpr size_t smem = (size_t)4 * NS * 32 * R::RB + (R16_THREADS / 64) * 16 * Cfg<bf16_t, HD>::RROW;
-    static OncePerDevice once;
-    if (once.need()) { set_smem(attn_fwd_ring16_kernel<HD, NS>, smem); }
-    const int64_t items = (int64_t)B * H;
-    const int64_t slots = device_cus();
-    const unsigned grid = (unsigned)(items < slots ? items : slots);
-    hipLaunchKernelGGL((attn_fwd_ring16_kernel<HD, NS>), dim3(grid), dim3(R16_THREADS), smem, stream,
-                       reinterpret_cast<const bf16_t*>(qkv), ld, reinterpret_cast<bf16_t*>(out), ldo, lse, N, H, hd, scale,
-                       (int)items);
-    ME_CHECK_LAUNCH("me_attention_fwd(ring16)");
-    return ME_OK;
-}
-template <int HD>
-int launch_fwd_ring16(const void* qkv, int64_t ld, void* out, int64_t ldo, float* lse, int B, int N, int H, int hd, float scale,
-                      hipStream_t stream) {
-    switch ((N + 31) / 32) {
-        case 3: return launch_fwd_ring16_ns<HD, 3>(qkv, ld, out, ldo, lse, B, N, H, hd, scale, stream);
-        case 4: return launch_fwd_ring16_ns<HD, 4>(qkv, ld, out, ldo, lse, B, N, H, hd, scale, stream);
-        case 5: return launch_fwd_ring16_ns<HD, 5>(qkv, ld, out, ldo, lse, B, N, H, hd, scale, stream);
-        case 6: return launch_fwd_ring16_ns<HD, 6>(qkv, ld, out, ldo, lse, B, N, H, hd, scale, stream);
-        default: return launch_fwd_ring16_ns<HD, 7>(qkv, ld, out, ldo, lse, B, N, H, hd, scale, stream);
-    }
-}
-template <int HD>
-int launch_bwd_small(const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dout, int64_t lddo, const float* lse,
-                     float* delta, void* dqkv, int64_t lddq, int B, int N, int H, int hd, float scale, hipStream_t stream) {
+template <int HD> int launch_bwd_small(const AttnCall& c) {
     typedef Cfg<bf16_t, HD> C;
-    const size_t smem = (size_t)4 * ((N + 31) / 32 * 32) * C::RROW + 2 * SM_MAXN * sizeof(float);
-    static OncePerDevice once;
-    if (once.need()) { set_smem(attn_bwd_small_kernel<HD>, (size_t)4 * SM_MAXN * C::RROW + 2 * SM_MAXN * sizeof(float)); }
-    hipLaunchKernelGGL((attn_bwd_small_kernel<HD>), dim3(H, B), dim3(SM_THREADS), smem, stream,
-                       reinterpret_cast<const bf16_t*>(qkv), ld, reinterpret_cast<const bf16_t*>(out), ldo,
-                       reinterpret_cast<const bf16_t*>(dout), lddo, lse, delta, reinterpret_cast<bf16_t*>(dqkv), lddq, N, H, hd,
-                       scale);
-    ME_CHECK_LAUNCH("me_attention_bwd(small)");
-    return ME_OK;
+    const auto p = c.as<bf16_t>();
+    const size_t smem = (size_t)4 * ((c.N + 31) / 32 * 32) * C::RROW + 2 * SM_MAXN * sizeof(float);
+    return attn_launch<attn_bwd_small_kernel<HD>>("me_attention_bwd(small)", dim3(c.H, c.B), SM_THREADS, smem,
+                                                  (size_t)4 * SM_MAXN * C::RROW + 2 * SM_MAXN * sizeof(float), c.stream, p.qkv, c.ld, p.out, c.ldo, p.dout,
+                                                  c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
 }
-
-template <int HD>
-int launch_fwd_stream16(const void* qkv, int64_t ld, void* out, int64_t ldo, float* lse, int B, int N, int H, int hd, float scale,
-                        hipStream_t stream) {
-    typedef RCfg<HD> R;
-    constexpr size_t smem = (size_t)ST_RING * 2 * ST_KC * R::RB + (R16_THREADS / 64) * 16 * Cfg<bf16_t, HD>::RROW;
-    static OncePerDevice once;
-    if (once.need()) { set_smem(attn_fwd_stream16_kernel<HD>, smem); }
-    // query blocks of (at most) 14 x 16 rows, evened out over the sequence
-    const int nqb = (N + 223) / 224;
-    const int QB = ((N + nqb - 1) / nqb + 15) / 16 * 16;
-    const int64_t items = (int64_t)B * H * nqb;
-    const int64_t slots = device_cus();
-    const unsigned grid = (unsigned)(items < slots ? items : slots);
-    hipLaunchKernelGGL((attn_fwd_stream16_kernel<HD>), dim3(grid), dim3(R16_THREADS), smem, stream,
-                       reinterpret_cast<const bf16_t*>(qkv), ld, reinterpret_cast<bf16_t*>(out), ldo, lse, N, H, hd, scale, QB, nqb,
-                       (int)items);
-    ME_CHECK_LAUNCH("me_attention_fwd(stream16)");
-    return ME_OK;
+template <int HD, int NS> int launch_fwd_ring16(const AttnCall& c) {
+    constexpr size_t smem = (size_t)4 * NS * 32 * RCfg<HD>::RB + (R16_THREADS / 64) * 16 * Cfg<bf16_t, HD>::RROW;
+    const auto p = c.as<bf16_t>();
+    const int64_t items = (int64_t)c.B * c.H;
+    return attn_launch<attn_fwd_ring16_kernel<HD, NS>>("me_attention_fwd(ring16)", dim3(persistent_grid(items)), R16_THREADS, smem, smem, c.stream, p.qkv,
+                                                       c.ld, p.out, c.ldo, c.lse, c.N, c.H, c.hd, c.scale, (int)items);
 }
-template <int HD>
-int launch_bwd_stream16(const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dout, int64_t lddo, const float* lse,
-                        float* delta, void* dqkv, int64_t lddq, int B, int N, int H, int hd, float scale, hipStream_t stream) {
-    typedef RCfg<HD> R;
-    constexpr size_t ring = (size_t)ST_RING * 2 * ST_KC * R::RB, fl = (size_t)ST_RING * 2 * ST_KC * sizeof(float);
+template <int HD, int NS> int launch_bwd_ring16(const AttnCall& c) {
+    constexpr size_t smem = (size_t)4 * NS * 32 * RCfg<HD>::RB + 2 * NS * 32 * sizeof(float) + (R16_THREADS / 64) * 16 * Cfg<bf16_t, HD>::RROW + 16;
+    const auto p = c.as<bf16_t>();
+    unsigned* ctr = me_work_counters(c.stream);      // (null while capturing: static schedule)
+    if (ctr) ctr += 1;                                // word 1 of the stream's set (word 0: the resident GEMM, XCD 0)
+    const int64_t items = (int64_t)c.B * c.H;
+    return attn_launch<attn_bwd_ring16_kernel<HD, NS>>("me_attention_bwd(ring16)", dim3(persistent_grid(items)), R16_THREADS, smem, smem, c.stream, p.qkv,
+                                                       c.ld, p.out, c.ldo, p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale, (int)items,
+                                                       ctr);
+}
+template <int HD> int launch_fwd_stream16(const AttnCall& c, const AttnRoute& r) {
+    constexpr size_t smem = (size_t)ST_RING * 2 * ST_KC * RCfg<HD>::RB + (R16_THREADS / 64) * 16 * Cfg<bf16_t, HD>::RROW;
+    const auto p = c.as<bf16_t>();
+    const int64_t items = (int64_t)c.B * c.H * r.nblk;
+    return attn_launch<attn_fwd_stream16_kernel<HD>>("me_attention_fwd(stream16)", dim3(persistent_grid(items)), R16_THREADS, smem, smem, c.stream, p.qkv, c.ld,
+                                                     p.out, c.ldo, c.lse, c.N, c.H, c.hd, c.scale, r.rows, r.nblk, (int)items);
+}
+template <int HD> int launch_bwd_stream16(const AttnCall& c, const AttnRoute& r) {
+    constexpr size_t ring = (size_t)ST_RING * 2 * ST_KC * RCfg<HD>::RB, fl = (size_t)ST_RING * 2 * ST_KC * sizeof(float);
     constexpr size_t smem1 = ring + (R16_THREADS / 64) * 16 * Cfg<bf16_t, HD>::RROW;
     constexpr size_t smem2 = smem1 + fl;
     constexpr size_t smem3 = ring + (ST32_THREADS / 64) * 16 * Cfg<bf16_t, HD>::RROW + fl;
-    static OncePerDevice once;
-    if (once.need()) {
-        set_smem(attn_bwd_dq_stream16_kernel<HD>, smem1);
-        set_smem(attn_bwd_dkdv_stream16_kernel<HD>, smem2);
-        set_smem(attn_bwd_dkdv_stream32_kernel<HD>, smem3);
-    }
-    // row blocks of (at most) 14 x 16 rows, evened out over the sequence (queries in the first kernel, keys in the second)
-    const int nrb = (N + 223) / 224;
-    const int RBk = ((N + nrb - 1) / nrb + 15) / 16 * 16;
-    const int64_t items = (int64_t)B * H * nrb;
-    const int64_t slots = device_cus();
-    const unsigned grid = (unsigned)(items < slots ? items : slots);
-    hipLaunchKernelGGL((attn_bwd_dq_stream16_kernel<HD>), dim3(grid), dim3(R16_THREADS), smem1, stream,
-                       reinterpret_cast<const bf16_t*>(qkv), ld, reinterpret_cast<const bf16_t*>(out), ldo,
-                       reinterpret_cast<const bf16_t*>(dout), lddo, lse, delta, reinterpret_cast<bf16_t*>(dqkv), lddq, N, H, hd, scale,
-                       RBk, nrb, (int)items);
-    ME_CHECK_LAUNCH("me_attention_bwd(dq stream16)");
-    // dK / dV: 32-key waves when the key blocks fill seven of them (see attn_bwd_dkdv_stream32_kernel)
-    const int KB32 = (RBk + 31) / 32 * 32;
-    if (KB32 == 224) {
-        hipLaunchKernelGGL((attn_bwd_dkdv_stream32_kernel<HD>), dim3(grid), dim3(ST32_THREADS), smem3, stream,
-                           reinterpret_cast<const bf16_t*>(qkv), ld, reinterpret_cast<const bf16_t*>(dout), lddo, lse, delta,
-                           reinterpret_cast<bf16_t*>(dqkv), lddq, N, H, hd, scale, KB32, nrb, (int)items);
-        ME_CHECK_LAUNCH("me_attention_bwd(dkdv stream32)");
-        return ME_OK;
-    }
-    hipLaunchKernelGGL((attn_bwd_dkdv_stream16_kernel<HD>), dim3(grid), dim3(R16_THREADS), smem2, stream,
-                       reinterpret_cast<const bf16_t*>(qkv), ld, reinterpret_cast<const bf16_t*>(dout), lddo, lse, delta,
-                       reinterpret_cast<bf16_t*>(dqkv), lddq, N, H, hd, scale, RBk, nrb, (int)items);
-    ME_CHECK_LAUNCH("me_attention_bwd(dkdv stream16)");
-    return ME_OK;
+    const auto p = c.as<bf16_t>();
+    const int64_t items = (int64_t)c.B * c.H * r.nblk;
+    const dim3 grid(persistent_grid(items));
+    if (int rc = attn_launch<attn_bwd_dq_stream16_kernel<HD>>("me_attention_bwd(dq stream16)", grid, R16_THREADS, smem1, smem1, c.stream, p.qkv, c.ld, p.out,
+                                                              c.ldo, p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale, r.rows, r.nblk,
+                                                              (int)items))
+        return rc;
+    if (!r.dkdv32)
+        return attn_launch<attn_bwd_dkdv_stream16_kernel<HD>>("me_attention_bwd(dkdv stream16)", grid, R16_THREADS, smem2, smem2, c.stream, p.qkv, c.ld, p.dout,
+                                                              c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale, r.krows, r.nblk, (int)items);
+    return attn_launch<attn_bwd_dkdv_stream32_kernel<HD>>("me_attention_bwd(dkdv stream32)", grid, ST32_THREADS, smem3, smem3, c.stream, p.qkv, c.ld, p.dout,
+                                                          c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale, r.krows, r.nblk, (int)items);
 }
-template <int HD, int NS>
-int launch_bwd_ring16_ns(const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dout, int64_t lddo, const float* lse,
-                         float* delta, void* dqkv, int64_t lddq, int B, int N, int H, int hd, float scale, hipStream_t stream) {
-    typedef RCfg<HD> R;
-    constexpr size_t smem = (size_t)4 * NS * 32 * R::RB + 2 * NS * 32 * sizeof(float) + (R16_THREADS / 64) * 16 * Cfg<bf16_t, HD>::RROW + 16;
-    static OncePerDevice once;
-    if (once.need()) { set_smem(attn_bwd_ring16_kernel<HD, NS>, smem); }
-    unsigned* ctr = me_work_counters(stream);      // (null while capturing: static schedule)
-    if (ctr) ctr += 1;                              // word 1 of the stream's set (word 0: the resident GEMM, XCD 0)
-    const int64_t items = (int64_t)B * H;
-    const int64_t slots = device_cus();
-    const unsigned grid = (unsigned)(items < slots ? items : slots);
-    hipLaunchKernelGGL((attn_bwd_ring16_kernel<HD, NS>), dim3(grid), dim3(R16_THREADS), smem, stream,
-                       reinterpret_cast<const bf16_t*>(qkv), ld, reinterpret_cast<const bf16_t*>(out), ldo,
-                       reinterpret_cast<const bf16_t*>(dout), lddo, lse, delta, reinterpret_cast<bf16_t*>(dqkv), lddq, N, H, hd, scale,
-                       (int)items, ctr);
-    ME_CHECK_LAUNCH("me_attention_bwd(ring16)");
-    return ME_OK;
-}
-template <int HD>
-int launch_bwd_ring16(const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dout, int64_t lddo, const float* lse,
-                      float* delta, void* dqkv, int64_t lddq, int B, int N, int H, int hd, float scale, hipStream_t stream) {
-    switch ((N + 31) / 32) {
-        case 3: return launch_bwd_ring16_ns<HD, 3>(qkv, ld, out, ldo, dout, lddo, lse, delta, dqkv, lddq, B, N, H, hd, scale, stream);
-        case 4: return launch_bwd_ring16_ns<HD, 4>(qkv, ld, out, ldo, dout, lddo, lse, delta, dqkv, lddq, B, N, H, hd, scale, stream);
-        case 5: return launch_bwd_ring16_ns<HD, 5>(qkv, ld, out, ldo, dout, lddo, lse, delta, dqkv, lddq, B, N, H, hd, scale, stream);
-        case 6: return launch_bwd_ring16_ns<HD, 6>(qkv, ld, out, ldo, dout, lddo, lse, delta, dqkv, lddq, B, N, H, hd, scale, stream);
-        default: return launch_bwd_ring16_ns<HD, 7>(qkv, ld, out, ldo, dout, lddo, lse, delta, dqkv, lddq, B, N, H, hd, scale, stream);
-    }
-}
-template <int HD, int NTHR, int MAXN>
-int launch_fwd_mid(const void* qkv, int64_t ld, void* out, int64_t ldo, float* lse, int B, int N, int H, int hd, float scale,
-                   hipStream_t stream) {
+template <int HD> int launch_fwd_mid(const AttnCall& c) {
     typedef Cfg<bf16_t, HD> C;
-    const size_t smem = (size_t)2 * ((N + 31) / 32 * 32) * C::RROW;
-    static OncePerDevice once;
-    if (once.need()) { set_smem(attn_fwd_mid_kernel<HD, NTHR, MAXN>, (size_t)2 * MAXN * C::RROW); }
-    hipLaunchKernelGGL((attn_fwd_mid_kernel<HD, NTHR, MAXN>), dim3(H, B), dim3(NTHR), smem, stream,
-                       reinterpret_cast<const bf16_t*>(qkv), ld, reinterpret_cast<bf16_t*>(out), ldo, lse, N, H, hd, scale);
-    ME_CHECK_LAUNCH("me_attention_fwd(mid)");
-    return ME_OK;
+    const auto p = c.as<bf16_t>();
+    return attn_launch<attn_fwd_mid_kernel<HD, 512, MD_MAXN>>("me_attention_fwd(mid)", dim3(c.H, c.B), 512, (size_t)2 * ((c.N + 31) / 32 * 32) * C::RROW,
+                                                              (size_t)2 * MD_MAXN * C::RROW, c.stream, p.qkv, c.ld, p.out, c.ldo, c.lse, c.N, c.H, c.hd, c.scale);
 }
-template <int HD, int NTHR, int MAXN>
-int launch_bwd_mid(const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dout, int64_t lddo, const float* lse,
-                   float* delta, void* dqkv, int64_t lddq, int B, int N, int H, int hd, float scale, hipStream_t stream) {
+template <int HD> int launch_bwd_mid(const AttnCall& c) {
     typedef Cfg<bf16_t, HD> C;
-    const size_t smem = (size_t)2 * ((N + 31) / 32 * 32) * C::RROW + 2 * MAXN * sizeof(float);
-    static OncePerDevice once;
-    if (once.need()) { set_smem(attn_bwd_mid_kernel<HD, NTHR, MAXN>, (size_t)2 * MAXN * C::RROW + 2 * MAXN * sizeof(float)); }
-    hipLaunchKernelGGL((attn_bwd_mid_kernel<HD, NTHR, MAXN>), dim3(H, B), dim3(NTHR), smem, stream,
-                       reinterpret_cast<const bf16_t*>(qkv), ld, reinterpret_cast<const bf16_t*>(out), ldo,
-                       reinterpret_cast<const bf16_t*>(dout), lddo, lse, delta, reinterpret_cast<bf16_t*>(dqkv), lddq, N, H, hd,
-                       scale);
-    ME_CHECK_LAUNCH("me_attention_bwd(mid)");
-    return ME_OK;
+    const auto p = c.as<bf16_t>();
+    return attn_launch<attn_bwd_mid_kernel<HD, 512, MD_MAXN>>("me_attention_bwd(mid)", dim3(c.H, c.B), 512,
+                                                              (size_t)2 * ((c.N + 31) / 32 * 32) * C::RROW + 2 * MD_MAXN * sizeof(float),
+                                                              (size_t)2 * MD_MAXN * C::RROW + 2 * MD_MAXN * sizeof(float), c.stream, p.qkv, c.ld, p.out, c.ldo,
+                                                              p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
+}
+template <int HD> int launch_fwd_chunk(const AttnCall& c) {
+    const size_t smem = (size_t)2 * CH_ROWS * Cfg<bf16_t, HD>::RROW;
+    const auto p = c.as<bf16_t>();
+    return attn_launch<attn_fwd_chunk_kernel<HD>>("me_attention_fwd(chunk)", dim3((c.N + CH_ROWS - 1) / CH_ROWS, c.H, c.B), SM_THREADS, smem, smem, c.stream,
+                                                  p.qkv, c.ld, p.out, c.ldo, c.lse, c.N, c.H, c.hd, c.scale);
+}
+template <int HD> int launch_bwd_chunk(const AttnCall& c) {
+    const size_t smem1 = (size_t)2 * CH_ROWS * Cfg<bf16_t, HD>::RROW, smem2 = smem1 + 2 * CH_ROWS * sizeof(float);
+    const auto p = c.as<bf16_t>();
+    const dim3 grid((c.N + CH_ROWS - 1) / CH_ROWS, c.H, c.B);
+    if (int rc = attn_launch<attn_bwd_dq_chunk_kernel<HD>>("me_attention_bwd(dq chunk)", grid, SM_THREADS, smem1, smem1, c.stream, p.qkv, c.ld, p.out, c.ldo,
+                                                           p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale))
+        return rc;
+    return attn_launch<attn_bwd_dkdv_chunk_kernel<HD>>("me_attention_bwd(dkdv chunk)", grid, SM_THREADS, smem2, smem2, c.stream, p.qkv, c.ld, p.dout, c.lddo,
+                                                       c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
 }
 
-template <int HD>
-int launch_fwd_chunk(const void* qkv, int64_t ld, void* out, int64_t ldo, float* lse, int B, int N, int H, int hd, float scale,
-                     hipStream_t stream) {
-    typedef Cfg<bf16_t, HD> C;
-    const size_t smem = (size_t)2 * CH_ROWS * C::RROW;
-    static OncePerDevice once;
-    if (once.need()) { set_smem(attn_fwd_chunk_kernel<HD>, smem); }
-    hipLaunchKernelGGL((attn_fwd_chunk_kernel<HD>), dim3((N + CH_ROWS - 1) / CH_ROWS, H, B), dim3(SM_THREADS), smem, stream,
-                       reinterpret_cast<const bf16_t*>(qkv), ld, reinterpret_cast<bf16_t*>(out), ldo, lse, N, H, hd, scale);
-    ME_CHECK_LAUNCH("me_attention_fwd(chunk)");
-    return ME_OK;
-}
-template <int HD>
-int launch_bwd_chunk(const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dout, int64_t lddo, const float* lse,
-                     float* delta, void* dqkv, int64_t lddq, int B, int N, int H, int hd, float scale, hipStream_t stream) {
-    typedef Cfg<bf16_t, HD> C;
-    const size_t smem1 = (size_t)2 * CH_ROWS * C::RROW, smem2 = smem1 + 2 * CH_ROWS * sizeof(float);
-    static OncePerDevice once;
-    if (once.need()) {
-        set_smem(attn_bwd_dq_chunk_kernel<HD>, smem1);
-        set_smem(attn_bwd_dkdv_chunk_kernel<HD>, smem2);
-    }
-    dim3 grid((N + CH_ROWS - 1) / CH_ROWS, H, B);
-    hipLaunchKernelGGL((attn_bwd_dq_chunk_kernel<HD>), grid, dim3(SM_THREADS), smem1, stream, reinterpret_cast<const bf16_t*>(qkv),
-                       ld, reinterpret_cast<const bf16_t*>(out), ldo, reinterpret_cast<const bf16_t*>(dout), lddo, lse, delta,
-                       reinterpret_cast<bf16_t*>(dqkv), lddq, N, H, hd, scale);
-    ME_CHECK_LAUNCH("me_attention_bwd(dq chunk)");
-    hipLaunchKernelGGL((attn_bwd_dkdv_chunk_kernel<HD>), grid, dim3(SM_THREADS), smem2, stream, reinterpret_cast<const bf16_t*>(qkv),
-                       ld, reinterpret_cast<const bf16_t*>(dout), lddo, lse, delta, reinterpret_cast<bf16_t*>(dqkv), lddq, N, H, hd,
-                       scale);
-    ME_CHECK_LAUNCH("me_attention_bwd(dkdv chunk)");
-    return ME_OK;
-}
-
-template <typename T, int HD>
-int launch_fwd(const void* qkv, int64_t ld, void* out, int64_t ldo, float* lse, int B, int N, int H, int hd, float scale,
-               float p_drop, uint64_t seed, hipStream_t stream) {
+// the generic tiled kernels (either dtype, head_dim up to 128, dropout)
+template <typename T, int HD> int launch_fwd(const AttnCall& c) {
     typedef Cfg<T, HD> C;
     const size_t smem = C::R_BYTES + (C::T_BYTES > C::R_BYTES ? C::T_BYTES : C::R_BYTES);   // V tile: transposed (fp32) or row-major (bf16)
-    static OncePerDevice once;
-    if (once.need()) { set_smem(attn_fwd_kernel<T, HD>, smem); }
-    dim3 grid((N + QPB - 1) / QPB, H, B);
-    hipLaunchKernelGGL((attn_fwd_kernel<T, HD>), grid, dim3(AT_THREADS), smem, stream, reinterpret_cast<const T*>(qkv), ld,
-                       reinterpret_cast<T*>(out), ldo, lse, N, H, hd, scale, p_drop, seed);
-    ME_CHECK_LAUNCH("me_attention_fwd");
-    return ME_OK;
+    const auto p = c.as<T>();
+    return attn_launch<attn_fwd_kernel<T, HD>>("me_attention_fwd", dim3((c.N + QPB - 1) / QPB, c.H, c.B), AT_THREADS, smem, smem, c.stream, p.qkv, c.ld, p.out,
+                                               c.ldo, c.lse, c.N, c.H, c.hd, c.scale, c.p_drop, c.seed);
 }
-
-template <typename T, int HD>
-int launch_bwd(const void* qkv, int64_t ld, const void* dout, int64_t lddo, const float* lse, const float* delta, void* dqkv,
-               int64_t lddq, int B, int N, int H, int hd, float scale, float p_drop, uint64_t seed, hipStream_t stream) {
+template <typename T, int HD> int launch_bwd(const AttnCall& c) {
     typedef Cfg<T, HD> C;
     constexpr size_t TB = TRead<T, HD>::kNeedsTransposedTile ? C::T_BYTES : 0;
     const size_t smem1 = 2 * C::R_BYTES + 2 * TB + 2 * KVT * sizeof(float);
     const size_t smem2 = 2 * C::R_BYTES + TB;
-    static OncePerDevice once;
-    if (once.need()) {
-        set_smem(attn_bwd_dkdv_kernel<T, HD>, smem1);
-        set_smem(attn_bwd_dq_kernel<T, HD>, smem2);
+    const auto p = c.as<T>();
+    const dim3 grid((c.N + QPB - 1) / QPB, c.H, c.B);
+    if (int rc = attn_launch<attn_bwd_dkdv_kernel<T, HD>>("me_attention_bwd(dkdv)", grid, AT_THREADS, smem1, smem1, c.stream, p.qkv, c.ld, p.dout, c.lddo, c.lse,
+                                                          c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale, c.p_drop, c.seed))
+        return rc;
+    return attn_launch<attn_bwd_dq_kernel<T, HD>>("me_attention_bwd(dq)", grid, AT_THREADS, smem2, smem2, c.stream, p.qkv, c.ld, p.dout, c.lddo, c.lse, c.delta,
+                                                  p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale, c.p_drop, c.seed);
+}
+// delta = rowsum(dO o O): the generic backward's first pass
+int launch_delta(const AttnCall& c) {
+    const int64_t rows = (int64_t)c.B * c.N;
+    const int64_t nw = rows * c.H;
+    const int lph = c.hd / 8;
+    if (c.dtype == ME_BF16 && c.hd % 8 == 0 && (lph & (lph - 1)) == 0 && lph <= 64 && c.ldo % 8 == 0 && c.lddo % 8 == 0) {
+        const auto p = c.as<bf16_t>();
+        hipLaunchKernelGGL(attn_delta_vec_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, c.stream, p.out, c.ldo, p.dout, c.lddo, c.delta, c.N, c.H,
+                           c.hd, rows);
+    } else {
+        hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, c.stream, c.out, c.ldo, c.dout, c.lddo, c.dtype, c.delta, c.N,
+                           c.H, c.hd, rows);
     }
-    dim3 grid((N + QPB - 1) / QPB, H, B);
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, HD>), grid, dim3(AT_THREADS), smem1, stream,
-                       reinterpret_cast<const T*>(qkv), ld, reinterpret_cast<const T*>(dout), lddo, lse, delta,
-                       reinterpret_cast<T*>(dqkv), lddq, N, H, hd, scale, p_drop, seed);
-    ME_CHECK_LAUNCH("me_attention_bwd(dkdv)");
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, HD>), grid, dim3(AT_THREADS), smem2, stream,
-                       reinterpret_cast<const T*>(qkv), ld, reinterpret_cast<const T*>(dout), lddo, lse, delta,
-                       reinterpret_cast<T*>(dqkv), lddq, N, H, hd, scale, p_drop, seed);
-    ME_CHECK_LAUNCH("me_attention_bwd(dq)");
+    ME_CHECK_LAUNCH("me_attention_bwd(delta)");
     return ME_OK;
 }
 
@@ -3296,19 +3237,6 @@ int check_attn_args(const char* fn, int64_t ld, int B, int N, int H, int hd, int
 
 }  // namespace
 
-#define ATTN_DISPATCH(FN, ...)                                                                   \
-    do {                                                                                         \
-        if (dtype == ME_BF16) {                                                                  \
-            if (head_dim <= 32) return FN<bf16_t, 32>(__VA_ARGS__);                              \
-            if (head_dim <= 64) return FN<bf16_t, 64>(__VA_ARGS__);                              \
-            return FN<bf16_t, 128>(__VA_ARGS__);                                                 \
-        } else {                                                                                 \
-            if (head_dim <= 32) return FN<float, 32>(__VA_ARGS__);                               \
-            if (head_dim <= 64) return FN<float, 64>(__VA_ARGS__);                               \
-            return FN<float, 128>(__VA_ARGS__);                                                  \
-        }                                                                                        \
-    } while (0)
-
 extern "C" int me_attention_fwd(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, float* lse, int B, int N,
                                 int H, int head_dim, float scale, int dtype, float p_drop, uint64_t seed, void* stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -3318,31 +3246,19 @@ extern "C" int me_attention_fwd(const void* qkv, int64_t ld_qkv, void* out, int6
     if (rc) return rc;
     ME_CHECK_ARG(ld_out % 4 == 0, "me_attention_fwd: ld_out must be a multiple of 4");
     ME_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "me_attention_fwd: p_drop must be in [0, 1)");
-    // very short sequences (the Tabular / Graph recipes): one wave per (batch, head), attention_tiny.hip
-    if (p_drop == 0.f && N <= SM_MINN && attn_tiny_ok(dtype, ld_qkv, ld_out, B, N, H, head_dim))
-        return launch_attn_tiny_fwd(dtype, qkv, ld_qkv, out, ld_out, lse, B, N, H, head_dim, scale, stream);
-    if (p_drop == 0.f && dtype == ME_BF16 && head_dim <= 64 && N > SM_MINN && N <= SM_MAXN) {
-        if (N <= RS_MAXN && (int64_t)N * ld_qkv * 2 < (int64_t)0x7e000000) {
-            if (head_dim <= 32) return launch_fwd_ring16<32>(qkv, ld_qkv, out, ld_out, lse, B, N, H, head_dim, scale, stream);
-            return launch_fwd_ring16<64>(qkv, ld_qkv, out, ld_out, lse, B, N, H, head_dim, scale, stream);
-        }
-        if (head_dim <= 32) return launch_fwd_small<32>(qkv, ld_qkv, out, ld_out, lse, B, N, H, head_dim, scale, stream);
-        return launch_fwd_small<64>(qkv, ld_qkv, out, ld_out, lse, B, N, H, head_dim, scale, stream);
+    const AttnCall c = {qkv, ld_qkv, out, ld_out, nullptr, 0, lse, nullptr, nullptr, 0, B, N, H, head_dim, scale, dtype, p_drop, seed, stream};
+    const AttnRoute r = attn_route(c, false);
+    prof.plan = r.plan();
+    switch (r.form) {
+        case ME_ATTN_TINY: return launch_attn_tiny(c, false);
+        case ME_ATTN_RING16: return by_hd<64>(r, [&](auto HD) { return by_ns(r, [&](auto NS) { return launch_fwd_ring16<HD(), NS()>(c); }); });
+        case ME_ATTN_RESIDENT: return by_hd<64>(r, [&](auto HD) { return launch_fwd_small<HD()>(c); });
+        case ME_ATTN_STREAM16: return launch_fwd_stream16<64>(c, r);
+        case ME_ATTN_MID: return by_hd<64>(r, [&](auto HD) { return launch_fwd_mid<HD()>(c); });
+        case ME_ATTN_CHUNK: return by_hd<64>(r, [&](auto HD) { return launch_fwd_chunk<HD()>(c); });
     }
-    // (head_dim <= 32: half the MFMA work per key for the same softmax arithmetic -- the 32-row kernels below measured faster there)
-    if (p_drop == 0.f && dtype == ME_BF16 && head_dim > 32 && head_dim <= 64 && N > SM_MAXN && (int64_t)N * ld_qkv * 2 < (int64_t)0x7e000000 &&
-        (int64_t)B * H * ((N + 223) / 224) < (int64_t)0x7fffffff && ld_out % 8 == 0) {
-        return launch_fwd_stream16<64>(qkv, ld_qkv, out, ld_out, lse, B, N, H, head_dim, scale, stream);
-    }
-    if (p_drop == 0.f && dtype == ME_BF16 && head_dim <= 64 && N > SM_MAXN && N <= MD_MAXN) {
-        if (head_dim <= 32) return launch_fwd_mid<32, 512, MD_MAXN>(qkv, ld_qkv, out, ld_out, lse, B, N, H, head_dim, scale, stream);
-        return launch_fwd_mid<64, 512, MD_MAXN>(qkv, ld_qkv, out, ld_out, lse, B, N, H, head_dim, scale, stream);
-    }
-    if (p_drop == 0.f && dtype == ME_BF16 && head_dim <= 64 && N > MD_MAXN && B <= 65535) {
-        if (head_dim <= 32) return launch_fwd_chunk<32>(qkv, ld_qkv, out, ld_out, lse, B, N, H, head_dim, scale, stream);
-        return launch_fwd_chunk<64>(qkv, ld_qkv, out, ld_out, lse, B, N, H, head_dim, scale, stream);
-    }
-    ATTN_DISPATCH(launch_fwd, qkv, ld_qkv, out, ld_out, lse, B, N, H, head_dim, scale, p_drop, seed, stream);
+    if (dtype == ME_BF16) return by_hd<128>(r, [&](auto HD) { return launch_fwd<bf16_t, HD()>(c); });
+    return by_hd<128>(r, [&](auto HD) { return launch_fwd<float, HD()>(c); });
 }
 
 extern "C" int me_attention_bwd(const void* qkv, int64_t ld_qkv, const void* out, int64_t ld_out, const void* dout,
@@ -3357,49 +3273,19 @@ extern "C" int me_attention_bwd(const void* qkv, int64_t ld_qkv, const void* out
     const int E = dtype == ME_BF16 ? 8 : 4;
     ME_CHECK_ARG(ld_dout % E == 0 && ld_dqkv % 4 == 0, "me_attention_bwd: bad strides");
     ME_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "me_attention_bwd: p_drop must be in [0, 1)");
-    if (p_drop == 0.f && N <= SM_MINN && attn_tiny_ok(dtype, ld_qkv, ld_out, B, N, H, head_dim) && ld_dout % E == 0 && ld_dqkv % E == 0)
-        return launch_attn_tiny_bwd(dtype, qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, delta, dqkv, ld_dqkv, B, N, H, head_dim, scale, stream);
-    if (p_drop == 0.f && dtype == ME_BF16 && head_dim <= 64 && N > SM_MINN && N <= SM_MAXN && ld_out % 8 == 0) {
-        if (N <= RS_MAXN && (int64_t)N * ld_qkv * 2 < (int64_t)0x7e000000 && (int64_t)N * ld_dout * 2 < (int64_t)0x7e000000) {
-            if (head_dim <= 32)
-                return launch_bwd_ring16<32>(qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, delta, dqkv, ld_dqkv, B, N, H, head_dim, scale, stream);
-            return launch_bwd_ring16<64>(qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, delta, dqkv, ld_dqkv, B, N, H, head_dim, scale, stream);
-        }
-        if (head_dim <= 32)
-            return launch_bwd_small<32>(qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, delta, dqkv, ld_dqkv, B, N, H, head_dim,
-                                        scale, stream);
-        return launch_bwd_small<64>(qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, delta, dqkv, ld_dqkv, B, N, H, head_dim, scale,
-                                    stream);
+    const AttnCall c = {qkv, ld_qkv, const_cast<void*>(out), ld_out, dout, ld_dout, const_cast<float*>(lse), delta, dqkv, ld_dqkv,
+                        B, N, H, head_dim, scale, dtype, p_drop, seed, stream};
+    const AttnRoute r = attn_route(c, true);
+    prof.plan = r.plan();
+    switch (r.form) {
+        case ME_ATTN_TINY: return launch_attn_tiny(c, true);
+        case ME_ATTN_RING16: return by_hd<64>(r, [&](auto HD) { return by_ns(r, [&](auto NS) { return launch_bwd_ring16<HD(), NS()>(c); }); });
+        case ME_ATTN_RESIDENT: return by_hd<64>(r, [&](auto HD) { return launch_bwd_small<HD()>(c); });
+        case ME_ATTN_STREAM16: return launch_bwd_stream16<64>(c, r);
+        case ME_ATTN_MID: return by_hd<64>(r, [&](auto HD) { return launch_bwd_mid<HD()>(c); });
+        case ME_ATTN_CHUNK: return by_hd<64>(r, [&](auto HD) { return launch_bwd_chunk<HD()>(c); });
     }
-    if (p_drop == 0.f && dtype == ME_BF16 && head_dim > 32 && head_dim <= 64 && N >= ST_BWD_MINN && ld_out % 8 == 0 && ld_dqkv % 8 == 0 &&
-        (int64_t)N * ld_qkv * 2 < (int64_t)0x7e000000 && (int64_t)N * ld_dout * 2 < (int64_t)0x7e000000 &&
-        (int64_t)B * H * ((N + 223) / 224) < (int64_t)0x7fffffff) {
-        return launch_bwd_stream16<64>(qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, delta, dqkv, ld_dqkv, B, N, H, head_dim, scale, stream);
-    }
-    if (p_drop == 0.f && dtype == ME_BF16 && head_dim <= 64 && N > SM_MAXN && N <= MD_MAXN && ld_out % 8 == 0) {
-        if (head_dim <= 32)
-            return launch_bwd_mid<32, 512, MD_MAXN>(qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, delta, dqkv, ld_dqkv, B, N, H,
-                                                    head_dim, scale, stream);
-        return launch_bwd_mid<64, 512, MD_MAXN>(qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, delta, dqkv, ld_dqkv, B, N, H,
-                                                head_dim, scale, stream);
-    }
-    if (p_drop == 0.f && dtype == ME_BF16 && head_dim <= 64 && N > MD_MAXN && ld_out % 8 == 0) {
-        if (head_dim <= 32)
-            return launch_bwd_chunk<32>(qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, delta, dqkv, ld_dqkv, B, N, H, head_dim, scale,
-                                        stream);
-        return launch_bwd_chunk<64>(qkv, ld_qkv, out, ld_out, dout, ld_dout, lse, delta, dqkv, ld_dqkv, B, N, H, head_dim, scale,
-                                    stream);
-    }
-    const int64_t rows = (int64_t)B * N;
-    const int64_t nw = rows * H;
-    const int lph = head_dim / 8;
-    if (dtype == ME_BF16 && head_dim % 8 == 0 && (lph & (lph - 1)) == 0 && lph <= 64 && ld_out % 8 == 0 && ld_dout % 8 == 0)
-        hipLaunchKernelGGL(attn_delta_vec_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream,
-                           reinterpret_cast<const bf16_t*>(out), ld_out, reinterpret_cast<const bf16_t*>(dout), ld_dout, delta, N,
-                           H, head_dim, rows);
-    else
-        hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, stream, out, ld_out, dout, ld_dout,
-                           dtype, delta, N, H, head_dim, rows);
-    ME_CHECK_LAUNCH("me_attention_bwd(delta)");
-    ATTN_DISPATCH(launch_bwd, qkv, ld_qkv, dout, ld_dout, lse, delta, dqkv, ld_dqkv, B, N, H, head_dim, scale, p_drop, seed, stream);
+    if ((rc = launch_delta(c))) return rc;
+    if (dtype == ME_BF16) return by_hd<128>(r, [&](auto HD) { return launch_bwd<bf16_t, HD()>(c); });
+    return by_hd<128>(r, [&](auto HD) { return launch_bwd<float, HD()>(c); });
 }

@@ -1,0 +1,54 @@
+// attention_host.h -- host side of the attention entry points: what me_attention_fwd / _bwd (attention.hip) hand from validation to
+// route to launch, shared with the N <= 64 kernels of attention_tiny.hip and with block.hip.  No device code.
+#pragma once
+#include "common.h"
+
+// One call's arguments, filled once by the entry point after validation.  The backward-only fields stay null / 0 in a forward call.
+struct AttnCall {
+    const void* qkv; int64_t ld;
+    void* out; int64_t ldo;            // (backward reads it)
+    const void* dout; int64_t lddo;
+    float* lse;                        // (backward reads it)
+    float* delta;
+    void* dqkv; int64_t lddq;
+    int B, N, H, hd;
+    float scale;
+    int dtype;
+    float p_drop;
+    uint64_t seed;
+    hipStream_t stream;
+    // the typed pointers of a kernel instantiated for element type T
+    template <typename T> struct Ptrs { const T* qkv; T* out; const T* dout; T* dqkv; };
+    template <typename T> Ptrs<T> as() const {
+        return {static_cast<const T*>(qkv), static_cast<T*>(out), static_cast<const T*>(dout), static_cast<T*>(dqkv)};
+    }
+};
+
+// What attn_route (attention.hip) decides for a call.  form: ME_ATTN_* of include/metaenc.h.
+struct AttnRoute {
+    int form;
+    int hd;                // instantiated head width: 32, 64 or 128
+    int ns;                // ring16: 32-row sub-tiles of the sequence (3 .. 7)
+    int nblk, rows;        // stream16: row blocks per (batch, head) and rows per block
+    int krows;             // stream16 backward: keys per block of the dK / dV kernel
+    bool dkdv32;           // stream16 backward: dK / dV on the 32-key kernel
+    int plan() const { return form | (dkdv32 ? ME_ATTN_DKDV32 : 0); }       // me_gemm_profile_rec.plan
+};
+
+// attention_tiny.hip: N <= 64, one small workgroup per (batch, head)
+bool attn_tiny_ok(const AttnCall& c);
+int launch_attn_tiny(const AttnCall& c, bool backward);
+
+// an ME_BF16X3 Block runs its attention as three bf16 products (attention_x3.hip) at this shape, on the exact-fp32 kernels otherwise
+// (N <= 64: the exact-fp32 one-workgroup-per-head kernels, attention_tiny.hip, are faster and exact)
+inline bool attn_x3_takes(int hd, int N) { return hd == 64 && N > 64; }
+
+// Launch of one kernel instantiation: its dynamic-LDS limit (lds_max: the most any call asks of it) is raised once per device.
+template <auto Kernel, typename... Args>
+int attn_launch(const char* label, dim3 grid, int threads, size_t lds, size_t lds_max, hipStream_t stream, Args... args) {
+    static OncePerDevice once;
+    if (once.need()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+    hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, stream, args...);
+    ME_CHECK_LAUNCH(label);
+    return ME_OK;
+}

@@ -25,7 +25,7 @@
 // fp32 (the reference's default arithmetic; Tabular runs it): the same kernels on v_mfma_f32_16x16x4_f32 -- exact products, fp32 P and dS.
 // A lane's 16-byte fragment is then 4 floats = its share of FOUR k-steps of 4 (the contraction order inside a 16-long block is permuted
 // identically on both operands), so the LDS addressing is byte for byte the bf16 one: row * pitch + 64 * kstep + 16 * g.
-#include "common.h"
+#include "attention_host.h"
 
 namespace {
 
@@ -314,74 +314,34 @@ __global__ __launch_bounds__(NMAX * 4) void attn_tiny_bwd_kernel(const T* __rest
     }
 }
 
-template <typename T, int HD, int NMAX>
-int launch_fwd(const void* qkv, int64_t ld, void* out, int64_t ldo, float* lse, int B, int N, int H, int hd, float scale, hipStream_t stream) {
+// one instantiation of one direction
+template <typename T, int HD, int NMAX, bool BWD> int launch(const AttnCall& c) {
     typedef TinyCfg<T, HD, NMAX> C;
-    static OncePerDevice once;
-    if (once.need()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_tiny_fwd_kernel<T, HD, NMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, C::FWD_LDS);
-    hipLaunchKernelGGL((attn_tiny_fwd_kernel<T, HD, NMAX>), dim3((unsigned)((int64_t)B * H)), dim3(NMAX * 4), C::FWD_LDS, stream, reinterpret_cast<const T*>(qkv), ld,
-                       reinterpret_cast<T*>(out), ldo, lse, N, H, hd, scale);
-    ME_CHECK_LAUNCH("me_attention_fwd(tiny)");
-    return ME_OK;
+    const auto p = c.as<T>();
+    const dim3 grid((unsigned)((int64_t)c.B * c.H));
+    if constexpr (BWD)
+        return attn_launch<attn_tiny_bwd_kernel<T, HD, NMAX>>("me_attention_bwd(tiny)", grid, NMAX * 4, C::BWD_LDS, C::BWD_LDS, c.stream, p.qkv, c.ld, p.out, c.ldo,
+                                                              p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
+    else
+        return attn_launch<attn_tiny_fwd_kernel<T, HD, NMAX>>("me_attention_fwd(tiny)", grid, NMAX * 4, C::FWD_LDS, C::FWD_LDS, c.stream, p.qkv, c.ld, p.out, c.ldo,
+                                                              c.lse, c.N, c.H, c.hd, c.scale);
 }
-template <typename T, int HD, int NMAX>
-int launch_bwd(const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dout, int64_t lddo, const float* lse, float* delta, void* dqkv,
-               int64_t lddq, int B, int N, int H, int hd, float scale, hipStream_t stream) {
-    typedef TinyCfg<T, HD, NMAX> C;
-    static OncePerDevice once;
-    if (once.need()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_tiny_bwd_kernel<T, HD, NMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, C::BWD_LDS);
-    hipLaunchKernelGGL((attn_tiny_bwd_kernel<T, HD, NMAX>), dim3((unsigned)((int64_t)B * H)), dim3(NMAX * 4), C::BWD_LDS, stream, reinterpret_cast<const T*>(qkv), ld,
-                       reinterpret_cast<const T*>(out), ldo, reinterpret_cast<const T*>(dout), lddo, lse, delta, reinterpret_cast<T*>(dqkv), lddq,
-                       N, H, hd, scale);
-    ME_CHECK_LAUNCH("me_attention_bwd(tiny)");
-    return ME_OK;
+// element type, head width (32 / 64) and token capacity (16 / 32 / 64) of the instantiation a call takes
+template <typename T, int HD, bool BWD> int launch_n(const AttnCall& c) {
+    if (c.N <= 16) return launch<T, HD, 16, BWD>(c);
+    if (c.N <= 32) return launch<T, HD, 32, BWD>(c);
+    return launch<T, HD, 64, BWD>(c);
 }
+template <typename T, bool BWD> int launch_hd(const AttnCall& c) { return c.hd <= 32 ? launch_n<T, 32, BWD>(c) : launch_n<T, 64, BWD>(c); }
+template <bool BWD> int launch_t(const AttnCall& c) { return c.dtype == ME_BF16 ? launch_hd<bf16_t, BWD>(c) : launch_hd<float, BWD>(c); }
 
 }  // namespace
 
 // no dropout, N <= 64, head_dim <= 64, 16-byte aligned head rows (row strides and head_dim multiples of 8 bf16 / 4 fp32 elements)
-bool attn_tiny_ok(int dtype, int64_t ld_qkv, int64_t ld_out, int B, int N, int H, int hd) {
-    const int E = dtype == ME_BF16 ? 8 : 4;
-    return (dtype == ME_BF16 || dtype == ME_F32) && N >= 1 && N <= 64 && hd >= E && hd <= 64 && hd % E == 0 && ld_qkv % E == 0 && ld_out % E == 0 &&
-           (int64_t)B * H < (1ll << 31);
+bool attn_tiny_ok(const AttnCall& c) {
+    const int E = c.dtype == ME_BF16 ? 8 : 4;
+    return (c.dtype == ME_BF16 || c.dtype == ME_F32) && c.N >= 1 && c.N <= 64 && c.hd >= E && c.hd <= 64 && c.hd % E == 0 && c.ld % E == 0 && c.ldo % E == 0 &&
+           (int64_t)c.B * c.H < (1ll << 31);
 }
 
-int launch_attn_tiny_fwd(int dtype, const void* qkv, int64_t ld, void* out, int64_t ldo, float* lse, int B, int N, int H, int hd, float scale,
-                         hipStream_t stream) {
-#define TINY_FWD(T_, HD_, NM_) return launch_fwd<T_, HD_, NM_>(qkv, ld, out, ldo, lse, B, N, H, hd, scale, stream)
-#define TINY_FWD_T(T_)                      \
-    do {                                    \
-        if (hd <= 32) {                     \
-            if (N <= 16) TINY_FWD(T_, 32, 16); \
-            if (N <= 32) TINY_FWD(T_, 32, 32); \
-            TINY_FWD(T_, 32, 64);           \
-        }                                   \
-        if (N <= 16) TINY_FWD(T_, 64, 16);  \
-        if (N <= 32) TINY_FWD(T_, 64, 32);  \
-        TINY_FWD(T_, 64, 64);               \
-    } while (0)
-    if (dtype == ME_BF16) TINY_FWD_T(bf16_t);
-    TINY_FWD_T(float);
-#undef TINY_FWD_T
-#undef TINY_FWD
-}
-
-int launch_attn_tiny_bwd(int dtype, const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dout, int64_t lddo, const float* lse,
-                         float* delta, void* dqkv, int64_t lddq, int B, int N, int H, int hd, float scale, hipStream_t stream) {
-#define TINY_BWD(T_, HD_, NM_) return launch_bwd<T_, HD_, NM_>(qkv, ld, out, ldo, dout, lddo, lse, delta, dqkv, lddq, B, N, H, hd, scale, stream)
-#define TINY_BWD_T(T_)                      \
-    do {                                    \
-        if (hd <= 32) {                     \
-            if (N <= 16) TINY_BWD(T_, 32, 16); \
-            if (N <= 32) TINY_BWD(T_, 32, 32); \
-            TINY_BWD(T_, 32, 64);           \
-        }                                   \
-        if (N <= 16) TINY_BWD(T_, 64, 16);  \
-        if (N <= 32) TINY_BWD(T_, 64, 32);  \
-        TINY_BWD(T_, 64, 64);               \
-    } while (0)
-    if (dtype == ME_BF16) TINY_BWD_T(bf16_t);
-    TINY_BWD_T(float);
-#undef TINY_BWD_T
-#undef TINY_BWD
-}
+int launch_attn_tiny(const AttnCall& c, bool backward) { return !backward ? launch_t<false>(c) : launch_t<true>(c); }

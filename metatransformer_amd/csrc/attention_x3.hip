@@ -755,6 +755,7 @@ extern "C" int me_attention_fwd_x3(const float* qkv, int64_t ld_qkv, float* out,
     const int64_t nwg = (int64_t)B * H * ((N + X3_QB - 1) / X3_QB);
     ME_CHECK_ARG(nwg < (int64_t)0x7fffffff, "me_attention_fwd_x3: too many workgroups");
     ME_CHECK_ARG((int64_t)N * ld_qkv < (int64_t)0x7fffffff, "me_attention_fwd_x3: N * ld_qkv must fit 31 bits (row offsets are 32-bit)");
+    prof.plan = ME_ATTN_X3;
     hipLaunchKernelGGL(attn_fwd_x3_kernel, dim3((unsigned)nwg), dim3(256), 0, stream, qkv, ld_qkv, out, ld_out, reinterpret_cast<uint16_t*>(out3), lse, N,
                        H, scale);
     ME_CHECK_LAUNCH("me_attention_fwd_x3");
@@ -779,6 +780,7 @@ extern "C" int me_attention_bwd_x3(const float* qkv, int64_t ld_qkv, const float
     ME_CHECK_ARG((int64_t)N * ld_qkv < (int64_t)0x7fffffff && (int64_t)N * ld_dout < (int64_t)0x7fffffff, "me_attention_bwd_x3: N * ld must fit 31 bits");
     const int64_t nwg = (int64_t)B * H * ((N + X3_QB - 1) / X3_QB);
     ME_CHECK_ARG(nwg < (int64_t)0x7fffffff, "me_attention_bwd_x3: too many workgroups");
+    prof.plan = ME_ATTN_X3;
     static OncePerDevice once;
     if (once.need()) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS_DQ);

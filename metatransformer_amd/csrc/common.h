@@ -59,6 +59,17 @@ struct OncePerDevice {
     }
 };
 
+// CUs of the current device (the resident / persistent kernel forms launch one workgroup, or a few, per CU); asked once per translation unit
+static inline int device_cus() {
+    static int n = 0;
+    if (!n) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    }
+    return n;
+}
+
 // optional per-launch timing (me_gemm_profile_enable / _read, api.hip): brackets the launches an entry point makes with
 // HIP events on its stream while profiling is on; free when off.  op: ME_GEMM_NT / ME_GEMM_TN or an ME_PROF_* code.
 struct ProfScope {

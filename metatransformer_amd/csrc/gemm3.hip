@@ -1088,7 +1088,7 @@ bool g3_supported(const GemmParams& p, int op) {
     return true;
 }
 
-int g3_cu_count() { return g3_cus(); }
+int g3_cu_count() { return device_cus(); }
 
 // The one place that says which NT kernel a descriptor runs on.  The resident form (one workgroup per CU, operand stream running
 // through the epilogues) whenever one of its (EPI, PRE) instantiations covers the epilogue, every CU gets work and the output / row

@@ -611,15 +611,4 @@ __device__ __forceinline__ void g3_epilogue(const GemmParams& p, G3State& s, int
     }
 }
 
-// CUs of the current device (the resident / persistent forms launch one workgroup per CU)
-inline int g3_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    }
-    return n;
-}
-
 }  // namespace

@@ -374,6 +374,63 @@ def test_attention_persistent_kernels_fwd_bwd(dev, B, N, H, hd):
     assert torch.equal(dqkv, ops.attention_bwd(qkv.to(dev), out, do.to(dev), lse, B, N, H, hd, scale))
 
 
+# ---- which kernel form takes which call (csrc/attention.hip: attn_route; the ME_ATTN_* codes of include/metaenc.h).  The shape lists above
+# pick their kernels by N and head_dim alone; this pins the choice itself: both sides of every threshold, both head-width classes, the
+# two places where forward and backward differ on purpose (257 <= N <= 512 at head_dim 64), the 16- / 32-key dK / dV kernels of the
+# streaming backward (rows per block 176 / 208 -> 224 / 224), and what falls through to the generic kernels.
+GENERIC, TINY, RING16, RESIDENT, STREAM16, MID, CHUNK, DKDV32 = 1, 2, 3, 4, 5, 6, 7, 16
+# (N, head_dim, dtype, p_drop, B, H, forward form, backward form)
+ROUTE_CASES = [(64, 64, "bf16", 0.0, 2, 2, TINY, TINY), (64, 64, "fp32", 0.0, 2, 2, TINY, TINY), (65, 64, "bf16", 0.0, 2, 2, RING16, RING16),
+               (224, 64, "bf16", 0.0, 2, 2, RING16, RING16), (128, 24, "bf16", 0.0, 2, 2, RING16, RING16), (129, 40, "bf16", 0.0, 2, 2, RING16, RING16),
+               (225, 64, "bf16", 0.0, 2, 2, RESIDENT, RESIDENT), (256, 64, "bf16", 0.0, 2, 2, RESIDENT, RESIDENT),
+               (257, 64, "bf16", 0.0, 2, 2, STREAM16, MID), (512, 64, "bf16", 0.0, 2, 2, STREAM16, MID), (257, 32, "bf16", 0.0, 2, 2, MID, MID),
+               (300, 24, "bf16", 0.0, 2, 2, MID, MID), (513, 64, "bf16", 0.0, 2, 2, STREAM16, STREAM16), (700, 64, "bf16", 0.0, 2, 2, STREAM16, STREAM16),
+               (592, 64, "bf16", 0.0, 2, 2, STREAM16, STREAM16 | DKDV32), (1568, 64, "bf16", 0.0, 1, 1, STREAM16, STREAM16 | DKDV32),
+               (513, 32, "bf16", 0.0, 2, 2, CHUNK, CHUNK), (600, 24, "bf16", 0.0, 2, 2, CHUNK, CHUNK), (130, 128, "bf16", 0.0, 2, 2, GENERIC, GENERIC),
+               (64, 128, "bf16", 0.0, 2, 2, GENERIC, GENERIC), (65, 64, "fp32", 0.0, 2, 2, GENERIC, GENERIC),
+               (197, 64, "bf16", 0.1, 2, 2, GENERIC, GENERIC), (100, 24, "bf16", 0.1, 2, 2, GENERIC, GENERIC)]
+
+
+def _attention_plans(body):
+    """(op, plan) of the attention records `body` leaves in the library's launch profile"""
+    ops.gemm_profile(True)
+    try:
+        body()
+        recs = ops.gemm_profile_read(with_plan=True)
+    finally:
+        ops.gemm_profile(False)
+    return [(r[0], r[6]) for r in recs if r[0] in (_capi.ME_PROF_ATTN_FWD, _capi.ME_PROF_ATTN_BWD)]
+
+
+@pytest.mark.parametrize("N,hd,dt,p_drop,B,H,fwd,bwd", ROUTE_CASES)
+def test_attention_route(dev, N, hd, dt, p_drop, B, H, fwd, bwd):
+    dtype = torch.bfloat16 if dt == "bf16" else torch.float32
+    qkv = rnd(B * N, 3 * H * hd, seed=N).to(dtype).to(dev)
+    do = rnd(B * N, H * hd, seed=N + 1).to(dtype).to(dev)
+
+    def body():
+        out, lse = ops.attention_fwd(qkv, B, N, H, hd, hd ** -0.5, True, p_drop=p_drop, seed=3)
+        ops.attention_bwd(qkv, out, do, lse, B, N, H, hd, hd ** -0.5, p_drop=p_drop, seed=3)
+    assert _attention_plans(body) == [(_capi.ME_PROF_ATTN_FWD, fwd), (_capi.ME_PROF_ATTN_BWD, bwd)]
+
+
+def test_attention_route_padded_output_stride(dev):
+    """ld_out = C + 4 (the C entry; the Python wrapper passes dense strides): not a multiple of 8, so the forward at N = 300, head_dim 64
+    stays on the mid kernel where a dense output goes to the streaming one"""
+    B, N, H, hd = 2, 300, 2, 64
+    C = H * hd
+    qkv = rnd(B * N, 3 * C, seed=300).bfloat16().to(dev)
+    out = torch.zeros(B * N, C + 4, dtype=torch.bfloat16, device=dev)
+    lse = torch.empty(B, H, N, dtype=torch.float32, device=dev)
+
+    def body():
+        _capi.check(_capi.load().me_attention_fwd(_capi.ptr(qkv), 3 * C, _capi.ptr(out), C + 4, _capi.ptr(lse), B, N, H, hd, hd ** -0.5,
+                                                  _capi.ME_BF16, 0.0, 0, _capi.stream_ptr()), "me_attention_fwd")
+    assert _attention_plans(body) == [(_capi.ME_PROF_ATTN_FWD, MID)]
+    ref, _ = attn_ref(qkv.cpu(), B, N, H, hd, hd ** -0.5)
+    assert rel_err(out[:, :C].float(), ref) < 1.5e-2 and not bool(out[:, C:].any())
+
+
 @pytest.mark.parametrize("B,N,H,hd", [(32, 1568, 16, 64), (64, 592, 12, 64), (128, 512, 16, 64)])
 def test_attention_full_batch_of_configs_3_4_5(dev, B, N, H, hd):
     """the attention launches of BASELINE configs 5 / 4 / 3 at the batch bench.py runs them at (the CPU-oracle tests above cut the batch):

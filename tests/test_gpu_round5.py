@@ -268,6 +268,23 @@ def test_backward_3xbf16_every_gradient_vs_oracle(dev, B, N, depth):
         check_close(p.grad, 2 * first[k], 1e-5, f"accumulated d{k}")
 
 
+@pytest.mark.parametrize("N,forms", [(70, {8}), (64, {1, 2})], ids=["70_tokens", "64_tokens"])
+def test_3xbf16_block_attention_form(dev, N, forms):
+    """which attention an fp32 three-product Block with head_dim 64 runs (me_gemm_profile_rec.plan of its attention records): the
+    three-product kernels (form 8) above 64 tokens, the exact-fp32 kernels (tiny, 2, or generic, 1) up to 64 -- never form 8 there"""
+    enc = make_encoder(1, 256, 4, dev).train()
+    enc[0].compute_dtype = "fp32_3xbf16"
+    x = rnd(2, N, 256, seed=N).to(dev).requires_grad_(True)
+    ops.gemm_profile(True)
+    try:
+        enc(x).sum().backward()
+        recs = ops.gemm_profile_read(with_plan=True)
+    finally:
+        ops.gemm_profile(False)
+    attn = [(r[0], r[6]) for r in recs if r[0] in (_capi.ME_PROF_ATTN_FWD, _capi.ME_PROF_ATTN_BWD)]
+    assert [op for op, _ in attn] == [_capi.ME_PROF_ATTN_FWD, _capi.ME_PROF_ATTN_BWD] and all(plan in forms for _, plan in attn), attn
+
+
 def test_3xbf16_falls_back_to_exact_where_it_is_not_built(dev):
     """widths that are not multiples of 256, bf16 tokens and windowed blocks run the exact path (same results as fp32_mode='exact')"""
     enc = make_encoder(1, 192, 3, dev)

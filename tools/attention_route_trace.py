@@ -1,0 +1,86 @@
+"""Trace of the attention entry points (me_attention_fwd / me_attention_bwd) over every kernel form their route has, for comparing
+two commits: run it at each, the two outputs must be byte-identical.
+
+    python tools/attention_route_trace.py OUT                 # per case: sha256 of out, lse, dqkv
+    python tools/attention_route_trace.py --host-time [CALLS]  # wall time of CALLS (2000) back-to-back forward + backward calls
+
+It uses only names that both sides of such a comparison have: ops.attention_fwd / ops.attention_bwd, and the ctypes entry for the
+case with a padded output stride.  Under `rocprofv3 --kernel-trace -- python tools/attention_route_trace.py OUT` the kernel
+sequence (name, grid, workgroup, LDS bytes) is the record of which kernel each case took.  The cases are those of
+tests/test_gpu_ops.py::test_attention_route.  profiles/attention_route_equivalence.txt holds the record made with it."""
+import hashlib
+import sys
+import time
+
+import torch
+
+from metatransformer_amd import _capi, ops
+from metatransformer_amd._capi import check, dtype_code, ptr, stream_ptr
+
+dev = torch.device("cuda", 0)
+# (N, head_dim, dtype, p_drop, B, H)
+CASES = [(64, 64, "bf16", 0.0, 2, 2), (64, 64, "fp32", 0.0, 2, 2), (65, 64, "bf16", 0.0, 2, 2), (224, 64, "bf16", 0.0, 2, 2),
+         (128, 24, "bf16", 0.0, 2, 2), (129, 40, "bf16", 0.0, 2, 2), (225, 64, "bf16", 0.0, 2, 2), (256, 64, "bf16", 0.0, 2, 2),
+         (257, 64, "bf16", 0.0, 2, 2), (512, 64, "bf16", 0.0, 2, 2), (257, 32, "bf16", 0.0, 2, 2), (300, 24, "bf16", 0.0, 2, 2),
+         (513, 64, "bf16", 0.0, 2, 2), (700, 64, "bf16", 0.0, 2, 2), (592, 64, "bf16", 0.0, 2, 2), (1568, 64, "bf16", 0.0, 1, 1),
+         (513, 32, "bf16", 0.0, 2, 2), (600, 24, "bf16", 0.0, 2, 2), (130, 128, "bf16", 0.0, 2, 2), (64, 128, "bf16", 0.0, 2, 2),
+         (65, 64, "fp32", 0.0, 2, 2), (197, 64, "bf16", 0.1, 2, 2), (100, 24, "bf16", 0.1, 2, 2)]
+DT = {"bf16": torch.bfloat16, "fp32": torch.float32}
+
+
+def sha(t):
+    t = t.detach().contiguous()
+    return f"{str(t.dtype)[6:]}{list(t.shape)} " + hashlib.sha256(t.view(torch.uint8).cpu().numpy().tobytes()).hexdigest()
+
+
+def inputs(B, N, H, hd, dt, seed):
+    g = torch.Generator().manual_seed(seed)
+    qkv = torch.randn(B * N, 3 * H * hd, generator=g).to(dev, DT[dt])
+    dout = torch.randn(B * N, H * hd, generator=g).to(dev, DT[dt])
+    return qkv, dout
+
+
+def trace(path):
+    out_f = open(path, "w")
+    for i, (N, hd, dt, p, B, H) in enumerate(CASES):
+        qkv, dout = inputs(B, N, H, hd, dt, 100 + i)
+        scale = hd ** -0.5
+        out, lse = ops.attention_fwd(qkv, B, N, H, hd, scale, True, p_drop=p, seed=7)
+        dqkv = ops.attention_bwd(qkv, out, dout, lse, B, N, H, hd, scale, p_drop=p, seed=7)
+        torch.cuda.synchronize()
+        out_f.write(f"== N={N} hd={hd} {dt} p_drop={p} B={B} H={H}\n  out: {sha(out)}\n  lse: {sha(lse)}\n  dqkv: {sha(dqkv)}\n")
+    # forward with ld_out = C + 4 (the Python wrappers always pass dense strides): the ctypes entry
+    B, N, H, hd = 2, 300, 2, 64
+    C = H * hd
+    qkv, _ = inputs(B, N, H, hd, "bf16", 200)
+    out = torch.zeros(B * N, C + 4, dtype=torch.bfloat16, device=dev)
+    lse = torch.empty(B, H, N, dtype=torch.float32, device=dev)
+    check(_capi.load().me_attention_fwd(ptr(qkv), 3 * C, ptr(out), C + 4, ptr(lse), B, N, H, hd, hd ** -0.5, dtype_code(torch.bfloat16), 0.0, 0,
+                                        stream_ptr()), "me_attention_fwd")
+    torch.cuda.synchronize()
+    out_f.write(f"== N={N} hd={hd} bf16 ld_out=C+4 B={B} H={H} (forward only)\n  out: {sha(out)}\n  lse: {sha(lse)}\n")
+    out_f.close()
+
+
+def host_time(calls):
+    B, N, H, hd = 1, 16, 4, 64
+    qkv, dout = inputs(B, N, H, hd, "bf16", 1)
+    scale = hd ** -0.5
+    for n in (200, calls):                    # warm-up, then the timed run
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            out, lse = ops.attention_fwd(qkv, B, N, H, hd, scale, True)
+            ops.attention_bwd(qkv, out, dout, lse, B, N, H, hd, scale)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+    print(f"host-time: {calls} x (attention_fwd + attention_bwd) at B=1 N=16 H=4 hd=64 bf16: {dt * 1e3:.2f} ms ({dt / calls * 1e6:.2f} us per pair)")
+
+
+if __name__ == "__main__":
+    if len(sys.argv) < 2:
+        sys.exit(__doc__)
+    if sys.argv[1] == "--host-time":
+        host_time(int(sys.argv[2]) if len(sys.argv) > 2 else 2000)
+    else:
+        trace(sys.argv[1])
