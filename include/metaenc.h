@@ -221,6 +221,7 @@ enum { ME_ATTN_GENERIC = 1,    /* tiled 128-query x 64-key kernels: fp32, head_d
        ME_ATTN_MID = 6,        /* 256 < N <= 512: one workgroup per (batch, head) */
        ME_ATTN_CHUNK = 7,      /* N > 512: 256-row chunks */
        ME_ATTN_X3 = 8,         /* me_attention_fwd_x3 / _bwd_x3 */
+       ME_ATTN_QKV = 9,        /* me_attention_qkv_fwd / _bwd: separate Q / K / V, two lengths, causal (attention_qkv.hip) */
        ME_ATTN_DKDV32 = 16     /* bit 4, on an ME_ATTN_STREAM16 backward record: dK / dV ran on the 32-key kernel */ };
 int me_gemm_profile_enable(int on);
 int me_gemm_profile_read(me_gemm_profile_rec* out, int max);
@@ -253,6 +254,37 @@ int me_attention_bwd(const void* qkv, int64_t ld_qkv, const void* out, int64_t l
                      const void* dout, int64_t ld_dout, const float* lse, float* delta,
                      void* dqkv, int64_t ld_dqkv,
                      int B, int N, int H, int head_dim, float scale, int dtype, float p_drop, uint64_t seed, void* stream);
+
+/* ------------------------------------------------------------------ Attention over separate Q, K and V (decoder side)
+ * Replaces FullAttention.forward and the head reshapes of AttentionLayer (Time-Series/layers/SelfAttention_Family.py:56-75,195-211):
+ * P = softmax(scale * Q K^T), out = P V, for Nq queries against Nk keys.  q, k and v each have their own pointer and row stride
+ * (elements); head h is columns [h*hd, (h+1)*hd) from each pointer, batch item b is rows [b*Nq, (b+1)*Nq) of q / out and
+ * [b*Nk, (b+1)*Nk) of k / v.  So one call reads Q from a [B*Nq, C] projection and K, V from one packed [B*Nk, 2C] GEMM output
+ * (k = base, v = base + C, ld_k = ld_v = 2C), or all three from a packed [B*N, 3C] -- no permute or copy in between.
+ * out is [B*Nq, H*hd] (row stride ld_out), lse [B, H, Nq] fp32 (forward: may be NULL).
+ * causal = 1: key j is visible to query i iff j <= i (TriangularCausalMask, utils/masking.py:4-8); needs Nq == Nk (ME_ERR_ARG otherwise).
+ * p_drop > 0: dropout on the normalised probabilities, kept values scaled by 1/(1 - p_drop); the mask is the counter hash of me_attention_fwd
+ * at index ((b*H + h)*Nq + q)*Nk + k, regenerated by the backward from the same p_drop / seed.
+ * dtype ME_F32 (exact-fp32 MFMA) or ME_BF16; head_dim a multiple of 4 (fp32) / 8 (bf16), at most 128; the operand strides multiples
+ * of the same, the output strides multiples of 4, every pointer 16-byte aligned; B, H <= 65535.
+ * Backward: dout [B*Nq, H*hd], delta [B, H, Nq] fp32 scratch, dq / dk / dv laid out like q / k / v with their own strides (they may
+ * point into one packed gradient buffer).  Every gradient element is written exactly once, no atomics: two runs are bit-identical. */
+typedef struct me_attn_qkv_desc {
+    const void* q; const void* k; const void* v;
+    int64_t ld_q, ld_k, ld_v;
+    void* out; int64_t ld_out;            /* (the ME_F32 backward reads it: delta = dO . O; ME_BF16 forms delta from the tiles) */
+    float* lse;                           /* (backward reads it) */
+    const void* dout; int64_t ld_dout;    /* from here to ld_dv: backward only */
+    float* delta;
+    void* dq; void* dk; void* dv;
+    int64_t ld_dq, ld_dk, ld_dv;
+    uint64_t seed;
+    int32_t B, Nq, Nk, H, head_dim;
+    int32_t dtype, causal;
+    float scale, p_drop;
+} me_attn_qkv_desc;
+int me_attention_qkv_fwd(const me_attn_qkv_desc* d, void* stream);
+int me_attention_qkv_bwd(const me_attn_qkv_desc* d, void* stream);
 
 /* fp8 (OCP e4m3) forward for long sequences -- BASELINE config 5 (Large video tokens [32, 1568, 1024]).  Same contract as
  * me_attention_fwd (math of Video/models/modeling_finetune.py:172-195) for bf16 qkv / out and head_dim 64, with Q, K, V and

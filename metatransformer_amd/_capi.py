@@ -81,6 +81,17 @@ class GraphDesc(ctypes.Structure):
                 + [(n, c_int32) for n in ("B", "T", "C", "Fn", "Fe", "Sn", "Se", "max_n", "atom_rows", "edge_rows")])
 
 
+class AttnQkvDesc(ctypes.Structure):
+    """Mirror of ``struct me_attn_qkv_desc`` (include/metaenc.h)."""
+    _fields_ = ([("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("ld_q", c_int64), ("ld_k", c_int64), ("ld_v", c_int64),
+                 ("out", c_void_p), ("ld_out", c_int64), ("lse", c_void_p),
+                 ("dout", c_void_p), ("ld_dout", c_int64), ("delta", c_void_p),
+                 ("dq", c_void_p), ("dk", c_void_p), ("dv", c_void_p), ("ld_dq", c_int64), ("ld_dk", c_int64), ("ld_dv", c_int64),
+                 ("seed", ctypes.c_uint64)]
+                + [(n, c_int32) for n in ("B", "Nq", "Nk", "H", "head_dim", "dtype", "causal")]
+                + [("scale", c_float), ("p_drop", c_float)])
+
+
 class GemmProfileRec(ctypes.Structure):
     """Mirror of ``struct me_gemm_profile_rec``."""
     _fields_ = [("op", c_int32), ("ab_dtype", c_int32), ("M", c_int64), ("N", c_int64), ("K", c_int64), ("ms", c_float),
@@ -163,6 +174,8 @@ SIGNATURES = {
     "me_attention_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                  c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_int, c_float, ctypes.c_uint64,
                                  c_void_p]),
+    "me_attention_qkv_fwd": (c_int, [POINTER(AttnQkvDesc), c_void_p]),
+    "me_attention_qkv_bwd": (c_int, [POINTER(AttnQkvDesc), c_void_p]),
     "me_attention_fp8_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "me_attention_fwd_fp8": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                      c_void_p, c_size_t, c_void_p]),

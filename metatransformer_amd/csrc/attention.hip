@@ -14,192 +14,12 @@
 // V^T with the same permutation (common.h: any assignment works if A and B agree).
 // fp32 runs the same code on the exact-fp32 MFMA (parity mode); bf16 is the performance mode.
 #include "attention_host.h"
+#include "attention_tile.h"
 #include <math.h>
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
-
-constexpr int AT_THREADS = 256;
-constexpr int KVT = 64;      // keys per LDS tile
-constexpr int QPB = 128;     // queries per block (32 per wave)
-
-template <typename T, int HD> struct Cfg {
-    static constexpr int E = 16 / sizeof(T);
-    static constexpr int CPR = HD / E;                       // 16-byte chunks per row along d
-    static constexpr int NKK = HD / (2 * E);                 // chunk pairs along d
-    static constexpr int NDB = HD / 32;                      // 32-wide d blocks
-    static constexpr int RROW = HD * sizeof(T) + 16;         // row-major tile row stride (bytes), conflict-free pad
-    static constexpr int TROW = KVT * sizeof(T) + (sizeof(T) == 2 ? 8 : 16);   // transposed tile row stride
-    static constexpr int R_BYTES = KVT * RROW;               // [64][HD] row-major tile
-    static constexpr int T_BYTES = HD * TROW;                // [HD][64] transposed tile
-    static constexpr int NPC = KVT / (2 * E);                // P chunks per 64-key tile (4 bf16 / 8 fp32)
-    static constexpr int R_ITEMS = (KVT * CPR + AT_THREADS - 1) / AT_THREADS;
-    static constexpr int T_ITEMS = sizeof(T) == 2 ? ((KVT / 2) * CPR + AT_THREADS - 1) / AT_THREADS
-                                                  : (KVT * CPR + AT_THREADS - 1) / AT_THREADS;
-    static constexpr int T_REGS = sizeof(T) == 2 ? 2 * T_ITEMS : T_ITEMS;
-};
-
-__device__ __forceinline__ u32x4 zero4() { return u32x4{0u, 0u, 0u, 0u}; }
-
-// ---- row-major [64][HD] tile: global -> regs -> LDS
-template <typename T, int HD> struct RowStage {
-    typedef Cfg<T, HD> C;
-    u32x4 v[C::R_ITEMS];
-    __device__ __forceinline__ void load(const T* __restrict__ base, int64_t ld, int r0, int nrows, int hd, int tid) {
-#pragma unroll
-        for (int i = 0; i < C::R_ITEMS; ++i) {
-            const int it = tid + AT_THREADS * i;
-            const int chunk = it % C::CPR, row = it / C::CPR;
-            const bool ok = (row < KVT) && (r0 + row < nrows) && (chunk * C::E < hd);
-            v[i] = ok ? *reinterpret_cast<const u32x4*>(base + (int64_t)(r0 + row) * ld + chunk * C::E) : zero4();
-        }
-    }
-    __device__ __forceinline__ void store(char* lds, int tid) const {
-#pragma unroll
-        for (int i = 0; i < C::R_ITEMS; ++i) {
-            const int it = tid + AT_THREADS * i;
-            const int chunk = it % C::CPR, row = it / C::CPR;
-            if (row < KVT) *reinterpret_cast<u32x4*>(lds + row * C::RROW + chunk * 16) = v[i];
-        }
-    }
-};
-
-// ---- transposed [HD][64] tile (rows = d, 64 keys/queries contiguous): global -> regs -> LDS
-template <typename T, int HD> struct TransStage;
-template <int HD> struct TransStage<bf16_t, HD> {
-    typedef Cfg<bf16_t, HD> C;
-    u32x4 v[C::T_REGS];
-    __device__ __forceinline__ void load(const bf16_t* __restrict__ base, int64_t ld, int r0, int nrows, int hd, int tid) {
-#pragma unroll
-        for (int i = 0; i < C::T_ITEMS; ++i) {
-            const int it = tid + AT_THREADS * i;
-            const int chunk = it % C::CPR, p = it / C::CPR;
-            const int row = r0 + 2 * p;
-            const bool okc = (p < KVT / 2) && (chunk * 8 < hd);
-            v[2 * i] = (okc && row < nrows) ? *reinterpret_cast<const u32x4*>(base + (int64_t)row * ld + chunk * 8) : zero4();
-            v[2 * i + 1] = (okc && row + 1 < nrows) ? *reinterpret_cast<const u32x4*>(base + (int64_t)(row + 1) * ld + chunk * 8) : zero4();
-        }
-    }
-    __device__ __forceinline__ void store(char* lds, int tid) const {
-#pragma unroll
-        for (int i = 0; i < C::T_ITEMS; ++i) {
-            const int it = tid + AT_THREADS * i;
-            const int chunk = it % C::CPR, p = it / C::CPR;
-            if (p < KVT / 2) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const uint32_t w0 = v[2 * i][e >> 1], w1 = v[2 * i + 1][e >> 1];
-                    const uint32_t lo = (e & 1) ? (w0 >> 16) : (w0 & 0xffffu);
-                    const uint32_t hi = (e & 1) ? (w1 & 0xffff0000u) : (w1 << 16);
-                    *reinterpret_cast<uint32_t*>(lds + (chunk * 8 + e) * C::TROW + p * 4) = lo | hi;
-                }
-            }
-        }
-    }
-};
-template <int HD> struct TransStage<float, HD> {
-    typedef Cfg<float, HD> C;
-    u32x4 v[C::T_REGS];
-    __device__ __forceinline__ void load(const float* __restrict__ base, int64_t ld, int r0, int nrows, int hd, int tid) {
-#pragma unroll
-        for (int i = 0; i < C::T_ITEMS; ++i) {
-            const int it = tid + AT_THREADS * i;
-            const int chunk = it % C::CPR, row = it / C::CPR;
-            const bool ok = (row < KVT) && (r0 + row < nrows) && (chunk * 4 < hd);
-            v[i] = ok ? *reinterpret_cast<const u32x4*>(base + (int64_t)(r0 + row) * ld + chunk * 4) : zero4();
-        }
-    }
-    __device__ __forceinline__ void store(char* lds, int tid) const {
-#pragma unroll
-        for (int i = 0; i < C::T_ITEMS; ++i) {
-            const int it = tid + AT_THREADS * i;
-            const int chunk = it % C::CPR, row = it / C::CPR;
-            if (row < KVT) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    *reinterpret_cast<uint32_t*>(lds + (chunk * 4 + e) * C::TROW + row * 4) = v[i][e];
-            }
-        }
-    }
-};
-
-// A-operand chunk from a row-major tile: row, d-chunk index (2*kk + h)
-template <typename T, int HD>
-__device__ __forceinline__ typename Chunk<T>::type rtile_chunk(const char* lds, int row, int chunk) {
-    return *reinterpret_cast<const typename Chunk<T>::type*>(lds + row * Cfg<T, HD>::RROW + chunk * 16);
-}
-// A-operand chunk from a transposed tile: row d, P-chunk c (0..NPC-1) of the 64-wide tile, half h.
-// Element e of the chunk is reduction index (within the 64-tile):
-//   bf16: 16c + 4h + (e&3) + 8(e>>2)        fp32: 8c + 4h + e
-// which is exactly the index that accumulator register (E*(c % (NPC/2)) + e) of 32-subtile u = c / (NPC/2)
-// holds in half h (acc_row), so S/P registers feed the next MFMA without any cross-lane movement.
-template <int HD>
-__device__ __forceinline__ bf16x8 ttile_chunk(const bf16_t*, const char* lds, int d, int c, int h) {
-    const char* base = lds + d * Cfg<bf16_t, HD>::TROW;
-    union { u32x2 w[2]; bf16x8 b; } u;
-    u.w[0] = *reinterpret_cast<const u32x2*>(base + (16 * c + 4 * h) * 2);
-    u.w[1] = *reinterpret_cast<const u32x2*>(base + (16 * c + 8 + 4 * h) * 2);
-    return u.b;
-}
-template <int HD>
-__device__ __forceinline__ f32x4 ttile_chunk(const float*, const char* lds, int d, int c, int h) {
-    return *reinterpret_cast<const f32x4*>(lds + d * Cfg<float, HD>::TROW + (8 * c + 4 * h) * 4);
-}
-// bf16: the same operand straight from a ROW-MAJOR [64][HD] tile with the LDS transpose read (ds_read_b64_tr_b16),
-// no transposed staging at all.  A 16-lane group reads four reduction rows x 16 columns; lane p of the group supplies
-// the address of row +(p>>2), columns +4*(p&3) and receives column +p of the four rows (tools/probe_isa.hip).  Rows are
-// picked so that element e = 4r + j of half h is reduction index 16c + 8r + 4h + j == the accumulator-register mapping
-// above, so P / dS registers still feed the MFMA unchanged.
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_t;
-template <int HD>
-__device__ __forceinline__ bf16x8 tr_chunk(const char* tile, int dbase, int c, int lane) {
-    const int g = lane >> 4, p = lane & 15, h = g >> 1;
-    const int col = dbase + 16 * (g & 1) + 4 * (p & 3);
-    const uint32_t base = (uint32_t)(uintptr_t)tile + col * 2;
-    union { bf16x4 q[2]; bf16x8 v; } u;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int row = 16 * c + 8 * r + 4 * h + (p >> 2);
-        u.q[r] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(base + row * Cfg<bf16_t, HD>::RROW));
-    }
-    return u.v;
-}
-// "operand with the reduction index along the tile rows": fp32 -> transposed tile + 16-byte reads, bf16 -> row tile + tr reads
-template <typename T, int HD> struct TRead;
-template <int HD> struct TRead<float, HD> {
-    static constexpr bool kNeedsTransposedTile = true;
-    static __device__ __forceinline__ f32x4 chunk(const char* ttile, const char*, int db, int c, int lane) {
-        return ttile_chunk<HD>((const float*)nullptr, ttile, 32 * db + (lane & 31), c, lane >> 5);
-    }
-};
-template <int HD> struct TRead<bf16_t, HD> {
-    static constexpr bool kNeedsTransposedTile = false;
-    static __device__ __forceinline__ bf16x8 chunk(const char*, const char* rtile, int db, int c, int lane) {
-        return tr_chunk<HD>(rtile, 32 * db, c, lane);
-    }
-};
-
-// B-operand chunk c from the two 32x32 accumulators of a 64-wide tile
-__device__ __forceinline__ bf16x8 pack_chunk(const bf16_t*, const f32x16 (&s)[2], int c) {
-    const int u = c >> 1, o = (c & 1) * 8;
-    bf16x8 r;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (bf16_t)s[u][o + e];
-    return r;
-}
-__device__ __forceinline__ f32x4 pack_chunk(const float*, const f32x16 (&s)[2], int c) {
-    const int u = c >> 2, o = (c & 3) * 4;
-    return f32x4{s[u][o], s[u][o + 1], s[u][o + 2], s[u][o + 3]};
-}
-
-template <typename T> __device__ __forceinline__ void store_quad(T* p, f32x4 v);
-template <> __device__ __forceinline__ void store_quad<float>(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-template <> __device__ __forceinline__ void store_quad<bf16_t>(bf16_t* p, f32x4 v) {
-    bf16x4 o;
-    o[0] = (bf16_t)v[0]; o[1] = (bf16_t)v[1]; o[2] = (bf16_t)v[2]; o[3] = (bf16_t)v[3];
-    *reinterpret_cast<bf16x4*>(p) = o;
-}
 
 // =====================================================================================================
 // forward
@@ -337,49 +157,6 @@ __global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(const T* __restric
 // Two kernels, no atomics: (1) dK/dV: a wave owns 32 keys, walks query tiles; (2) dQ: a wave owns 32 queries,
 // walks key tiles (recomputing S and dP).
 // =====================================================================================================
-__global__ __launch_bounds__(256) void attn_delta_kernel(const void* __restrict__ o, int64_t ldo,
-                                                         const void* __restrict__ dout, int64_t lddo, int dt,
-                                                         float* __restrict__ delta, int N, int H, int hd, int64_t rows) {
-    // one wave per (token row, head)
-    const int lane = threadIdx.x & 63;
-    const int64_t gw = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (gw >= rows * H) return;
-    const int64_t row = gw / H;
-    const int head = (int)(gw % H);
-    float s = 0.f;
-    for (int d = lane; d < hd; d += 64)
-        s += load1_as_f32(o, dt, row * ldo + head * hd + d) * load1_as_f32(dout, dt, row * lddo + head * hd + d);
-    s = wave_sum(s);
-    if (lane == 0) {
-        const int64_t b = row / N, n = row % N;
-        delta[(b * H + head) * N + n] = s;
-    }
-}
-
-// vector path for bf16 with head_dim a power-of-two multiple of 8 (<= 512): one wave per token row, a lane owns 8
-// consecutive channels (16-byte loads of O and dO), the head_dim/8 lanes of a head fold with xor-shuffles.
-__global__ __launch_bounds__(256) void attn_delta_vec_kernel(const bf16_t* __restrict__ o, int64_t ldo,
-                                                             const bf16_t* __restrict__ dout, int64_t lddo,
-                                                             float* __restrict__ delta, int N, int H, int hd, int64_t rows) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int C8 = (H * hd) / 8, lph = hd / 8;      // chunks per row, lanes per head
-    const int64_t b = row / N, n = row % N;
-    for (int c = lane; c < ((C8 + 63) / 64) * 64; c += 64) {
-        float s = 0.f;
-        if (c < C8) {
-            const u32x4 ro = *reinterpret_cast<const u32x4*>(o + row * ldo + c * 8);
-            const u32x4 rd = *reinterpret_cast<const u32x4*>(dout + row * lddo + c * 8);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                s += __uint_as_float(ro[e] << 16) * __uint_as_float(rd[e] << 16) +
-                     __uint_as_float(ro[e] & 0xffff0000u) * __uint_as_float(rd[e] & 0xffff0000u);
-        }
-        for (int off = 1; off < lph; off <<= 1) s += __shfl_xor(s, off, 64);
-        if (c < C8 && (c % lph) == 0) delta[(b * H + c / lph) * N + n] = s;
-    }
-}
 
 // ---- dK / dV
 template <typename T, int HD>

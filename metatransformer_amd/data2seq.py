@@ -9,7 +9,9 @@ modalities whose tokenizers are on the north-star path (SURVEY.md 8a rows a12-a1
                construction is Audio/src/models/ast_models.py:86, which this follows)
   video        Video/models/modeling_finetune.py:263-297  Conv3d(3, C, k=s=(2,16,16)) tubelets
                (Data2Seq/Video.py is broken in the reference)
-  time-series  Data2Seq/Time_Series.py:109-126  Conv1d k3 circular + sinusoid PE + temporal-embedding gathers
+  time-series  Data2Seq/Time_Series.py:109-126  Conv1d k3 circular + sinusoid PE + temporal-embedding gathers (embed_type='fixed'), or
+               + Linear on float time features (embed_type='timeF', Time-Series/layers/Embed.py:96-106: what Time-Series/run.py
+               defaults to); the decoder side of that recipe is timeseries.py
   graph        Data2Seq/Graph.py:43-305      TokenGT GraphFeatureTokenizer: node / edge embedding sums, node identifiers, type id
                -> one GEMM over the node rows + one assembly kernel (graph preprocessing -- Laplacian eigenvectors, the
                collator -- stays with the caller)
@@ -234,20 +236,35 @@ class _PosEmb(nn.Module):
         self.register_buffer("pe", sinusoid_table(max_len, d_model).unsqueeze(0))
 
 
+class _TimeFeature(nn.Module):
+    """TimeFeatureEmbedding (Time-Series/layers/Embed.py:96-106): Linear(d_inp, d_model, bias=False) on float time features"""
+    D_INP = {"h": 4, "t": 5, "s": 6, "m": 1, "a": 1, "w": 2, "d": 3, "b": 3}      # features per time stamp, by sampling frequency
+
+    def __init__(self, d_model, freq="h"):
+        super().__init__()
+        if freq not in self.D_INP:
+            raise MetaEncError(f"DataEmbedding(embed_type='timeF'): unknown freq {freq!r} (one of {sorted(self.D_INP)})")
+        self.embed = nn.Linear(self.D_INP[freq], d_model, bias=False)
+
+
 class DataEmbedding(nn.Module):
-    """Time-series DataEmbedding -- Data2Seq/Time_Series.py:109-126 (``embed_type='fixed'``).
-    forward(x [B,L,c_in], x_mark [B,L,4|5] or None) -> [B,L,C].  The three terms (circular Conv1d k3, temporal
-    table gathers indexed by ``x_mark.long()``, positional slice ``pe[:, :L]``) are one fused kernel; the gathers
-    are integer-indexed and bit-exact.  Dropout(p=0.1) is identity in eval; training-mode dropout is applied by
-    the caller's nn.Dropout if wanted."""
+    """Time-series DataEmbedding -- Data2Seq/Time_Series.py:109-126 / Time-Series/layers/Embed.py:109-126.
+    forward(x [B,L,c_in], x_mark or None) -> [B,L,C].
+    ``embed_type='fixed'`` (x_mark [B,L,4|5] calendar indices): the three terms (circular Conv1d k3, temporal table gathers indexed by
+    ``x_mark.long()``, positional slice ``pe[:, :L]``) are one fused kernel; the gathers are integer-indexed and bit-exact.
+    ``embed_type='timeF'`` (x_mark [B,L,d_inp] float time features, d_inp by ``freq``; the Time-Series recipes' default): the same
+    kernel forms the value and positional terms, the temporal term ``embed(x_mark)`` is a GEMM on features and weight zero-padded to 8
+    columns with that embedding as its fused residual.  Gradients go to the Conv1d weight and to ``temporal_embedding.embed.weight``.
+    Dropout(p) is applied in training mode (me_dropout_add, one int64 seed per call from torch's CPU generator), identity in eval."""
 
     def __init__(self, c_in, d_model, embed_type="fixed", freq="h", dropout=0.1):
         super().__init__()
-        if embed_type != "fixed":
-            raise MetaEncError("only embed_type='fixed' (the reference default) is implemented")
+        if embed_type not in ("fixed", "timeF"):
+            raise MetaEncError("embed_type must be 'fixed' (the Data2Seq default) or 'timeF' (the Time-Series recipes' default)")
+        self.embed_type = embed_type
         self.value_embedding = _TokenConv(c_in, d_model)
         self.position_embedding = _PosEmb(d_model)
-        self.temporal_embedding = _Temporal(d_model, freq)
+        self.temporal_embedding = _Temporal(d_model, freq) if embed_type == "fixed" else _TimeFeature(d_model, freq)
         self.dropout = nn.Dropout(p=dropout)
         self.d_model = d_model
 
@@ -262,7 +279,14 @@ class DataEmbedding(nn.Module):
         if L > pe.shape[0]:
             raise MetaEncError(f"sequence length {L} exceeds positional table {pe.shape[0]}")
         marks, tabs = None, []
-        if x_mark is not None:
+        timef = self.embed_type == "timeF"
+        if x_mark is not None and timef:
+            d_inp = self.temporal_embedding.embed.in_features
+            if x_mark.dim() != 3 or tuple(x_mark.shape[:2]) != (B, L) or x_mark.shape[-1] != d_inp:
+                raise MetaEncError(f"x_mark must be [B, L, {d_inp}] time features for this freq, got {tuple(x_mark.shape)}")
+            if x_mark.device != x.device:
+                raise MetaEncError(f"x_mark is on {x_mark.device}, the series on {x.device}: move it first (no implicit copies)")
+        elif x_mark is not None:
             tabs = [t.detach().float().contiguous() for t in self.temporal_embedding.tables()]
             if x_mark.shape[-1] < len(tabs):
                 raise MetaEncError(f"x_mark has {x_mark.shape[-1]} columns, need {len(tabs)}")
@@ -276,6 +300,14 @@ class DataEmbedding(nn.Module):
         out_dtype = torch.bfloat16 if acast in (torch.bfloat16, torch.float16) else torch.float32      # fp16: bf16 compute, cast out
         p = float(self.dropout.p) if self.training else 0.0
         seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p > 0 else 0
+        if timef:      # value + positional from the fused kernel, + embed(x_mark) by a GEMM with that as residual, then the dropout
+            y = _TSEmbedFn.apply(x.detach().float().contiguous(), self.value_embedding.tokenConv.weight, None, [], pe.contiguous(), out_dtype,
+                                 0.0, 0)
+            if x_mark is not None:
+                y = _TimeFeatFn.apply(x_mark.detach().float().reshape(B * L, -1), self.temporal_embedding.embed.weight, y)
+            if p > 0:
+                y = _DropoutFn.apply(y, L, p, seed)
+            return y.to(torch.float16) if acast == torch.float16 else y
         y = _TSEmbedFn.apply(x.detach().float().contiguous(), self.value_embedding.tokenConv.weight, marks, tabs,
                              pe.contiguous(), out_dtype, p, seed)
         return y.to(torch.float16) if acast == torch.float16 else y
@@ -328,6 +360,51 @@ class _TSEmbedFn(torch.autograd.Function):
         dw = ops.gemm(dy2, xu, op=_capi.ME_GEMM_TN, out_dtype=torch.float32)          # [C, ncols]
         dw = dw[:, :3 * cin].reshape(C, cin, 3).to(wdt)
         return (None, dw, None, None, None, None, None, None)
+
+
+class _TimeFeatFn(torch.autograd.Function):
+    """emb + feats W^T: the temporal term of DataEmbedding(embed_type='timeF').  feats [M, d_inp] fp32 and W [C, d_inp] are zero-padded to 8
+    columns (one 16-byte bf16 row of the GEMM's operands); emb [B, L, C] is the GEMM's fused residual and fixes the compute dtype (bf16 under
+    autocast, exact fp32 otherwise).  Backward: dW = dY^T feats (TN GEMM), d emb = dY."""
+
+    @staticmethod
+    def forward(ctx, feats, weight, emb):
+        C, d_inp = weight.shape
+        cdt = emb.dtype
+        fc = F.pad(feats, (0, 8 - d_inp)).to(cdt).contiguous()
+        wc = F.pad(weight.detach().float(), (0, 8 - d_inp)).to(cdt).contiguous()
+        y = ops.gemm(fc, wc, residual=emb.reshape(-1, C).contiguous(), out_dtype=cdt)
+        ctx.save_for_backward(fc)
+        ctx.meta = (d_inp, weight.dtype, emb.shape)
+        return y.reshape(emb.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (fc,) = ctx.saved_tensors
+        d_inp, wdt, eshape = ctx.meta
+        dw = None
+        if ctx.needs_input_grad[1]:
+            d = ops.cast(dy.reshape(-1, eshape[-1]).contiguous(), fc.dtype)
+            M = d.shape[0]
+            if M % 8:      # the TN kernel wants the row count a multiple of 8: zero rows pad it
+                d = torch.cat([d, d.new_zeros(8 - M % 8, d.shape[1])])
+                fc = torch.cat([fc, fc.new_zeros(8 - M % 8, 8)])
+            dw = ops.gemm(d, fc, op=ME_GEMM_TN, out_dtype=torch.float32)[:, :d_inp].to(wdt)
+        return None, dw, dy if ctx.needs_input_grad[2] else None
+
+
+class _DropoutFn(torch.autograd.Function):
+    """nn.Dropout(p) in training mode on me_dropout_add; backward regenerates the mask from the seed"""
+
+    @staticmethod
+    def forward(ctx, x, rows_per_sample, p, seed):
+        ctx.meta = (rows_per_sample, p, seed)
+        return ops.dropout_add(x.contiguous(), None, rows_per_sample, p, 0.0, seed)
+
+    @staticmethod
+    def backward(ctx, dy):
+        rows_per_sample, p, seed = ctx.meta
+        return ops.dropout_add(dy.contiguous(), None, rows_per_sample, p, 0.0, seed), None, None, None
 
 
 class _NodeIdProjFn(torch.autograd.Function):

@@ -386,6 +386,73 @@ def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse:
     return dqkv
 
 
+def _qkv_operand(t: torch.Tensor, name: str, rows: int, C: int) -> torch.Tensor:
+    """an attention_qkv operand: a 2-D [rows, C] tensor or VIEW (columns of a packed projection), unit column stride"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise MetaEncError(f"{name}: expected a CUDA/ROCm tensor (libmetaenc has no CPU path)")
+    if t.dim() != 2 or tuple(t.shape) != (rows, C) or t.stride(1) != 1:
+        raise MetaEncError(f"{name}: expected a [{rows}, {C}] tensor or column view with unit column stride, got {tuple(t.shape)} "
+                           f"strides {tuple(t.stride())}")
+    return t
+
+
+def _attn_qkv_desc(q, k, v, B, Nq, Nk, H, hd, scale, causal, p_drop, seed) -> "_capi.AttnQkvDesc":
+    C = H * hd
+    _qkv_operand(q, "q", B * Nq, C); _qkv_operand(k, "k", B * Nk, C); _qkv_operand(v, "v", B * Nk, C)
+    if not (q.dtype == k.dtype == v.dtype):
+        raise MetaEncError(f"attention_qkv: operand dtypes differ ({q.dtype}, {k.dtype}, {v.dtype})")
+    d = _capi.AttnQkvDesc()
+    d.q, d.k, d.v = ptr(q), ptr(k), ptr(v)
+    d.ld_q, d.ld_k, d.ld_v = q.stride(0), k.stride(0), v.stride(0)
+    d.B, d.Nq, d.Nk, d.H, d.head_dim = B, Nq, Nk, H, hd
+    d.dtype, d.causal = dtype_code(q.dtype), 1 if causal else 0
+    d.scale, d.p_drop, d.seed = float(scale), float(p_drop), seed & 0xFFFFFFFFFFFFFFFF
+    return d
+
+
+def attention_qkv_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, Nq: int, Nk: int, H: int, hd: int, scale: float,
+                      causal: bool = False, need_lse: bool = False, p_drop: float = 0.0, seed: int = 0):
+    """softmax(scale * Q K^T [causal]) V over separate operands (me_attention_qkv_fwd): q [B*Nq, H*hd], k / v [B*Nk, H*hd], each a tensor
+    or a column view of a packed projection output (q = qkv[:, :C], k = kv[:, :C], v = kv[:, C:] ...) -- read in place through its row
+    stride.  -> (out [B*Nq, H*hd], lse [B, H, Nq] or None).  causal needs Nq == Nk; p_drop / seed as attention_fwd."""
+    lib = _capi.load()
+    d = _attn_qkv_desc(q, k, v, B, Nq, Nk, H, hd, scale, causal, p_drop, seed)
+    out = torch.empty((B * Nq, H * hd), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device) if need_lse else None
+    d.out, d.ld_out, d.lse = ptr(out), out.stride(0), ptr(lse)
+    check(lib.me_attention_qkv_fwd(ctypes.byref(d), stream_ptr()), "me_attention_qkv_fwd")
+    return out, lse
+
+
+def attention_qkv_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor,
+                      B: int, Nq: int, Nk: int, H: int, hd: int, scale: float, causal: bool = False, p_drop: float = 0.0, seed: int = 0,
+                      grads: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+    """backward of attention_qkv_fwd (me_attention_qkv_bwd) -> (dq, dk, dv).  grads: (dq, dk, dv) tensors or column views to write into --
+    e.g. the thirds of one packed [B*N, 3C] gradient, which the projection's dgrad / wgrad GEMMs then read as one operand; fresh dense
+    tensors otherwise.  Every element is written."""
+    lib = _capi.load()
+    C = H * hd
+    d = _attn_qkv_desc(q, k, v, B, Nq, Nk, H, hd, scale, causal, p_drop, seed)
+    _qkv_operand(out, "out", B * Nq, C); _qkv_operand(dout, "dout", B * Nq, C)
+    _req(lse, "lse")
+    if out.dtype != q.dtype or dout.dtype != q.dtype or lse.dtype != torch.float32 or tuple(lse.shape) != (B, H, Nq):
+        raise MetaEncError("attention_qkv_bwd: out / dout must have the operands' dtype, lse must be float32 [B, H, Nq]")
+    if grads is None:
+        grads = (torch.empty((B * Nq, C), dtype=q.dtype, device=q.device), torch.empty((B * Nk, C), dtype=q.dtype, device=q.device),
+                 torch.empty((B * Nk, C), dtype=q.dtype, device=q.device))
+    dq, dk, dv = grads
+    _qkv_operand(dq, "dq", B * Nq, C); _qkv_operand(dk, "dk", B * Nk, C); _qkv_operand(dv, "dv", B * Nk, C)
+    if not (dq.dtype == dk.dtype == dv.dtype == q.dtype):
+        raise MetaEncError("attention_qkv_bwd: gradient dtypes must equal the operands' dtype")
+    delta = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    d.out, d.ld_out, d.lse = ptr(out), out.stride(0), ptr(lse)
+    d.dout, d.ld_dout, d.delta = ptr(dout), dout.stride(0), ptr(delta)
+    d.dq, d.dk, d.dv = ptr(dq), ptr(dk), ptr(dv)
+    d.ld_dq, d.ld_dk, d.ld_dv = dq.stride(0), dk.stride(0), dv.stride(0)
+    check(lib.me_attention_qkv_bwd(ctypes.byref(d), stream_ptr()), "me_attention_qkv_bwd")
+    return dq, dk, dv
+
+
 # ----------------------------------------------------------------------------- element-wise
 
 def cast(x: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
