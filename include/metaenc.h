@@ -213,7 +213,7 @@ typedef struct me_gemm_profile_rec {
                         * Attention records (ME_PROF_ATTN_FWD / _BWD): the kernel form, one of ME_ATTN_* below.  Other records: 0 */
 } me_gemm_profile_rec;
 /* me_gemm_profile_rec.plan of an attention record: which kernel family ran the call (csrc/attention.hip: attn_route) */
-enum { ME_ATTN_GENERIC = 1,    /* tiled 128-query x 64-key kernels: fp32, head_dim > 64, dropout, and whatever no other form takes */
+enum { ME_ATTN_GENERIC = 1,    /* the tiled 128-query x 64-key kernels (attention_qkv.hip) on the packed qkv: fp32, head_dim > 64, dropout, and whatever no other form takes */
        ME_ATTN_TINY = 2,       /* N <= 64: one small workgroup per (batch, head), attention_tiny.hip (bf16 and fp32) */
        ME_ATTN_RING16 = 3,     /* 64 < N <= 224: the sequence resident in LDS, 16 waves of 16 rows */
        ME_ATTN_RESIDENT = 4,   /* up to N = 256: the sequence resident in LDS, 32 rows per wave (launch label "small") */

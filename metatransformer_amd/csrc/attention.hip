@@ -5,413 +5,18 @@
 // tiles of 64 keys are staged in LDS, the softmax runs online in registers, heads are addressed in place in
 // the [tokens, 3C] Linear output (no permute copy) and O is written head-major straight into [tokens, C].
 //
-// MFMA formulation (32x32 shapes, see common.h): every product is issued "transposed" so that the softmax
-// row (one query) lives in ONE lane (plus its partner lane^32):
-//   S^T[kv][q] = K Q^T           A = K rows (from LDS), B = Q rows (registers)      -> lane q, regs kv
-//   O^T[d][q] += V^T P^T         A = V^T rows d (LDS, transposed while staging), B = P (registers, in place)
-// The row max / row sum are 16-register reductions plus one xor-32 shuffle; the running rescale of O^T is a
-// per-lane scalar.  The reduction-index permutation the accumulator layout imposes on P is absorbed by reading
-// V^T with the same permutation (common.h: any assignment works if A and B agree).
-// fp32 runs the same code on the exact-fp32 MFMA (parity mode); bf16 is the performance mode.
+// This file: the entry points, the route (attn_route) and the kernel forms special to bf16 without dropout at head_dim <= 64.  What none
+// of them takes (ME_ATTN_GENERIC) runs on the tiled kernels of attention_qkv.hip, which also has the MFMA formulation all forms share.
 #include "attention_host.h"
 #include "attention_tile.h"
 #include <math.h>
 #include <stdlib.h>
-#include <type_traits>
 
 namespace {
 
 // =====================================================================================================
-// forward
-// =====================================================================================================
-template <typename T, int HD>
-__global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(const T* __restrict__ qkv, int64_t ld,
-                                                              T* __restrict__ out, int64_t ldo,
-                                                              float* __restrict__ lse, int N, int H, int hd,
-                                                              float scale, float p_drop, uint64_t seed) {
-    typedef Cfg<T, HD> C;
-    typedef typename Chunk<T>::type chunk_t;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr bool TT = TRead<T, HD>::kNeedsTransposedTile;
-    char* Ks = smem;
-    char* Vs = smem + C::R_BYTES;              // fp32: transposed [HD][64]; bf16: row-major [64][HD] (read with tr)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int b = blockIdx.z, head = blockIdx.y;
-    const int qbase = blockIdx.x * QPB + wave * 32;
-    const int Cdim = H * hd;
-    const T* qptr = qkv + (int64_t)b * N * ld + head * hd;
-    const T* kptr = qptr + Cdim;
-    const T* vptr = qptr + 2 * Cdim;
-
-    chunk_t qf[C::NKK];
-    {
-        const int qrow = (qbase + l31 < N) ? qbase + l31 : N - 1;
-#pragma unroll
-        for (int kk = 0; kk < C::NKK; ++kk) {
-            const int d = (2 * kk + h) * C::E;
-            u32x4 raw = (d < hd) ? *reinterpret_cast<const u32x4*>(qptr + (int64_t)qrow * ld + d) : zero4();
-            qf[kk] = *reinterpret_cast<chunk_t*>(&raw);
-        }
-    }
-    f32x16 o[C::NDB];
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
-    const bool active = qbase < N;      // wave-uniform
-    const int ntiles = (N + KVT - 1) / KVT;
-
-    RowStage<T, HD> ks, vrs;
-    TransStage<T, HD> vts;
-    ks.load(kptr, ld, 0, N, hd, tid);
-    if (TT) vts.load(vptr, ld, 0, N, hd, tid); else vrs.load(vptr, ld, 0, N, hd, tid);
-    for (int j = 0; j < ntiles; ++j) {
-        __syncthreads();
-        ks.store(Ks, tid);
-        if (TT) vts.store(Vs, tid); else vrs.store(Vs, tid);
-        __syncthreads();
-        if (j + 1 < ntiles) {
-            ks.load(kptr, ld, (j + 1) * KVT, N, hd, tid);
-            if (TT) vts.load(vptr, ld, (j + 1) * KVT, N, hd, tid); else vrs.load(vptr, ld, (j + 1) * KVT, N, hd, tid);
-        }
-        if (!active) continue;
-        f32x16 s[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[u][r] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < C::NKK; ++kk)
-                s[u] = mma_chunk(rtile_chunk<T, HD>(Ks, 32 * u + l31, 2 * kk + h), qf[kk], s[u]);
-        }
-        const int kv0 = j * KVT;
-        float mt = -INFINITY;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int kv = kv0 + 32 * u + acc_row(r, h);
-                const float v = (kv < N) ? s[u][r] * scale : -INFINITY;
-                s[u][r] = v;
-                mt = fmaxf(mt, v);
-            }
-        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-        const float m_new = fmaxf(m_run, mt);      // finite: every tile holds at least one valid key
-        const float alpha = __expf(m_run - m_new);
-        float ps = 0.f;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = __expf(s[u][r] - m_new);
-                s[u][r] = p;
-                ps += p;
-            }
-        l_run = l_run * alpha + ps;
-        m_run = m_new;
-        if (p_drop > 0.f) {      // attn_drop (attention.py:33): mask the NORMALISED probabilities -- the row sum stays unmasked
-            const float keep = 1.0f / (1.0f - p_drop);
-            const uint64_t rowbase = (((uint64_t)b * H + head) * N + (uint64_t)(qbase + l31)) * (uint64_t)N;
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    s[u][r] = u01_hash(seed, rowbase + (uint64_t)(kv0 + 32 * u + acc_row(r, h))) >= p_drop ? s[u][r] * keep : 0.f;
-        }
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db) o[db] *= alpha;
-#pragma unroll
-        for (int c = 0; c < C::NPC; ++c) {
-            const chunk_t pb = pack_chunk((const T*)nullptr, s, c);
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-                o[db] = mma_chunk(TRead<T, HD>::chunk(Vs, Vs, db, c, lane), pb, o[db]);
-        }
-    }
-    if (!active) return;
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
-    const int q = qbase + l31;
-    if (q < N) {
-        T* orow = out + ((int64_t)b * N + q) * ldo + head * hd;
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = 32 * db + 8 * g + 4 * h;
-                if (d < hd)
-                    store_quad<T>(orow + d, f32x4{o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv,
-                                                  o[db][4 * g + 3] * inv});
-            }
-        if (lse && h == 0) lse[((int64_t)b * H + head) * N + q] = m_run + __logf(l_tot);
-    }
-}
-
-// =====================================================================================================
-// backward
-//   delta[q]   = sum_d dO[q,d] O[q,d]
-//   P          = exp(S*scale - lse[q]) ; dP = dO V^T ; dS = P * (dP - delta[q]) * scale
-//   dV = P^T dO ; dK = dS^T Q ; dQ = dS K
-// Two kernels, no atomics: (1) dK/dV: a wave owns 32 keys, walks query tiles; (2) dQ: a wave owns 32 queries,
-// walks key tiles (recomputing S and dP).
-// =====================================================================================================
-
-// ---- dK / dV
-template <typename T, int HD>
-__global__ __launch_bounds__(AT_THREADS) void attn_bwd_dkdv_kernel(const T* __restrict__ qkv, int64_t ld,
-                                                                   const T* __restrict__ dout, int64_t lddo,
-                                                                   const float* __restrict__ lse,
-                                                                   const float* __restrict__ delta,
-                                                                   T* __restrict__ dqkv, int64_t lddq, int N, int H,
-                                                                   int hd, float scale, float p_drop, uint64_t seed) {
-    typedef Cfg<T, HD> C;
-    typedef typename Chunk<T>::type chunk_t;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int TB = TRead<T, HD>::kNeedsTransposedTile ? C::T_BYTES : 0;   // bf16 reads the row tiles transposed (tr)
-    char* Qs = smem;                           // [64 q][HD]
-    char* dOs = Qs + C::R_BYTES;               // [64 q][HD]
-    char* QTs = dOs + C::R_BYTES;              // [HD][64 q]   (fp32 only)
-    char* dOTs = QTs + TB;                     // [HD][64 q]   (fp32 only)
-    float* lse_s = reinterpret_cast<float*>(dOTs + TB);           // [64]
-    float* del_s = lse_s + KVT;                                   // [64]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int b = blockIdx.z, head = blockIdx.y;
-    const int kvbase = blockIdx.x * QPB + wave * 32;
-    const int Cdim = H * hd;
-    const T* qptr = qkv + (int64_t)b * N * ld + head * hd;
-    const T* kptr = qptr + Cdim;
-    const T* vptr = qptr + 2 * Cdim;
-    const T* doptr = dout + (int64_t)b * N * lddo + head * hd;
-    const float* lse_bh = lse + ((int64_t)b * H + head) * N;
-    const float* del_bh = delta + ((int64_t)b * H + head) * N;
-
-    chunk_t kf[C::NKK], vf[C::NKK];
-    {
-        const int kvrow = (kvbase + l31 < N) ? kvbase + l31 : N - 1;
-#pragma unroll
-        for (int kk = 0; kk < C::NKK; ++kk) {
-            const int d = (2 * kk + h) * C::E;
-            u32x4 rk = (d < hd) ? *reinterpret_cast<const u32x4*>(kptr + (int64_t)kvrow * ld + d) : zero4();
-            u32x4 rv = (d < hd) ? *reinterpret_cast<const u32x4*>(vptr + (int64_t)kvrow * ld + d) : zero4();
-            kf[kk] = *reinterpret_cast<chunk_t*>(&rk);
-            vf[kk] = *reinterpret_cast<chunk_t*>(&rv);
-        }
-    }
-    f32x16 dk[C::NDB], dv[C::NDB];
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { dk[db][r] = 0.f; dv[db][r] = 0.f; }
-    const bool active = kvbase < N;
-    const bool kv_ok = kvbase + l31 < N;
-    const int ntiles = (N + KVT - 1) / KVT;
-
-    constexpr bool TT = TRead<T, HD>::kNeedsTransposedTile;
-    RowStage<T, HD> qs, dos;
-    TransStage<T, HD> qts, dots;
-    float lse_r = INFINITY, del_r = 0.f;
-    auto gload = [&](int q0) {
-        qs.load(qptr, ld, q0, N, hd, tid);
-        dos.load(doptr, lddo, q0, N, hd, tid);
-        if (TT) {
-            qts.load(qptr, ld, q0, N, hd, tid);
-            dots.load(doptr, lddo, q0, N, hd, tid);
-        }
-        if (tid < KVT) {
-            const int q = q0 + tid;
-            lse_r = (q < N) ? lse_bh[q] : INFINITY;          // exp(s - inf) = 0 masks padded queries
-            del_r = (q < N) ? del_bh[q] : 0.f;
-        }
-    };
-    gload(0);
-    for (int j = 0; j < ntiles; ++j) {
-        __syncthreads();
-        qs.store(Qs, tid);
-        dos.store(dOs, tid);
-        if (TT) {
-            qts.store(QTs, tid);
-            dots.store(dOTs, tid);
-        }
-        if (tid < KVT) {
-            lse_s[tid] = lse_r;
-            del_s[tid] = del_r;
-        }
-        __syncthreads();
-        if (j + 1 < ntiles) gload((j + 1) * KVT);            // next tile's global loads fly during this tile's MFMAs
-        if (!active) continue;
-        f32x16 s[2], dp[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[u][r] = 0.f; dp[u][r] = 0.f; }
-#pragma unroll
-            for (int kk = 0; kk < C::NKK; ++kk) {
-                s[u] = mma_chunk(rtile_chunk<T, HD>(Qs, 32 * u + l31, 2 * kk + h), kf[kk], s[u]);      // S[q][kv]
-                dp[u] = mma_chunk(rtile_chunk<T, HD>(dOs, 32 * u + l31, 2 * kk + h), vf[kk], dp[u]);   // dP[q][kv]
-            }
-        }
-        // lane: kv = l31 (fixed), regs: q = 32u + acc_row(r,h)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 L = *reinterpret_cast<const f32x4*>(lse_s + 32 * u + 8 * g + 4 * h);
-                const f32x4 D = *reinterpret_cast<const f32x4*>(del_s + 32 * u + 8 * g + 4 * h);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = 4 * g + e;
-                    const float p = kv_ok ? __expf(s[u][r] * scale - L[e]) : 0.f;
-                    float pm = p, dpm = dp[u][r];
-                    if (p_drop > 0.f) {      // same mask as forward: dV sees the dropped P, dS the dropped dP
-                        const uint64_t q = (uint64_t)(j * KVT + 32 * u + acc_row(r, h));
-                        const uint64_t idx = (((uint64_t)b * H + head) * N + q) * (uint64_t)N + (uint64_t)(kvbase + l31);
-                        const float k = u01_hash(seed, idx) >= p_drop ? 1.0f / (1.0f - p_drop) : 0.f;
-                        pm *= k; dpm *= k;
-                    }
-                    s[u][r] = pm;                                  // (dropped) P
-                    dp[u][r] = p * (dpm - D[e]) * scale;           // dS
-                }
-            }
-#pragma unroll
-        for (int c = 0; c < C::NPC; ++c) {
-            const chunk_t pb = pack_chunk((const T*)nullptr, s, c);
-            const chunk_t dsb = pack_chunk((const T*)nullptr, dp, c);
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db) {
-                dv[db] = mma_chunk(TRead<T, HD>::chunk(dOTs, dOs, db, c, lane), pb, dv[db]);   // dV^T[d][kv]
-                dk[db] = mma_chunk(TRead<T, HD>::chunk(QTs, Qs, db, c, lane), dsb, dk[db]);  // dK^T[d][kv]
-            }
-        }
-    }
-    if (!active || !kv_ok) return;
-    T* dkrow = dqkv + ((int64_t)b * N + kvbase + l31) * lddq + Cdim + head * hd;
-    T* dvrow = dkrow + Cdim;
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d = 32 * db + 8 * g + 4 * h;
-            if (d < hd) {
-                store_quad<T>(dkrow + d, f32x4{dk[db][4 * g], dk[db][4 * g + 1], dk[db][4 * g + 2], dk[db][4 * g + 3]});
-                store_quad<T>(dvrow + d, f32x4{dv[db][4 * g], dv[db][4 * g + 1], dv[db][4 * g + 2], dv[db][4 * g + 3]});
-            }
-        }
-}
-
-// ---- dQ
-template <typename T, int HD>
-__global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(const T* __restrict__ qkv, int64_t ld,
-                                                                 const T* __restrict__ dout, int64_t lddo,
-                                                                 const float* __restrict__ lse,
-                                                                 const float* __restrict__ delta,
-                                                                 T* __restrict__ dqkv, int64_t lddq, int N, int H,
-                                                                 int hd, float scale, float p_drop, uint64_t seed) {
-    typedef Cfg<T, HD> C;
-    typedef typename Chunk<T>::type chunk_t;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Ks = smem;                    // [64 kv][HD]
-    char* Vs = Ks + C::R_BYTES;         // [64 kv][HD]
-    char* KTs = Vs + C::R_BYTES;        // [HD][64 kv]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int b = blockIdx.z, head = blockIdx.y;
-    const int qbase = blockIdx.x * QPB + wave * 32;
-    const int Cdim = H * hd;
-    const T* qptr = qkv + (int64_t)b * N * ld + head * hd;
-    const T* kptr = qptr + Cdim;
-    const T* vptr = qptr + 2 * Cdim;
-    const T* doptr = dout + (int64_t)b * N * lddo + head * hd;
-
-    const bool q_ok = qbase + l31 < N;
-    const int qrow = q_ok ? qbase + l31 : N - 1;
-    chunk_t qf[C::NKK], dof[C::NKK];
-#pragma unroll
-    for (int kk = 0; kk < C::NKK; ++kk) {
-        const int d = (2 * kk + h) * C::E;
-        u32x4 rq = (d < hd) ? *reinterpret_cast<const u32x4*>(qptr + (int64_t)qrow * ld + d) : zero4();
-        u32x4 rd = (d < hd) ? *reinterpret_cast<const u32x4*>(doptr + (int64_t)qrow * lddo + d) : zero4();
-        qf[kk] = *reinterpret_cast<chunk_t*>(&rq);
-        dof[kk] = *reinterpret_cast<chunk_t*>(&rd);
-    }
-    const float lse_q = lse[((int64_t)b * H + head) * N + qrow];
-    const float del_q = delta[((int64_t)b * H + head) * N + qrow];
-    f32x16 dq[C::NDB];
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dq[db][r] = 0.f;
-    const bool active = qbase < N;
-    const int ntiles = (N + KVT - 1) / KVT;
-
-    constexpr bool TT = TRead<T, HD>::kNeedsTransposedTile;
-    RowStage<T, HD> ks, vs;
-    TransStage<T, HD> kts;
-    auto gload = [&](int kv0) {
-        ks.load(kptr, ld, kv0, N, hd, tid);
-        vs.load(vptr, ld, kv0, N, hd, tid);
-        if (TT) kts.load(kptr, ld, kv0, N, hd, tid);
-    };
-    gload(0);
-    for (int j = 0; j < ntiles; ++j) {
-        const int kv0 = j * KVT;
-        __syncthreads();
-        ks.store(Ks, tid);
-        vs.store(Vs, tid);
-        if (TT) kts.store(KTs, tid);
-        __syncthreads();
-        if (j + 1 < ntiles) gload((j + 1) * KVT);
-        if (!active) continue;
-        f32x16 s[2], dp[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[u][r] = 0.f; dp[u][r] = 0.f; }
-#pragma unroll
-            for (int kk = 0; kk < C::NKK; ++kk) {
-                s[u] = mma_chunk(rtile_chunk<T, HD>(Ks, 32 * u + l31, 2 * kk + h), qf[kk], s[u]);      // S^T[kv][q]
-                dp[u] = mma_chunk(rtile_chunk<T, HD>(Vs, 32 * u + l31, 2 * kk + h), dof[kk], dp[u]);   // dP^T[kv][q]
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int kv = kv0 + 32 * u + acc_row(r, h);
-                const float p = (kv < N) ? __expf(s[u][r] * scale - lse_q) : 0.f;
-                float dpm = dp[u][r];
-                if (p_drop > 0.f) {
-                    const uint64_t idx = (((uint64_t)b * H + head) * N + (uint64_t)(qbase + l31)) * (uint64_t)N + (uint64_t)kv;
-                    dpm = u01_hash(seed, idx) >= p_drop ? dpm * (1.0f / (1.0f - p_drop)) : 0.f;
-                }
-                dp[u][r] = p * (dpm - del_q) * scale;          // dS^T
-            }
-#pragma unroll
-        for (int c = 0; c < C::NPC; ++c) {
-            const chunk_t dsb = pack_chunk((const T*)nullptr, dp, c);
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-                dq[db] = mma_chunk(TRead<T, HD>::chunk(KTs, Ks, db, c, lane), dsb, dq[db]);   // dQ^T[d][q]
-        }
-    }
-    if (!active || !q_ok) return;
-    T* dqrow = dqkv + ((int64_t)b * N + qbase + l31) * lddq + head * hd;
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d = 32 * db + 8 * g + 4 * h;
-            if (d < hd)
-                store_quad<T>(dqrow + d, f32x4{dq[db][4 * g], dq[db][4 * g + 1], dq[db][4 * g + 2], dq[db][4 * g + 3]});
-        }
-}
-
-
-// =====================================================================================================
 // small-sequence kernels (bf16, head_dim <= 64, N <= 256): ONE workgroup of 8 waves per (batch, head), the whole
-// sequence resident in LDS.  At the encoder's N = 197 the tiled kernels above are bound by staging, not math: two
+// sequence resident in LDS.  At the encoder's N = 197 the tiled kernels (attention_qkv.hip) are bound by staging, not math: two
 // query blocks per head re-fetch K/V through different XCD L2s, every 64-key tile costs two barriers, and the
 // 128-query / 64-key tiling pads 197 to 256 both ways.  Here each array is fetched exactly once with all loads in
 // flight together, rows are padded only to a multiple of 32, and the per-wave loops over key (query) sub-tiles run
@@ -2792,7 +2397,6 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_dkdv_chunk_kernel(const b
 }
 
 constexpr size_t LDS_PER_CU = 160 * 1024;
-template <int V> using Int = std::integral_constant<int, V>;
 
 // ---- the route: which kernel family takes a call, and the launch geometry that depends on more than (B, H).  The one place that
 // decides by SM_MINN / SM_MAXN / RS_MAXN / MD_MAXN / ST_BWD_MINN, the 31-bit offset guard, the stride alignments and the row-block
@@ -2855,12 +2459,8 @@ unsigned persistent_grid(int64_t items, int per_cu = 1) {
     const int64_t slots = (int64_t)device_cus() * per_cu;
     return (unsigned)(items < slots ? items : slots);
 }
-// f(Int<HD>) for the route's head width (MAXHD: the widest instantiation the form has), f(Int<NS>) for the ring's sub-tile count
-template <int MAXHD, typename F> int by_hd(const AttnRoute& r, F f) {
-    if (r.hd <= 32) return f(Int<32>());
-    if constexpr (MAXHD <= 64) return f(Int<64>());
-    else return r.hd <= 64 ? f(Int<64>()) : f(Int<128>());
-}
+// f(Int<HD>) for the route's head width (the special forms: head_dim <= 64), f(Int<NS>) for the ring's sub-tile count
+template <typename F> int by_hd(const AttnRoute& r, F f) { return r.hd <= 32 ? f(Int<32>()) : f(Int<64>()); }
 template <typename F> int by_ns(const AttnRoute& r, F f) {
     switch (r.ns) {
         case 3: return f(Int<3>());
@@ -2963,42 +2563,26 @@ template <int HD> int launch_bwd_chunk(const AttnCall& c) {
                                                        c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
 }
 
-// the generic tiled kernels (either dtype, head_dim up to 128, dropout)
-template <typename T, int HD> int launch_fwd(const AttnCall& c) {
-    typedef Cfg<T, HD> C;
-    const size_t smem = C::R_BYTES + (C::T_BYTES > C::R_BYTES ? C::T_BYTES : C::R_BYTES);   // V tile: transposed (fp32) or row-major (bf16)
-    const auto p = c.as<T>();
-    return attn_launch<attn_fwd_kernel<T, HD>>("me_attention_fwd", dim3((c.N + QPB - 1) / QPB, c.H, c.B), AT_THREADS, smem, smem, c.stream, p.qkv, c.ld, p.out,
-                                               c.ldo, c.lse, c.N, c.H, c.hd, c.scale, c.p_drop, c.seed);
-}
-template <typename T, int HD> int launch_bwd(const AttnCall& c) {
-    typedef Cfg<T, HD> C;
-    constexpr size_t TB = TRead<T, HD>::kNeedsTransposedTile ? C::T_BYTES : 0;
-    const size_t smem1 = 2 * C::R_BYTES + 2 * TB + 2 * KVT * sizeof(float);
-    const size_t smem2 = 2 * C::R_BYTES + TB;
-    const auto p = c.as<T>();
-    const dim3 grid((c.N + QPB - 1) / QPB, c.H, c.B);
-    if (int rc = attn_launch<attn_bwd_dkdv_kernel<T, HD>>("me_attention_bwd(dkdv)", grid, AT_THREADS, smem1, smem1, c.stream, p.qkv, c.ld, p.dout, c.lddo, c.lse,
-                                                          c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale, c.p_drop, c.seed))
-        return rc;
-    return attn_launch<attn_bwd_dq_kernel<T, HD>>("me_attention_bwd(dq)", grid, AT_THREADS, smem2, smem2, c.stream, p.qkv, c.ld, p.dout, c.lddo, c.lse, c.delta,
-                                                  p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale, c.p_drop, c.seed);
-}
-// delta = rowsum(dO o O): the generic backward's first pass
-int launch_delta(const AttnCall& c) {
-    const int64_t rows = (int64_t)c.B * c.N;
-    const int64_t nw = rows * c.H;
-    const int lph = c.hd / 8;
-    if (c.dtype == ME_BF16 && c.hd % 8 == 0 && (lph & (lph - 1)) == 0 && lph <= 64 && c.ldo % 8 == 0 && c.lddo % 8 == 0) {
-        const auto p = c.as<bf16_t>();
-        hipLaunchKernelGGL(attn_delta_vec_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, c.stream, p.out, c.ldo, p.dout, c.lddo, c.delta, c.N, c.H,
-                           c.hd, rows);
-    } else {
-        hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, c.stream, c.out, c.ldo, c.dout, c.lddo, c.dtype, c.delta, c.N,
-                           c.H, c.hd, rows);
-    }
-    ME_CHECK_LAUNCH("me_attention_bwd(delta)");
-    return ME_OK;
+// ME_ATTN_GENERIC: the packed call as the descriptor of the tiled kernels (attention_qkv.hip) -- q | k | v = qkv + {0, C, 2C} on one row
+// stride, dq | dk | dv = dqkv + {0, C, 2C} likewise, Nq = Nk = N, not causal
+me_attn_qkv_desc tiled_desc(const AttnCall& c) {
+    const size_t Cb = (size_t)c.H * c.hd * me_dtype_size(c.dtype);      // one third of a row, bytes
+    const char* q = static_cast<const char*>(c.qkv);
+    char* dq = static_cast<char*>(c.dqkv);                              // (null in a forward call)
+    me_attn_qkv_desc d = {};
+    d.q = q; d.k = q + Cb; d.v = q + 2 * Cb;
+    d.ld_q = d.ld_k = d.ld_v = c.ld;
+    d.out = c.out; d.ld_out = c.ldo;
+    d.lse = c.lse;
+    d.dout = c.dout; d.ld_dout = c.lddo;
+    d.delta = c.delta;
+    if (dq) { d.dq = dq; d.dk = dq + Cb; d.dv = dq + 2 * Cb; }
+    d.ld_dq = d.ld_dk = d.ld_dv = c.lddq;
+    d.seed = c.seed;
+    d.B = c.B; d.Nq = d.Nk = c.N; d.H = c.H; d.head_dim = c.hd;
+    d.dtype = c.dtype; d.causal = 0;
+    d.scale = c.scale; d.p_drop = c.p_drop;
+    return d;
 }
 
 int check_attn_args(const char* fn, int64_t ld, int B, int N, int H, int hd, int dtype) {
@@ -3028,14 +2612,13 @@ extern "C" int me_attention_fwd(const void* qkv, int64_t ld_qkv, void* out, int6
     prof.plan = r.plan();
     switch (r.form) {
         case ME_ATTN_TINY: return launch_attn_tiny(c, false);
-        case ME_ATTN_RING16: return by_hd<64>(r, [&](auto HD) { return by_ns(r, [&](auto NS) { return launch_fwd_ring16<HD(), NS()>(c); }); });
-        case ME_ATTN_RESIDENT: return by_hd<64>(r, [&](auto HD) { return launch_fwd_small<HD()>(c); });
+        case ME_ATTN_RING16: return by_hd(r, [&](auto HD) { return by_ns(r, [&](auto NS) { return launch_fwd_ring16<HD(), NS()>(c); }); });
+        case ME_ATTN_RESIDENT: return by_hd(r, [&](auto HD) { return launch_fwd_small<HD()>(c); });
         case ME_ATTN_STREAM16: return launch_fwd_stream16<64>(c, r);
-        case ME_ATTN_MID: return by_hd<64>(r, [&](auto HD) { return launch_fwd_mid<HD()>(c); });
-        case ME_ATTN_CHUNK: return by_hd<64>(r, [&](auto HD) { return launch_fwd_chunk<HD()>(c); });
+        case ME_ATTN_MID: return by_hd(r, [&](auto HD) { return launch_fwd_mid<HD()>(c); });
+        case ME_ATTN_CHUNK: return by_hd(r, [&](auto HD) { return launch_fwd_chunk<HD()>(c); });
     }
-    if (dtype == ME_BF16) return by_hd<128>(r, [&](auto HD) { return launch_fwd<bf16_t, HD()>(c); });
-    return by_hd<128>(r, [&](auto HD) { return launch_fwd<float, HD()>(c); });
+    return launch_attn_tiled_fwd(tiled_desc(c), stream);
 }
 
 extern "C" int me_attention_bwd(const void* qkv, int64_t ld_qkv, const void* out, int64_t ld_out, const void* dout,
@@ -3056,13 +2639,12 @@ extern "C" int me_attention_bwd(const void* qkv, int64_t ld_qkv, const void* out
     prof.plan = r.plan();
     switch (r.form) {
         case ME_ATTN_TINY: return launch_attn_tiny(c, true);
-        case ME_ATTN_RING16: return by_hd<64>(r, [&](auto HD) { return by_ns(r, [&](auto NS) { return launch_bwd_ring16<HD(), NS()>(c); }); });
-        case ME_ATTN_RESIDENT: return by_hd<64>(r, [&](auto HD) { return launch_bwd_small<HD()>(c); });
+        case ME_ATTN_RING16: return by_hd(r, [&](auto HD) { return by_ns(r, [&](auto NS) { return launch_bwd_ring16<HD(), NS()>(c); }); });
+        case ME_ATTN_RESIDENT: return by_hd(r, [&](auto HD) { return launch_bwd_small<HD()>(c); });
         case ME_ATTN_STREAM16: return launch_bwd_stream16<64>(c, r);
-        case ME_ATTN_MID: return by_hd<64>(r, [&](auto HD) { return launch_bwd_mid<HD()>(c); });
-        case ME_ATTN_CHUNK: return by_hd<64>(r, [&](auto HD) { return launch_bwd_chunk<HD()>(c); });
+        case ME_ATTN_MID: return by_hd(r, [&](auto HD) { return launch_bwd_mid<HD()>(c); });
+        case ME_ATTN_CHUNK: return by_hd(r, [&](auto HD) { return launch_bwd_chunk<HD()>(c); });
     }
-    if ((rc = launch_delta(c))) return rc;
-    if (dtype == ME_BF16) return by_hd<128>(r, [&](auto HD) { return launch_bwd<bf16_t, HD()>(c); });
-    return by_hd<128>(r, [&](auto HD) { return launch_bwd<float, HD()>(c); });
+    if ((rc = launch_attn_delta(out, ld_out, dout, ld_dout, dtype, delta, B, N, H, head_dim, stream))) return rc;      // delta = dO . O
+    return launch_attn_tiled_bwd(tiled_desc(c), stream);
 }

@@ -1,7 +1,11 @@
 // attention_host.h -- host side of the attention entry points: what me_attention_fwd / _bwd (attention.hip) hand from validation to
-// route to launch, shared with the N <= 64 kernels of attention_tiny.hip and with block.hip.  No device code.
+// route to launch, shared with the N <= 64 kernels of attention_tiny.hip, the tiled kernels of attention_qkv.hip and with block.hip.
+// No device code.
 #pragma once
 #include "common.h"
+#include <type_traits>
+
+template <int V> using Int = std::integral_constant<int, V>;      // a compile-time width handed to a generic lambda
 
 // One call's arguments, filled once by the entry point after validation.  The backward-only fields stay null / 0 in a forward call.
 struct AttnCall {
@@ -38,6 +42,15 @@ struct AttnRoute {
 // attention_tiny.hip: N <= 64, one small workgroup per (batch, head)
 bool attn_tiny_ok(const AttnCall& c);
 int launch_attn_tiny(const AttnCall& c, bool backward);
+
+// attention_qkv.hip: the tiled kernels (128 queries per block, 64-key LDS tiles; either dtype, head_dim up to 128, dropout), launched on
+// a descriptor that its entry point has checked: me_attention_qkv_fwd / _bwd, and the ME_ATTN_GENERIC arm of me_attention_fwd / _bwd with
+// the packed call written as one.  No argument checks, no ProfScope and no delta pass: the backward reads d.delta, which its caller filled.
+int launch_attn_tiled_fwd(const me_attn_qkv_desc& d, hipStream_t stream);
+int launch_attn_tiled_bwd(const me_attn_qkv_desc& d, hipStream_t stream);      // dK / dV, then dQ
+// delta[b, h, n] = dO . O over the head's channels, out and dout [B*N, H*hd]: the delta pass of me_attention_bwd and of the fp32 me_attention_qkv_bwd
+int launch_attn_delta(const void* out, int64_t ldo, const void* dout, int64_t lddo, int dtype, float* delta, int B, int N, int H, int hd,
+                      hipStream_t stream);
 
 // an ME_BF16X3 Block runs its attention as three bf16 products (attention_x3.hip) at this shape, on the exact-fp32 kernels otherwise
 // (N <= 64: the exact-fp32 one-workgroup-per-head kernels, attention_tiny.hip, are faster and exact)

@@ -1,22 +1,35 @@
-// attention_qkv.hip -- multi-head attention with SEPARATE Q, K and V operands, two sequence lengths and a causal flag
-// (me_attention_qkv_fwd / _bwd): the decoder side of the Time-Series forecaster.
+// attention_qkv.hip -- the tiled attention kernels: multi-head attention over SEPARATE Q, K and V operands, two sequence lengths and a causal
+// flag, flash-style.  Two callers:
+//   * me_attention_qkv_fwd / _bwd (here): the decoder side of the Time-Series forecaster.  Replaces FullAttention.forward
+//     (Time-Series/layers/SelfAttention_Family.py:56-75) together with the head reshapes of AttentionLayer (:195-211): scores = Q K^T,
+//     TriangularCausalMask (utils/masking.py:4-8) when mask_flag, softmax(scale * scores), dropout, A V.
+//   * the ME_ATTN_GENERIC arm of me_attention_fwd / _bwd (attention.hip): the packed [B*N, 3C] call is q = qkv, k = qkv + C, v = qkv + 2C
+//     on one row stride, Nq = Nk, not causal -- exact-fp32, head_dim > 64, dropout, and what no special form of attn_route takes.
+// Both reach the kernels through launch_attn_tiled_fwd / _bwd (attention_host.h).
 //
-// Replaces FullAttention.forward (Time-Series/layers/SelfAttention_Family.py:56-75) together with the head reshapes of AttentionLayer
-// (:195-211): scores = Q K^T, TriangularCausalMask (utils/masking.py:4-8) when mask_flag, softmax(scale * scores), dropout, A V.
 // Q, K and V are addressed in place, each by its own pointer and row stride, so one call reads Q from a [B*Nq, C] projection and K / V
-// from one packed [B*Nk, 2C] GEMM output (cross-attention) or all three from a packed [B*N, 3C] (self-attention).
+// from one packed [B*Nk, 2C] GEMM output (cross-attention) or all three from a packed [B*N, 3C] (self-attention).  The [B,H,Nq,Nk]
+// score matrix is never written: K / V tiles of 64 keys are staged in LDS (attention_tile.h), a block takes 128 queries (32 per wave),
+// the softmax runs online in registers, and O is written head-major straight into [tokens, C].  Instantiated for HD 32 / 64 / 128.
 //
-// The kernels are the generic tiled kernels of attention.hip (attn_fwd_kernel, attn_bwd_dkdv_kernel, attn_bwd_dq_kernel) -- same Cfg,
-// staging and transposed MFMA formulation (attention_tile.h), 128 queries per block, 64-key LDS tiles, HD 32 / 64 / 128 -- with
-//   * three operand pointers and Nq != Nk,
+// MFMA formulation (32x32 shapes, see common.h): every product is issued "transposed" so that the softmax
+// row (one query) lives in ONE lane (plus its partner lane^32):
+//   S^T[kv][q] = K Q^T           A = K rows (from LDS), B = Q rows (registers)      -> lane q, regs kv
+//   O^T[d][q] += V^T P^T         A = V^T rows d (LDS, transposed while staging), B = P (registers, in place)
+// The row max / row sum are 16-register reductions plus one xor-32 shuffle; the running rescale of O^T is a
+// per-lane scalar.  The reduction-index permutation the accumulator layout imposes on P is absorbed by reading
+// V^T with the same permutation (common.h: any assignment works if A and B agree).
+// fp32 runs the same code on the exact-fp32 MFMA (parity mode); bf16 is the performance mode.
+//
 //   * causal: tiles entirely on the masked side of the diagonal are skipped (the loop bounds are block-uniform, a wave skips the
 //     compute of a tile none of its rows sees), the tiles the diagonal crosses are masked element-wise,
-//   * the dropout stream indexed ((b*H + h)*Nq + q)*Nk + k (the index of me_attention_fwd when Nq == Nk).
-// Backward: delta pass (fp32: dO . O; bf16: from the tiles), dK / dV (a wave owns 32 keys, walks query tiles), dQ (a wave owns 32 queries, walks key tiles).  No atomics,
-// every output element is written exactly once, two runs are bit-identical.
+//   * the dropout stream is indexed ((b*H + h)*Nq + q)*Nk + k.
+// Backward: a delta pass chosen by the entry point (dO . O, or from the tiles: attn_qkv_delta_kernel says when), dK / dV (a wave owns
+// 32 keys, walks query tiles), dQ (a wave owns 32 queries, walks key tiles).  No atomics, every output element is written exactly
+// once, two runs are bit-identical.
+#include "attention_host.h"
 #include "attention_tile.h"
 #include <stdint.h>
-#include <type_traits>
 
 namespace {
 
@@ -25,7 +38,7 @@ __device__ __forceinline__ bool qkv_visible(int kv, int q, int Nk, int causal) {
 
 // fp32: the transposed [HD][64] copy of a tile written from the registers of its row-major stage.  RowStage<float> and TransStage<float> fetch
 // the same 16 bytes per item, so the backward kernels stage Q / dO / K once and store them twice instead of loading them twice
-// (the generic kernels keep two register sets; at HD 128 that second set is what no longer fits beside the accumulators).
+// (a second register set for the transposed copy is what no longer fits beside the accumulators at HD 128).
 template <int HD> __device__ __forceinline__ void store_transposed(const RowStage<float, HD>& st, char* lds, int tid) {
     typedef Cfg<float, HD> C;
 #pragma unroll
@@ -177,7 +190,12 @@ __global__ __launch_bounds__(AT_THREADS) void attn_qkv_fwd_kernel(const T* __res
 }
 
 // =====================================================================================================
-// backward (the formulas of attention.hip): P = exp(S*scale - lse[q]) on the visible entries, 0 elsewhere
+// backward
+//   delta[q]   = sum_d dO[q,d] O[q,d]
+//   P          = exp(S*scale - lse[q]) on the visible entries, 0 elsewhere ; dP = dO V^T ; dS = P * (dP - delta[q]) * scale
+//   dV = P^T dO ; dK = dS^T Q ; dQ = dS K
+// Two kernels, no atomics: (1) dK/dV: a wave owns 32 keys, walks query tiles; (2) dQ: a wave owns 32 queries,
+// walks key tiles (recomputing S and dP).
 // =====================================================================================================
 
 // ---- dK / dV: a wave owns 32 keys and walks the 64-query tiles that can see them.  The launch accumulates the NDBO 32-wide d blocks from
@@ -295,8 +313,8 @@ __global__ __launch_bounds__(AT_THREADS) void attn_qkv_bwd_dkdv_kernel(const T* 
                     dp[u][r] = p * (dpm - D[e]) * scale;           // dS
                 }
             }
-            // this 32-query half goes into dV / dK before the other half's S and dP are formed (the chunk order of the generic kernel, with
-            // half the S / dP registers live)
+            // this 32-query half goes into dV / dK before the other half's S and dP are formed (chunks still in ascending order, with half
+            // the S / dP registers live)
 #pragma unroll
             for (int c = u * (C::NPC / 2); c < (u + 1) * (C::NPC / 2); ++c) {
                 const chunk_t pb = pack_chunk((const T*)nullptr, s, c);
@@ -325,7 +343,7 @@ __global__ __launch_bounds__(AT_THREADS) void attn_qkv_bwd_dkdv_kernel(const T* 
 }
 
 // ---- delta for bf16: delta[q] = sum_k P~[q,k] dP[q,k] (P~: the dropped probabilities) from the tiles, in fp32.  In exact arithmetic this is
-// dO . O, which is how the fp32 path (and the generic backward) forms it; in bf16 that O is the rounded output of a forward that rounded P
+// dO . O, which is how the fp32 path (and me_attention_bwd) forms it; in bf16 that O is the rounded output of a forward that rounded P
 // too, and in the first rows of a causal call, where a few keys carry large probabilities, the error reaches dS undamped (measured: dQ
 // off by 0.5 % of max|dQ| at N = 129, head_dim 96).  Formed here, dS sums to zero over the keys as it should.  Same walk as the dQ kernel.
 template <typename T, int HD>
@@ -519,36 +537,75 @@ __global__ __launch_bounds__(AT_THREADS) void attn_qkv_bwd_dq_kernel(const T* __
         }
 }
 
-// ---- host
-template <int V> using Int = std::integral_constant<int, V>;
-template <auto Kernel, typename... Args>
-int qkv_launch(const char* label, dim3 grid, size_t lds, hipStream_t stream, Args... args) {
-    static OncePerDevice once;      // the dynamic-LDS limit of an instantiation is fixed (its tile sizes): raised once per device
-    if (once.need()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(Kernel, grid, dim3(AT_THREADS), lds, stream, args...);
-    ME_CHECK_LAUNCH(label);
-    return ME_OK;
+// ---- delta = dO . O
+// delta[q] = sum_d dO[q,d] O[q,d]: the first pass of the tiled backward (N = query rows per batch item)
+__global__ __launch_bounds__(256) void attn_delta_kernel(const void* __restrict__ o, int64_t ldo,
+                                                         const void* __restrict__ dout, int64_t lddo, int dt,
+                                                         float* __restrict__ delta, int N, int H, int hd, int64_t rows) {
+    // one wave per (token row, head)
+    const int lane = threadIdx.x & 63;
+    const int64_t gw = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gw >= rows * H) return;
+    const int64_t row = gw / H;
+    const int head = (int)(gw % H);
+    float s = 0.f;
+    for (int d = lane; d < hd; d += 64)
+        s += load1_as_f32(o, dt, row * ldo + head * hd + d) * load1_as_f32(dout, dt, row * lddo + head * hd + d);
+    s = wave_sum(s);
+    if (lane == 0) {
+        const int64_t b = row / N, n = row % N;
+        delta[(b * H + head) * N + n] = s;
+    }
 }
 
-template <typename T, int HD> int launch_qkv_fwd(const me_attn_qkv_desc& d, hipStream_t stream) {
+// vector path for bf16 with head_dim a power-of-two multiple of 8 (<= 512): one wave per token row, a lane owns 8
+// consecutive channels (16-byte loads of O and dO), the head_dim/8 lanes of a head fold with xor-shuffles.
+__global__ __launch_bounds__(256) void attn_delta_vec_kernel(const bf16_t* __restrict__ o, int64_t ldo,
+                                                             const bf16_t* __restrict__ dout, int64_t lddo,
+                                                             float* __restrict__ delta, int N, int H, int hd, int64_t rows) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int C8 = (H * hd) / 8, lph = hd / 8;      // chunks per row, lanes per head
+    const int64_t b = row / N, n = row % N;
+    for (int c = lane; c < ((C8 + 63) / 64) * 64; c += 64) {
+        float s = 0.f;
+        if (c < C8) {
+            const u32x4 ro = *reinterpret_cast<const u32x4*>(o + row * ldo + c * 8);
+            const u32x4 rd = *reinterpret_cast<const u32x4*>(dout + row * lddo + c * 8);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                s += __uint_as_float(ro[e] << 16) * __uint_as_float(rd[e] << 16) +
+                     __uint_as_float(ro[e] & 0xffff0000u) * __uint_as_float(rd[e] & 0xffff0000u);
+        }
+        for (int off = 1; off < lph; off <<= 1) s += __shfl_xor(s, off, 64);
+        if (c < C8 && (c % lph) == 0) delta[(b * H + c / lph) * N + n] = s;
+    }
+}
+
+// ---- host
+template <typename T, int HD> int launch_fwd(const me_attn_qkv_desc& d, hipStream_t stream) {
     typedef Cfg<T, HD> C;
     const size_t smem = C::R_BYTES + (C::T_BYTES > C::R_BYTES ? C::T_BYTES : C::R_BYTES);   // V tile: transposed (fp32) or row-major (bf16)
-    return qkv_launch<attn_qkv_fwd_kernel<T, HD>>("me_attention_qkv_fwd", dim3((d.Nq + QPB - 1) / QPB, d.H, d.B), smem, stream,
-                                                  (const T*)d.q, d.ld_q, (const T*)d.k, d.ld_k, (const T*)d.v, d.ld_v, (T*)d.out, d.ld_out, d.lse,
-                                                  d.Nq, d.Nk, d.H, d.head_dim, d.scale, d.causal, d.p_drop, d.seed);
+    return attn_launch<attn_qkv_fwd_kernel<T, HD>>("attention tiled fwd", dim3((d.Nq + QPB - 1) / QPB, d.H, d.B), AT_THREADS, smem, smem, stream,
+                                                   (const T*)d.q, d.ld_q, (const T*)d.k, d.ld_k, (const T*)d.v, d.ld_v, (T*)d.out, d.ld_out, d.lse,
+                                                   d.Nq, d.Nk, d.H, d.head_dim, d.scale, d.causal, d.p_drop, d.seed);
 }
-template <typename T, int HD> int launch_qkv_bwd(const me_attn_qkv_desc& d, hipStream_t stream) {
+template <typename T, int HD> int launch_bwd(const me_attn_qkv_desc& d, hipStream_t stream) {
     typedef Cfg<T, HD> C;
     constexpr size_t TB = TRead<T, HD>::kNeedsTransposedTile ? C::T_BYTES : 0;
     const size_t smem1 = 2 * C::R_BYTES + 2 * TB + 2 * KVT * sizeof(float);
     const size_t smem2 = 2 * C::R_BYTES + TB;
     const dim3 gridk((d.Nk + QPB - 1) / QPB, d.H, d.B);
     auto dkdv = [&](auto DB0, auto NDBO) {
-        return qkv_launch<attn_qkv_bwd_dkdv_kernel<T, HD, DB0(), NDBO()>>("me_attention_qkv_bwd(dkdv)", gridk, smem1, stream, (const T*)d.q, d.ld_q,
-                                                                          (const T*)d.k, d.ld_k, (const T*)d.v, d.ld_v, (const T*)d.dout, d.ld_dout,
-                                                                          d.lse, d.delta, (T*)d.dk, d.ld_dk, (T*)d.dv, d.ld_dv, d.Nq, d.Nk, d.H,
-                                                                          d.head_dim, d.scale, d.causal, d.p_drop, d.seed);
+        return attn_launch<attn_qkv_bwd_dkdv_kernel<T, HD, DB0(), NDBO()>>("attention tiled bwd (dkdv)", gridk, AT_THREADS, smem1, smem1, stream,
+                                                                           (const T*)d.q, d.ld_q, (const T*)d.k, d.ld_k, (const T*)d.v, d.ld_v,
+                                                                           (const T*)d.dout, d.ld_dout, d.lse, d.delta, (T*)d.dk, d.ld_dk, (T*)d.dv,
+                                                                           d.ld_dv, d.Nq, d.Nk, d.H, d.head_dim, d.scale, d.causal, d.p_drop, d.seed);
     };
+    // fp32 at head_dim > 64: two launches of two d blocks each, no scratch, S and dP formed in both -- against ONE launch of
+    // attn_qkv_bwd_dkdv_kernel<float, 128, 0, 4> (440 bytes of scratch per lane), same bits.  NOT TIMED against each other: the rule
+    // assumes that the launch without scratch traffic is no slower.  Both entry points take it.
     if constexpr (sizeof(T) == 4 && HD == 128) {
         if (int rc = dkdv(Int<0>(), Int<2>())) return rc;
         if (d.head_dim > 64)
@@ -556,25 +613,20 @@ template <typename T, int HD> int launch_qkv_bwd(const me_attn_qkv_desc& d, hipS
     } else {
         if (int rc = dkdv(Int<0>(), Int<C::NDB>())) return rc;
     }
-    return qkv_launch<attn_qkv_bwd_dq_kernel<T, HD>>("me_attention_qkv_bwd(dq)", dim3((d.Nq + QPB - 1) / QPB, d.H, d.B), smem2, stream, (const T*)d.q,
-                                                     d.ld_q, (const T*)d.k, d.ld_k, (const T*)d.v, d.ld_v, (const T*)d.dout, d.ld_dout, d.lse, d.delta,
-                                                     (T*)d.dq, d.ld_dq, d.Nq, d.Nk, d.H, d.head_dim, d.scale, d.causal, d.p_drop, d.seed);
+    return attn_launch<attn_qkv_bwd_dq_kernel<T, HD>>("attention tiled bwd (dq)", dim3((d.Nq + QPB - 1) / QPB, d.H, d.B), AT_THREADS, smem2, smem2, stream,
+                                                      (const T*)d.q, d.ld_q, (const T*)d.k, d.ld_k, (const T*)d.v, d.ld_v, (const T*)d.dout, d.ld_dout,
+                                                      d.lse, d.delta, (T*)d.dq, d.ld_dq, d.Nq, d.Nk, d.H, d.head_dim, d.scale, d.causal, d.p_drop, d.seed);
 }
-// delta pass: fp32 -> dO . O (attention_tile.h); bf16 -> from the tiles (attn_qkv_delta_kernel, which says why)
-int launch_qkv_delta_f32(const me_attn_qkv_desc& d, hipStream_t stream) {
-    const int64_t rows = (int64_t)d.B * d.Nq;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows * d.H + 3) / 4)), dim3(256), 0, stream, (const void*)d.out, d.ld_out, d.dout, d.ld_dout,
-                       d.dtype, d.delta, d.Nq, d.H, d.head_dim, rows);
-    ME_CHECK_LAUNCH("me_attention_qkv_bwd(delta)");
-    return ME_OK;
-}
+// bf16 delta of me_attention_qkv_bwd: from the tiles (attn_qkv_delta_kernel, which says why)
 template <int HD> int launch_qkv_delta_bf16(const me_attn_qkv_desc& d, hipStream_t stream) {
     typedef bf16_t T;
-    return qkv_launch<attn_qkv_delta_kernel<T, HD>>("me_attention_qkv_bwd(delta)", dim3((d.Nq + QPB - 1) / QPB, d.H, d.B), 2 * Cfg<T, HD>::R_BYTES, stream,
-                                                    (const T*)d.q, d.ld_q, (const T*)d.k, d.ld_k, (const T*)d.v, d.ld_v, (const T*)d.dout, d.ld_dout,
-                                                    d.lse, d.delta, d.Nq, d.Nk, d.H, d.head_dim, d.scale, d.causal, d.p_drop, d.seed);
+    constexpr size_t smem = 2 * Cfg<T, HD>::R_BYTES;
+    return attn_launch<attn_qkv_delta_kernel<T, HD>>("me_attention_qkv_bwd(delta)", dim3((d.Nq + QPB - 1) / QPB, d.H, d.B), AT_THREADS, smem, smem, stream,
+                                                     (const T*)d.q, d.ld_q, (const T*)d.k, d.ld_k, (const T*)d.v, d.ld_v, (const T*)d.dout, d.ld_dout,
+                                                     d.lse, d.delta, d.Nq, d.Nk, d.H, d.head_dim, d.scale, d.causal, d.p_drop, d.seed);
 }
 
+// f(Int<HD>) for the instantiated head width
 template <typename F> int qkv_by_hd(int hd, F f) {
     if (hd <= 32) return f(Int<32>());
     return hd <= 64 ? f(Int<64>()) : f(Int<128>());
@@ -610,13 +662,37 @@ int check_qkv_desc(const char* fn, const me_attn_qkv_desc* d, bool backward) {
 
 }  // namespace
 
+int launch_attn_tiled_fwd(const me_attn_qkv_desc& d, hipStream_t stream) {
+    if (d.dtype == ME_BF16) return qkv_by_hd(d.head_dim, [&](auto HD) { return launch_fwd<bf16_t, HD()>(d, stream); });
+    return qkv_by_hd(d.head_dim, [&](auto HD) { return launch_fwd<float, HD()>(d, stream); });
+}
+
+int launch_attn_tiled_bwd(const me_attn_qkv_desc& d, hipStream_t stream) {
+    if (d.dtype == ME_BF16) return qkv_by_hd(d.head_dim, [&](auto HD) { return launch_bwd<bf16_t, HD()>(d, stream); });
+    return qkv_by_hd(d.head_dim, [&](auto HD) { return launch_bwd<float, HD()>(d, stream); });
+}
+
+int launch_attn_delta(const void* out, int64_t ldo, const void* dout, int64_t lddo, int dtype, float* delta, int B, int N, int H, int hd,
+                      hipStream_t stream) {
+    const int64_t rows = (int64_t)B * N;
+    const int64_t nw = rows * H;
+    const int lph = hd / 8;
+    if (dtype == ME_BF16 && hd % 8 == 0 && (lph & (lph - 1)) == 0 && lph <= 64 && ldo % 8 == 0 && lddo % 8 == 0) {
+        hipLaunchKernelGGL(attn_delta_vec_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, (const bf16_t*)out, ldo, (const bf16_t*)dout,
+                           lddo, delta, N, H, hd, rows);
+    } else {
+        hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, stream, out, ldo, dout, lddo, dtype, delta, N, H, hd, rows);
+    }
+    ME_CHECK_LAUNCH("attention delta");
+    return ME_OK;
+}
+
 extern "C" int me_attention_qkv_fwd(const me_attn_qkv_desc* d, void* stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (int rc = check_qkv_desc("me_attention_qkv_fwd", d, false)) return rc;
     ProfScope prof(ME_PROF_ATTN_FWD, d->dtype, (int64_t)d->B * d->H, d->Nq, d->head_dim, stream);
     prof.plan = ME_ATTN_QKV;
-    if (d->dtype == ME_BF16) return qkv_by_hd(d->head_dim, [&](auto HD) { return launch_qkv_fwd<bf16_t, HD()>(*d, stream); });
-    return qkv_by_hd(d->head_dim, [&](auto HD) { return launch_qkv_fwd<float, HD()>(*d, stream); });
+    return launch_attn_tiled_fwd(*d, stream);
 }
 
 extern "C" int me_attention_qkv_bwd(const me_attn_qkv_desc* d, void* stream_) {
@@ -624,11 +700,9 @@ extern "C" int me_attention_qkv_bwd(const me_attn_qkv_desc* d, void* stream_) {
     if (int rc = check_qkv_desc("me_attention_qkv_bwd", d, true)) return rc;
     ProfScope prof(ME_PROF_ATTN_BWD, d->dtype, (int64_t)d->B * d->H, d->Nq, d->head_dim, stream);
     prof.plan = ME_ATTN_QKV;
-    if (d->dtype == ME_BF16)
-        return qkv_by_hd(d->head_dim, [&](auto HD) {
-            if (int rc = launch_qkv_delta_bf16<HD()>(*d, stream)) return rc;
-            return launch_qkv_bwd<bf16_t, HD()>(*d, stream);
-        });
-    if (int rc = launch_qkv_delta_f32(*d, stream)) return rc;
-    return qkv_by_hd(d->head_dim, [&](auto HD) { return launch_qkv_bwd<float, HD()>(*d, stream); });
+    // delta pass: fp32 -> dO . O; bf16 -> from the tiles
+    if (int rc = d->dtype == ME_BF16 ? qkv_by_hd(d->head_dim, [&](auto HD) { return launch_qkv_delta_bf16<HD()>(*d, stream); })
+                                     : launch_attn_delta(d->out, d->ld_out, d->dout, d->ld_dout, d->dtype, d->delta, d->B, d->Nq, d->H, d->head_dim, stream))
+        return rc;
+    return launch_attn_tiled_bwd(*d, stream);
 }

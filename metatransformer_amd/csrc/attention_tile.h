@@ -1,6 +1,6 @@
-// attention_tile.h -- device pieces shared by the tiled attention kernels of attention.hip (packed qkv) and attention_qkv.hip
-// (separate Q / K / V, two lengths, causal): tile geometry, global -> LDS staging, MFMA operand reads, and the delta pass of the
-// backward.  Included inside no namespace; everything here has internal linkage.
+// attention_tile.h -- device pieces shared by the tiled attention kernels of attention_qkv.hip and the sequence-resident kernels of
+// attention.hip: tile geometry, global -> LDS staging, MFMA operand reads.  Device code only.  Included inside no namespace;
+// everything here has internal linkage.
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -186,51 +186,6 @@ template <> __device__ __forceinline__ void store_quad<bf16_t>(bf16_t* p, f32x4 
     bf16x4 o;
     o[0] = (bf16_t)v[0]; o[1] = (bf16_t)v[1]; o[2] = (bf16_t)v[2]; o[3] = (bf16_t)v[3];
     *reinterpret_cast<bf16x4*>(p) = o;
-}
-
-// delta[q] = sum_d dO[q,d] O[q,d]: the first pass of the tiled backward (N = query rows per batch item)
-__global__ __launch_bounds__(256) void attn_delta_kernel(const void* __restrict__ o, int64_t ldo,
-                                                         const void* __restrict__ dout, int64_t lddo, int dt,
-                                                         float* __restrict__ delta, int N, int H, int hd, int64_t rows) {
-    // one wave per (token row, head)
-    const int lane = threadIdx.x & 63;
-    const int64_t gw = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (gw >= rows * H) return;
-    const int64_t row = gw / H;
-    const int head = (int)(gw % H);
-    float s = 0.f;
-    for (int d = lane; d < hd; d += 64)
-        s += load1_as_f32(o, dt, row * ldo + head * hd + d) * load1_as_f32(dout, dt, row * lddo + head * hd + d);
-    s = wave_sum(s);
-    if (lane == 0) {
-        const int64_t b = row / N, n = row % N;
-        delta[(b * H + head) * N + n] = s;
-    }
-}
-
-// vector path for bf16 with head_dim a power-of-two multiple of 8 (<= 512): one wave per token row, a lane owns 8
-// consecutive channels (16-byte loads of O and dO), the head_dim/8 lanes of a head fold with xor-shuffles.
-__global__ __launch_bounds__(256) void attn_delta_vec_kernel(const bf16_t* __restrict__ o, int64_t ldo,
-                                                             const bf16_t* __restrict__ dout, int64_t lddo,
-                                                             float* __restrict__ delta, int N, int H, int hd, int64_t rows) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int C8 = (H * hd) / 8, lph = hd / 8;      // chunks per row, lanes per head
-    const int64_t b = row / N, n = row % N;
-    for (int c = lane; c < ((C8 + 63) / 64) * 64; c += 64) {
-        float s = 0.f;
-        if (c < C8) {
-            const u32x4 ro = *reinterpret_cast<const u32x4*>(o + row * ldo + c * 8);
-            const u32x4 rd = *reinterpret_cast<const u32x4*>(dout + row * lddo + c * 8);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                s += __uint_as_float(ro[e] << 16) * __uint_as_float(rd[e] << 16) +
-                     __uint_as_float(ro[e] & 0xffff0000u) * __uint_as_float(rd[e] & 0xffff0000u);
-        }
-        for (int off = 1; off < lph; off <<= 1) s += __shfl_xor(s, off, 64);
-        if (c < C8 && (c % lph) == 0) delta[(b * H + c / lph) * N + n] = s;
-    }
 }
 
 }  // namespace

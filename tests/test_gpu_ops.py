@@ -414,6 +414,42 @@ def test_attention_route(dev, N, hd, dt, p_drop, B, H, fwd, bwd):
     assert _attention_plans(body) == [(_capi.ME_PROF_ATTN_FWD, fwd), (_capi.ME_PROF_ATTN_BWD, bwd)]
 
 
+# the smallest shapes that cross each boundary of the 128-query x 64-key tiling, at every instantiated head width: one key, one tile + 1,
+# one block + 1 / + 2 (head_dim 64 / 128 / 72: below, at and between the widths), bf16 at HD 32 / 64 / 128 (N = 64 takes this route at
+# head_dim 128) and head_dim 96
+TILED_CASES = [(1, 8, "fp32", 0.1), (65, 8, "fp32", 0.0), (129, 64, "fp32", 0.0), (130, 128, "fp32", 0.0), (130, 72, "fp32", 0.1),
+               (65, 24, "bf16", 0.1), (129, 64, "bf16", 0.1), (64, 128, "bf16", 0.0), (70, 96, "bf16", 0.0)]
+
+
+@pytest.mark.parametrize("N,hd,dt,p_drop", TILED_CASES)
+def test_attention_generic_is_the_qkv_kernels(dev, N, hd, dt, p_drop):
+    """the generic route of me_attention_fwd / _bwd and me_attention_qkv_fwd / _bwd on the three column views of the same packed buffer run
+    the same tiled kernels: bit-identical out and lse, and in fp32 (both form delta = dO . O) bit-identical gradients.  The two bf16 backward
+    entry points form delta differently on purpose (attention_qkv.hip: attn_qkv_delta_kernel); each has its own tolerance test."""
+    B, H = 2, 3
+    C = H * hd
+    dtype = torch.bfloat16 if dt == "bf16" else torch.float32
+    scale = hd ** -0.5
+    qkv = rnd(B * N, 3 * C, seed=N + hd).to(dtype).to(dev)
+    do = rnd(B * N, C, seed=N + hd + 1).to(dtype).to(dev)
+    res = {}
+
+    def body():
+        res["out"], res["lse"] = ops.attention_fwd(qkv, B, N, H, hd, scale, True, p_drop=p_drop, seed=11)
+        res["dqkv"] = ops.attention_bwd(qkv, res["out"], do, res["lse"], B, N, H, hd, scale, p_drop=p_drop, seed=11)
+    assert _attention_plans(body) == [(_capi.ME_PROF_ATTN_FWD, GENERIC), (_capi.ME_PROF_ATTN_BWD, GENERIC)]
+    q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+    out, lse = ops.attention_qkv_fwd(q, k, v, B, N, N, H, hd, scale, need_lse=True, p_drop=p_drop, seed=11)
+    assert torch.equal(out, res["out"])
+    assert torch.equal(lse, res["lse"])
+    dqkv = torch.full_like(qkv, float("nan"))
+    ops.attention_qkv_bwd(q, k, v, out, do, lse, B, N, N, H, hd, scale, p_drop=p_drop, seed=11,
+                          grads=(dqkv[:, :C], dqkv[:, C:2 * C], dqkv[:, 2 * C:]))
+    assert not bool(torch.isnan(dqkv).any())
+    if dtype == torch.float32:
+        assert torch.equal(dqkv, res["dqkv"])
+
+
 def test_attention_route_padded_output_stride(dev):
     """ld_out = C + 4 (the C entry; the Python wrapper passes dense strides): not a multiple of 8, so the forward at N = 300, head_dim 64
     stays on the mid kernel where a dense output goes to the streaming one"""

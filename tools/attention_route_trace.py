@@ -6,8 +6,9 @@ two commits: run it at each, the two outputs must be byte-identical.
 
 It uses only names that both sides of such a comparison have: ops.attention_fwd / ops.attention_bwd, and the ctypes entry for the
 case with a padded output stride.  Under `rocprofv3 --kernel-trace -- python tools/attention_route_trace.py OUT` the kernel
-sequence (name, grid, workgroup, LDS bytes) is the record of which kernel each case took.  The cases are those of
-tests/test_gpu_ops.py::test_attention_route.  profiles/attention_route_equivalence.txt holds the record made with it."""
+sequence (name, grid, workgroup, LDS bytes) is the record of which kernel each case took.  The first cases are those of
+tests/test_gpu_ops.py::test_attention_route (profiles/attention_route_equivalence.txt holds the record made with them), the rest walk the
+generic route."""
 import hashlib
 import sys
 import time
@@ -24,7 +25,14 @@ CASES = [(64, 64, "bf16", 0.0, 2, 2), (64, 64, "fp32", 0.0, 2, 2), (65, 64, "bf1
          (257, 64, "bf16", 0.0, 2, 2), (512, 64, "bf16", 0.0, 2, 2), (257, 32, "bf16", 0.0, 2, 2), (300, 24, "bf16", 0.0, 2, 2),
          (513, 64, "bf16", 0.0, 2, 2), (700, 64, "bf16", 0.0, 2, 2), (592, 64, "bf16", 0.0, 2, 2), (1568, 64, "bf16", 0.0, 1, 1),
          (513, 32, "bf16", 0.0, 2, 2), (600, 24, "bf16", 0.0, 2, 2), (130, 128, "bf16", 0.0, 2, 2), (64, 128, "bf16", 0.0, 2, 2),
-         (65, 64, "fp32", 0.0, 2, 2), (197, 64, "bf16", 0.1, 2, 2), (100, 24, "bf16", 0.1, 2, 2)]
+         (65, 64, "fp32", 0.0, 2, 2), (197, 64, "bf16", 0.1, 2, 2), (100, 24, "bf16", 0.1, 2, 2),
+         # the generic route at every instantiation of the tiled kernels (HD 32 / 64 / 128, both dtypes) and every boundary of their tiling
+         # (one key, 64-key tile + 1, 128-query block + 1 / + 2, two blocks + 1), with and without dropout; appended, so the lines above stay
+         # comparable with older records
+         (1, 8, "fp32", 0.1, 2, 2), (65, 8, "fp32", 0.0, 2, 2), (129, 64, "fp32", 0.1, 2, 2), (130, 96, "fp32", 0.0, 2, 2),
+         (130, 128, "fp32", 0.0, 2, 2), (257, 128, "fp32", 0.1, 2, 2), (37, 12, "fp32", 0.1, 2, 2),
+         (65, 24, "bf16", 0.1, 2, 2), (129, 48, "bf16", 0.1, 2, 2), (130, 64, "bf16", 0.5, 2, 2), (257, 72, "bf16", 0.0, 2, 2),
+         (70, 96, "bf16", 0.0, 2, 2), (130, 128, "bf16", 0.1, 2, 2)]
 DT = {"bf16": torch.bfloat16, "fp32": torch.float32}
 
 

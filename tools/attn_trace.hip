@@ -1,5 +1,7 @@
 // Developer tool: phase timeline of the small-sequence attention kernels (s_memtime stamps per workgroup).
-//   hipcc --offload-arch=gfx950 -O3 -o tools/attn_trace tools/attn_trace.hip metatransformer_amd/csrc/api.hip
+// It compiles attention.hip with the stamps in; everything else that file calls (the tiled and tiny attention kernels, the profile scope,
+// the work counters) comes from the built library:
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/attn_trace tools/attn_trace.hip -Lmetatransformer_amd -lmetaenc '-Wl,-rpath,$ORIGIN/../metatransformer_amd'
 #define ME_ATTN_TRACE 1
 #include "../metatransformer_amd/csrc/attention.hip"
 #include <vector>
