@@ -24,6 +24,10 @@ namespace {
 // and dQ, phase B (a wave owns 32 keys) computes dK and dV from the same resident tiles -- no delta kernel, no second
 // pass over HBM.  Both phases recompute S and dP (7 MFMA products instead of the minimal 5); results are
 // deterministic (no atomics).
+//
+// The per-wave pieces below (rows32_* and Rows32Stage: a wave owns 32 rows, 8 waves to a workgroup) are shared by seven
+// kernels: attn_fwd_small / attn_bwd_small here, attn_fwd_mid / attn_bwd_mid (N <= 512) and attn_fwd_chunk /
+// attn_bwd_dq_chunk / attn_bwd_dkdv_chunk (N > 512) further down.  Those differ only in what is resident in LDS and when.
 // =====================================================================================================
 // developer instrumentation (tools/attn_trace.hip defines ME_ATTN_TRACE and includes this file): per-workgroup
 // s_memtime stamps at the phase boundaries; compiled out of libmetaenc.so
@@ -40,7 +44,7 @@ constexpr int SM_MINN = 64;      // at or below one 64-key tile the tiled kernel
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
-template <int HD, int NARR, int MAXN = SM_MAXN, int NTHR = SM_THREADS> struct SmallStage {
+template <int HD, int NARR, int MAXN = SM_MAXN, int NTHR = SM_THREADS> struct Rows32Stage {
     static constexpr int CPR = HD / 8;
     static constexpr int ITEMS = (MAXN * CPR) / NTHR;
     u32x4 v[NARR][ITEMS];
@@ -72,7 +76,106 @@ template <int HD, int NARR, int MAXN = SM_MAXN, int NTHR = SM_THREADS> struct Sm
             }
         }
     }
+    // load + store back to back (no prefetch distance): rows [0, N) of every array into NR rows of its tile
+    __device__ __forceinline__ void fill(const bf16_t* const (&base)[NARR], const int64_t (&ld)[NARR], char* const (&lds)[NARR], int NR,
+                                         int N, int hd, int tid) {
+        load(base, ld, N, hd, tid);
+        store(lds, NR, tid, N, hd);
+    }
 };
+
+template <int NDB> __device__ __forceinline__ void rows32_zero(f32x16 (&acc)[NDB]) {
+#pragma unroll
+    for (int db = 0; db < NDB; ++db)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[db][r] = 0.f;
+}
+
+// acc + a . b over the 8 bf16 of two 16-byte fragments, in element order (per dword: low half, high half).  The 16-row ring and
+// stream backward keep the same sum written out: through this function hipcc swaps the operands of their multiplies and adds (same
+// values, another instruction sequence), and those kernels are not to change
+__device__ __forceinline__ float bf16x8_dot_acc(float acc, u32x4 a, u32x4 b) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        acc += __uint_as_float(a[e] << 16) * __uint_as_float(b[e] << 16) +
+               __uint_as_float(a[e] & 0xffff0000u) * __uint_as_float(b[e] & 0xffff0000u);
+    return acc;
+}
+
+// Q fragments of one row straight from HBM (qrow: that row's head slice); chunks past hd are zeros
+template <int HD>
+__device__ __forceinline__ void rows32_load_q(const bf16_t* qrow, int hd, int h, bf16x8 (&qf)[Cfg<bf16_t, HD>::NKK]) {
+#pragma unroll
+    for (int kk = 0; kk < Cfg<bf16_t, HD>::NKK; ++kk) {
+        const int d = (2 * kk + h) * 8;
+        const bool ok = d < hd;
+        u32x4 raw = *reinterpret_cast<const u32x4*>(qrow + (ok ? d : 0));
+        raw = ok ? raw : zero4();
+        qf[kk] = *reinterpret_cast<bf16x8*>(&raw);
+    }
+}
+
+// {Q, dO} fragments of one row straight from HBM and delta = dO . O of that row (returned, summed over the two half-waves).
+// Padded queries (row_ok false, the pointers at a clamped row) get zero fragments: P = 0 through lse = +inf as well
+template <int HD>
+__device__ __forceinline__ float rows32_load_q_do_delta(const bf16_t* qrow, const bf16_t* dorow, const bf16_t* orow, bool row_ok, int hd,
+                                                        int h, bf16x8 (&qf)[Cfg<bf16_t, HD>::NKK], bf16x8 (&dof)[Cfg<bf16_t, HD>::NKK]) {
+    float del = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < Cfg<bf16_t, HD>::NKK; ++kk) {
+        const int d = (2 * kk + h) * 8;
+        const bool ok = d < hd;
+        const int dc = ok ? d : 0;
+        u32x4 rq = *reinterpret_cast<const u32x4*>(qrow + dc);
+        u32x4 rd = *reinterpret_cast<const u32x4*>(dorow + dc);
+        u32x4 ro = *reinterpret_cast<const u32x4*>(orow + dc);
+        const bool keep = ok && row_ok;
+        rq = keep ? rq : zero4(); rd = keep ? rd : zero4(); ro = keep ? ro : zero4();
+        qf[kk] = *reinterpret_cast<bf16x8*>(&rq);
+        dof[kk] = *reinterpret_cast<bf16x8*>(&rd);
+        del = bf16x8_dot_acc(del, ro, rd);
+    }
+    return del + __shfl_xor(del, 32, 64);
+}
+
+// A lane's row of accumulators (transposed layout: lane = row l31, registers = d) times mul as bf16, 8 bytes per store.  grow: that
+// row's head slice; the caller has checked that the row exists.  The pair form stores dK and dV under one d < hd test per quad: as
+// two single calls it measured +33 / +64 instructions in attn_bwd_dkdv_chunk_kernel<32 / 64> and +77 / +145 in attn_bwd_mid_kernel
+// (pair: 0 / 0 and +15 / +25), all outside the loops (profiles/attention_rows32_refactor.txt)
+__device__ __forceinline__ void rows32_store_quad(bf16_t* p, const f32x16& acc, int g, float mul) {
+    store_quad<bf16_t>(p, f32x4{acc[4 * g] * mul, acc[4 * g + 1] * mul, acc[4 * g + 2] * mul, acc[4 * g + 3] * mul});
+}
+template <int HD>
+__device__ __forceinline__ void rows32_store_row(bf16_t* grow, const f32x16 (&acc)[Cfg<bf16_t, HD>::NDB], float mul, int hd, int h) {
+#pragma unroll
+    for (int db = 0; db < Cfg<bf16_t, HD>::NDB; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int d = 32 * db + 8 * g + 4 * h;
+            if (d < hd) rows32_store_quad(grow + d, acc[db], g, mul);
+        }
+}
+template <int HD>
+__device__ __forceinline__ void rows32_store_row_pair(bf16_t* grow0, const f32x16 (&acc0)[Cfg<bf16_t, HD>::NDB], float mul0, bf16_t* grow1,
+                                                      const f32x16 (&acc1)[Cfg<bf16_t, HD>::NDB], float mul1, int hd, int h) {
+#pragma unroll
+    for (int db = 0; db < Cfg<bf16_t, HD>::NDB; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int d = 32 * db + 8 * g + 4 * h;
+            if (d < hd) {
+                rows32_store_quad(grow0 + d, acc0[db], g, mul0);
+                rows32_store_quad(grow1 + d, acc1[db], g, mul1);
+            }
+        }
+}
+
+// End of a forward row: l summed over the two half-waves, lse (natural log) written where `write` holds; returns 1 / l
+__device__ __forceinline__ float rows32_softmax_finish(float m_run, float l_run, float* __restrict__ lse, int64_t idx, bool write) {
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    if (lse && write) lse[idx] = (m_run + __builtin_amdgcn_logf(l_tot)) * LN2;
+    return 1.0f / l_tot;
+}
 
 // Write one wave's 32 x HD result (accumulators in the transposed layout: lane = row l31, registers = d) as bf16 rows.
 // Straight from registers this is a row-per-lane scatter of 8-byte pieces (64 rows touched per store instruction), which
@@ -107,7 +210,7 @@ __device__ __forceinline__ void store_rows_via_lds(char* scr, const f32x16 (&acc
 
 // one step of the forward over NU 32-key sub-tiles starting at key kv0 (Kt / Vt point at that row of the resident tiles)
 template <int HD, int NU, bool MASK>
-__device__ __forceinline__ void fwd_small_step(const char* Kt, const char* Vt, int kv0, int N,
+__device__ __forceinline__ void rows32_fwd_step(const char* Kt, const char* Vt, int kv0, int N,
                                                const bf16x8 (&qf)[Cfg<bf16_t, HD>::NKK], float sl, float& m_run,
                                                float& l_run, f32x16 (&o)[Cfg<bf16_t, HD>::NDB], int lane) {
     typedef Cfg<bf16_t, HD> C;
@@ -153,6 +256,128 @@ __device__ __forceinline__ void fwd_small_step(const char* Kt, const char* Vt, i
     }
 }
 
+// phase A step (wave owns 32 queries): NU 32-key sub-tiles starting at kv0
+template <int HD, int NU, bool MASK>
+__device__ __forceinline__ void rows32_dq_step(const char* Kt, const char* Vt, int kv0, int N,
+                                                 const bf16x8 (&qf)[Cfg<bf16_t, HD>::NKK],
+                                                 const bf16x8 (&dof)[Cfg<bf16_t, HD>::NKK], float sl, float lse2,
+                                                 float del, f32x16 (&dq)[Cfg<bf16_t, HD>::NDB], int lane) {
+    typedef Cfg<bf16_t, HD> C;
+    const int l31 = lane & 31, h = lane >> 5;
+    f32x16 s[2], dp[2];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { s[u][r] = 0.f; dp[u][r] = 0.f; }
+#pragma unroll
+        for (int kk = 0; kk < C::NKK; ++kk) {
+            s[u] = mma_chunk(rtile_chunk<bf16_t, HD>(Kt, 32 * u + l31, 2 * kk + h), qf[kk], s[u]);      // S^T[kv][q]
+            dp[u] = mma_chunk(rtile_chunk<bf16_t, HD>(Vt, 32 * u + l31, 2 * kk + h), dof[kk], dp[u]);   // dP^T[kv][q]
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float p = __builtin_amdgcn_exp2f(s[u][r] * sl - lse2);
+            if (MASK) p = (kv0 + 32 * u + acc_row(r, h) < N) ? p : 0.f;
+            dp[u][r] = p * (dp[u][r] - del);                                   // dS^T / scale (scale applied to dQ once)
+        }
+#pragma unroll
+    for (int c = 0; c < 2 * NU; ++c) {
+        const bf16x8 dsb = pack_chunk((const bf16_t*)nullptr, dp, c);
+#pragma unroll
+        for (int db = 0; db < C::NDB; ++db) dq[db] = mma_chunk(tr_chunk<HD>(Kt, 32 * db, c, lane), dsb, dq[db]);   // dQ^T[d][q]
+    }
+}
+
+// phase B step (wave owns 32 keys): NU 32-query sub-tiles starting at q0; lse_t / del_t point at q0 (log2-scaled lse,
+// +inf on padded queries so that P = 0 there).  Padded KEYS need no mask: a key is a lane here, and whatever a padded
+// lane accumulates stays in its own dK/dV columns, which are never stored.
+template <int HD, int NU>
+__device__ __forceinline__ void rows32_dkdv_step(const char* Qt, const char* dOt, const float* lse_t, const float* del_t,
+                                                  const bf16x8 (&kf)[Cfg<bf16_t, HD>::NKK],
+                                                  const bf16x8 (&vf)[Cfg<bf16_t, HD>::NKK], float sl,
+                                                  f32x16 (&dk)[Cfg<bf16_t, HD>::NDB], f32x16 (&dv)[Cfg<bf16_t, HD>::NDB],
+                                                  int lane) {
+    typedef Cfg<bf16_t, HD> C;
+    const int l31 = lane & 31, h = lane >> 5;
+    f32x16 s[2], dp[2];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { s[u][r] = 0.f; dp[u][r] = 0.f; }
+#pragma unroll
+        for (int kk = 0; kk < C::NKK; ++kk) {
+            s[u] = mma_chunk(rtile_chunk<bf16_t, HD>(Qt, 32 * u + l31, 2 * kk + h), kf[kk], s[u]);      // S[q][kv]
+            dp[u] = mma_chunk(rtile_chunk<bf16_t, HD>(dOt, 32 * u + l31, 2 * kk + h), vf[kk], dp[u]);   // dP[q][kv]
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 L = *reinterpret_cast<const f32x4*>(lse_t + 32 * u + 8 * g + 4 * h);
+            const f32x4 D = *reinterpret_cast<const f32x4*>(del_t + 32 * u + 8 * g + 4 * h);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r = 4 * g + e;
+                const float p = __builtin_amdgcn_exp2f(s[u][r] * sl - L[e]);
+                s[u][r] = p;                                   // P
+                dp[u][r] = p * (dp[u][r] - D[e]);              // dS / scale (scale applied to dK once)
+            }
+        }
+#pragma unroll
+    for (int c = 0; c < 2 * NU; ++c) {
+        const bf16x8 pb = pack_chunk((const bf16_t*)nullptr, s, c);
+        const bf16x8 dsb = pack_chunk((const bf16_t*)nullptr, dp, c);
+#pragma unroll
+        for (int db = 0; db < C::NDB; ++db) {
+            dv[db] = mma_chunk(tr_chunk<HD>(dOt, 32 * db, c, lane), pb, dv[db]);    // dV^T[d][kv]
+            dk[db] = mma_chunk(tr_chunk<HD>(Qt, 32 * db, c, lane), dsb, dk[db]);    // dK^T[d][kv]
+        }
+    }
+}
+
+// The walks: a wave takes its step over every 32-row sub-tile of the tiles in LDS, 64 rows at a time.  Forward and dQ walk `rows`
+// keys that start at key kv0 of N (resident tiles: 0, N, N): full 64-key steps, then the masked tail -- two sub-tiles when the last
+// one is partial, one when 32 or fewer keys are left.  dK/dV walks NS query sub-tiles (padded queries carry P = 0: no mask).
+template <int HD>
+__device__ __forceinline__ void rows32_fwd_walk(const char* Kt, const char* Vt, int kv0, int rows, int N,
+                                                const bf16x8 (&qf)[Cfg<bf16_t, HD>::NKK], float sl, float& m_run, float& l_run,
+                                                f32x16 (&o)[Cfg<bf16_t, HD>::NDB], int lane) {
+    constexpr int SUB = 32 * Cfg<bf16_t, HD>::RROW;
+    const int NS = (rows + 31) >> 5;
+    int t = 0;
+    for (; 32 * (t + 2) <= rows; t += 2) rows32_fwd_step<HD, 2, false>(Kt + t * SUB, Vt + t * SUB, kv0 + 32 * t, N, qf, sl, m_run, l_run, o, lane);
+    if (t + 2 <= NS)
+        rows32_fwd_step<HD, 2, true>(Kt + t * SUB, Vt + t * SUB, kv0 + 32 * t, N, qf, sl, m_run, l_run, o, lane);
+    else if (t < NS)
+        rows32_fwd_step<HD, 1, true>(Kt + t * SUB, Vt + t * SUB, kv0 + 32 * t, N, qf, sl, m_run, l_run, o, lane);
+}
+template <int HD>
+__device__ __forceinline__ void rows32_dq_walk(const char* Kt, const char* Vt, int kv0, int rows, int N,
+                                               const bf16x8 (&qf)[Cfg<bf16_t, HD>::NKK], const bf16x8 (&dof)[Cfg<bf16_t, HD>::NKK], float sl,
+                                               float lse2, float del, f32x16 (&dq)[Cfg<bf16_t, HD>::NDB], int lane) {
+    constexpr int SUB = 32 * Cfg<bf16_t, HD>::RROW;
+    const int NS = (rows + 31) >> 5;
+    int t = 0;
+    for (; 32 * (t + 2) <= rows; t += 2) rows32_dq_step<HD, 2, false>(Kt + t * SUB, Vt + t * SUB, kv0 + 32 * t, N, qf, dof, sl, lse2, del, dq, lane);
+    if (t + 2 <= NS)
+        rows32_dq_step<HD, 2, true>(Kt + t * SUB, Vt + t * SUB, kv0 + 32 * t, N, qf, dof, sl, lse2, del, dq, lane);
+    else if (t < NS)
+        rows32_dq_step<HD, 1, true>(Kt + t * SUB, Vt + t * SUB, kv0 + 32 * t, N, qf, dof, sl, lse2, del, dq, lane);
+}
+template <int HD>
+__device__ __forceinline__ void rows32_dkdv_walk(const char* Qt, const char* dOt, const float* lse_t, const float* del_t, int NS,
+                                                 const bf16x8 (&kf)[Cfg<bf16_t, HD>::NKK], const bf16x8 (&vf)[Cfg<bf16_t, HD>::NKK], float sl,
+                                                 f32x16 (&dk)[Cfg<bf16_t, HD>::NDB], f32x16 (&dv)[Cfg<bf16_t, HD>::NDB], int lane) {
+    constexpr int SUB = 32 * Cfg<bf16_t, HD>::RROW;
+    int t = 0;
+    for (; t + 2 <= NS; t += 2) rows32_dkdv_step<HD, 2>(Qt + t * SUB, dOt + t * SUB, lse_t + 32 * t, del_t + 32 * t, kf, vf, sl, dk, dv, lane);
+    if (t < NS) rows32_dkdv_step<HD, 1>(Qt + t * SUB, dOt + t * SUB, lse_t + 32 * t, del_t + 32 * t, kf, vf, sl, dk, dv, lane);
+}
+
 // Persistent: a workgroup walks (batch, head) items with stride gridDim.x.  While item i is computed, the K/V rows and
 // Q fragments of item i+1 are already in flight into registers; they are parked in LDS once every wave is done with
 // item i -- HBM latency and the bursty all-CUs-load-at-once phase hide behind the math.
@@ -177,7 +402,7 @@ __global__ __launch_bounds__(SM_THREADS) void attn_fwd_small_kernel(const bf16_t
     const float sl = scale * LOG2E;
     const int64_t ldv[2] = {ld, ld};
 
-    SmallStage<HD, 2> st;
+    Rows32Stage<HD, 2> st;
     bf16x8 qf[C::NKK], qn[C::NKK];
     auto fresh_tid = [&]() { int t = tid; asm volatile("" : "+v"(t)); return t; };
     auto issue = [&](int it, bf16x8 (&qdst)[C::NKK]) {
@@ -216,25 +441,13 @@ __global__ __launch_bounds__(SM_THREADS) void attn_fwd_small_kernel(const bf16_t
         issue(nxt, qn);
         if (active) {
             f32x16 o[C::NDB];
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+            rows32_zero(o);
             float m_run = -INFINITY, l_run = 0.f;
-            int t = 0;
-            for (; 32 * (t + 2) <= N; t += 2)      // full 64-key steps
-                fwd_small_step<HD, 2, false>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, 32 * t, N, qf, sl, m_run, l_run, o, lane);
-            if (t + 2 <= NS) {
-                fwd_small_step<HD, 2, true>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, 32 * t, N, qf, sl, m_run, l_run, o, lane);
-            } else if (t < NS) {
-                fwd_small_step<HD, 1, true>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, 32 * t, N, qf, sl, m_run, l_run, o, lane);
-            }
+            rows32_fwd_walk<HD>(Ks, Vs, 0, N, N, qf, sl, m_run, l_run, o, lane);
             TRACE_STAMP(it, 1);
-            const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-            const float inv = 1.0f / l_tot;
             const int b = it / H, head = it % H;
+            const float inv = rows32_softmax_finish(m_run, l_run, lse, ((int64_t)b * H + head) * N + q, h == 0 && q < N);
             store_rows_via_lds<HD>(scr, o, inv, out + ((int64_t)b * N + 32 * wave) * ldo + head * hd, ldo, N - 32 * wave, hd, lane);
-            if (lse && h == 0 && q < N) lse[((int64_t)b * H + head) * N + q] = (m_run + __builtin_amdgcn_logf(l_tot)) * LN2;
         }
         TRACE_STAMP(it, 2);
         __syncthreads();      // every wave is done with the K/V tiles of this item
@@ -532,89 +745,6 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_ring16_kernel(const bf16
     }
 }
 
-// phase A step (wave owns 32 queries): NU 32-key sub-tiles starting at kv0
-template <int HD, int NU, bool MASK>
-__device__ __forceinline__ void bwd_small_q_step(const char* Kt, const char* Vt, int kv0, int N,
-                                                 const bf16x8 (&qf)[Cfg<bf16_t, HD>::NKK],
-                                                 const bf16x8 (&dof)[Cfg<bf16_t, HD>::NKK], float sl, float lse2,
-                                                 float del, f32x16 (&dq)[Cfg<bf16_t, HD>::NDB], int lane) {
-    typedef Cfg<bf16_t, HD> C;
-    const int l31 = lane & 31, h = lane >> 5;
-    f32x16 s[2], dp[2];
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { s[u][r] = 0.f; dp[u][r] = 0.f; }
-#pragma unroll
-        for (int kk = 0; kk < C::NKK; ++kk) {
-            s[u] = mma_chunk(rtile_chunk<bf16_t, HD>(Kt, 32 * u + l31, 2 * kk + h), qf[kk], s[u]);      // S^T[kv][q]
-            dp[u] = mma_chunk(rtile_chunk<bf16_t, HD>(Vt, 32 * u + l31, 2 * kk + h), dof[kk], dp[u]);   // dP^T[kv][q]
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < NU; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float p = __builtin_amdgcn_exp2f(s[u][r] * sl - lse2);
-            if (MASK) p = (kv0 + 32 * u + acc_row(r, h) < N) ? p : 0.f;
-            dp[u][r] = p * (dp[u][r] - del);                                   // dS^T / scale (scale applied to dQ once)
-        }
-#pragma unroll
-    for (int c = 0; c < 2 * NU; ++c) {
-        const bf16x8 dsb = pack_chunk((const bf16_t*)nullptr, dp, c);
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db) dq[db] = mma_chunk(tr_chunk<HD>(Kt, 32 * db, c, lane), dsb, dq[db]);   // dQ^T[d][q]
-    }
-}
-
-// phase B step (wave owns 32 keys): NU 32-query sub-tiles starting at q0; lse_t / del_t point at q0 (log2-scaled lse,
-// +inf on padded queries so that P = 0 there).  Padded KEYS need no mask: a key is a lane here, and whatever a padded
-// lane accumulates stays in its own dK/dV columns, which are never stored.
-template <int HD, int NU>
-__device__ __forceinline__ void bwd_small_kv_step(const char* Qt, const char* dOt, const float* lse_t, const float* del_t,
-                                                  const bf16x8 (&kf)[Cfg<bf16_t, HD>::NKK],
-                                                  const bf16x8 (&vf)[Cfg<bf16_t, HD>::NKK], float sl,
-                                                  f32x16 (&dk)[Cfg<bf16_t, HD>::NDB], f32x16 (&dv)[Cfg<bf16_t, HD>::NDB],
-                                                  int lane) {
-    typedef Cfg<bf16_t, HD> C;
-    const int l31 = lane & 31, h = lane >> 5;
-    f32x16 s[2], dp[2];
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { s[u][r] = 0.f; dp[u][r] = 0.f; }
-#pragma unroll
-        for (int kk = 0; kk < C::NKK; ++kk) {
-            s[u] = mma_chunk(rtile_chunk<bf16_t, HD>(Qt, 32 * u + l31, 2 * kk + h), kf[kk], s[u]);      // S[q][kv]
-            dp[u] = mma_chunk(rtile_chunk<bf16_t, HD>(dOt, 32 * u + l31, 2 * kk + h), vf[kk], dp[u]);   // dP[q][kv]
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < NU; ++u)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 L = *reinterpret_cast<const f32x4*>(lse_t + 32 * u + 8 * g + 4 * h);
-            const f32x4 D = *reinterpret_cast<const f32x4*>(del_t + 32 * u + 8 * g + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int r = 4 * g + e;
-                const float p = __builtin_amdgcn_exp2f(s[u][r] * sl - L[e]);
-                s[u][r] = p;                                   // P
-                dp[u][r] = p * (dp[u][r] - D[e]);              // dS / scale (scale applied to dK once)
-            }
-        }
-#pragma unroll
-    for (int c = 0; c < 2 * NU; ++c) {
-        const bf16x8 pb = pack_chunk((const bf16_t*)nullptr, s, c);
-        const bf16x8 dsb = pack_chunk((const bf16_t*)nullptr, dp, c);
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db) {
-            dv[db] = mma_chunk(tr_chunk<HD>(dOt, 32 * db, c, lane), pb, dv[db]);    // dV^T[d][kv]
-            dk[db] = mma_chunk(tr_chunk<HD>(Qt, 32 * db, c, lane), dsb, dk[db]);    // dK^T[d][kv]
-        }
-    }
-}
-
 // One workgroup per (batch, head); LDS holds {Q, K, V, dO} (4 x 32 KB at N = 197).  Once every wave has lifted its K/V row
 // fragments for phase B the K/V tiles are dead, and wave w reuses rows [32w, 32w+32) of them as its private scratch for
 // the coalesced row stores of dQ, dK and dV.
@@ -651,7 +781,7 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_small_kernel(const bf16_t
     const int trace_slot = blockIdx.y * gridDim.x + blockIdx.x;
     (void)trace_slot;
     TRACE_STAMP(trace_slot, 0);
-    SmallStage<HD, 4> st;
+    Rows32Stage<HD, 4> st;
     {
         const bf16_t* const bases[4] = {qptr, qptr + Cdim, qptr + 2 * Cdim, doptr};
         const int64_t ldv[4] = {ld, ld, ld, lddo};
@@ -686,11 +816,7 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_small_kernel(const bf16_t
         for (int kk = 0; kk < C::NKK; ++kk) {
             qf[kk] = rtile_chunk<bf16_t, HD>(Qs, row, 2 * kk + h);
             dof[kk] = rtile_chunk<bf16_t, HD>(dOs, row, 2 * kk + h);
-            const u32x4 rd = *reinterpret_cast<const u32x4*>(&dof[kk]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                del += __uint_as_float(of[kk][e] << 16) * __uint_as_float(rd[e] << 16) +
-                       __uint_as_float(of[kk][e] & 0xffff0000u) * __uint_as_float(rd[e] & 0xffff0000u);
+            del = bf16x8_dot_acc(del, of[kk], *reinterpret_cast<const u32x4*>(&dof[kk]));
         }
         del += __shfl_xor(del, 32, 64);
         if (h == 0) {
@@ -698,17 +824,8 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_small_kernel(const bf16_t
             if (row_ok && delta) delta[bh + row] = del;
         }
         const float lse2 = lse_s[row];      // +inf on padded queries -> P = 0
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dq[db][r] = 0.f;
-        int t = 0;
-        for (; 32 * (t + 2) <= N; t += 2)
-            bwd_small_q_step<HD, 2, false>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, 32 * t, N, qf, dof, sl, lse2, del, dq, lane);
-        if (t + 2 <= NS)
-            bwd_small_q_step<HD, 2, true>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, 32 * t, N, qf, dof, sl, lse2, del, dq, lane);
-        else if (t < NS)
-            bwd_small_q_step<HD, 1, true>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, 32 * t, N, qf, dof, sl, lse2, del, dq, lane);
+        rows32_zero(dq);
+        rows32_dq_walk<HD>(Ks, Vs, 0, N, N, qf, dof, sl, lse2, del, dq, lane);
     }
     TRACE_STAMP(trace_slot, 2);
     __syncthreads();      // del_s complete; every phase-A loop over the K/V tiles is finished
@@ -732,15 +849,9 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_small_kernel(const bf16_t
     TRACE_STAMP(trace_slot, 4);
     // ---- phase B: dK and dV for the 32 keys of this wave
     f32x16 dk[C::NDB], dv[C::NDB];
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { dk[db][r] = 0.f; dv[db][r] = 0.f; }
-    int t = 0;
-    for (; t + 2 <= NS; t += 2)
-        bwd_small_kv_step<HD, 2>(Qs + 32 * t * C::RROW, dOs + 32 * t * C::RROW, lse_s + 32 * t, del_s + 32 * t, kf, vf, sl, dk, dv, lane);
-    if (t < NS)
-        bwd_small_kv_step<HD, 1>(Qs + 32 * t * C::RROW, dOs + 32 * t * C::RROW, lse_s + 32 * t, del_s + 32 * t, kf, vf, sl, dk, dv, lane);
+    rows32_zero(dk);
+    rows32_zero(dv);
+    rows32_dkdv_walk<HD>(Qs, dOs, lse_s, del_s, NS, kf, vf, sl, dk, dv, lane);
     TRACE_STAMP(trace_slot, 5);
     store_rows_via_lds<HD>(scr0, dk, scale, grow0 + Cdim, lddq, N - 32 * wave, hd, lane);
     store_rows_via_lds<HD>(scr1, dv, 1.0f, grow0 + 2 * Cdim, lddq, N - 32 * wave, hd, lane);
@@ -1942,56 +2053,20 @@ __global__ __launch_bounds__(NTHR) void attn_fwd_mid_kernel(const bf16_t* __rest
     const int head = blockIdx.x, b = blockIdx.y;
     const int Cdim = H * hd;
     const bf16_t* qptr = qkv + (int64_t)b * N * ld + head * hd;
-    {
-        SmallStage<HD, 2, MAXN, NTHR> st;
-        const bf16_t* const bases[2] = {qptr + Cdim, qptr + 2 * Cdim};
-        const int64_t ldv[2] = {ld, ld};
-        st.load(bases, ldv, N, hd, tid);
-        char* const tiles[2] = {Ks, Vs};
-        st.store(tiles, NR, tid, N, hd);
-    }
+    Rows32Stage<HD, 2, MAXN, NTHR>().fill({qptr + Cdim, qptr + 2 * Cdim}, {ld, ld}, {Ks, Vs}, NR, N, hd, tid);
     __syncthreads();
     const float sl = scale * LOG2E;
     for (int sub = wave; sub < NS; sub += NTHR / 64) {      // wave-uniform
         const int q = 32 * sub + l31;
         const int qrow = (q < N) ? q : N - 1;
         bf16x8 qf[C::NKK];
-#pragma unroll
-        for (int kk = 0; kk < C::NKK; ++kk) {
-            const int d = (2 * kk + h) * 8;
-            const bool ok = d < hd;
-            u32x4 raw = *reinterpret_cast<const u32x4*>(qptr + (int64_t)qrow * ld + (ok ? d : 0));
-            raw = ok ? raw : zero4();
-            qf[kk] = *reinterpret_cast<bf16x8*>(&raw);
-        }
+        rows32_load_q<HD>(qptr + (int64_t)qrow * ld, hd, h, qf);
         f32x16 o[C::NDB];
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+        rows32_zero(o);
         float m_run = -INFINITY, l_run = 0.f;
-        int t = 0;
-        for (; 32 * (t + 2) <= N; t += 2)
-            fwd_small_step<HD, 2, false>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, 32 * t, N, qf, sl, m_run, l_run, o, lane);
-        if (t + 2 <= NS)
-            fwd_small_step<HD, 2, true>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, 32 * t, N, qf, sl, m_run, l_run, o, lane);
-        else if (t < NS)
-            fwd_small_step<HD, 1, true>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, 32 * t, N, qf, sl, m_run, l_run, o, lane);
-        const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-        const float inv = 1.0f / l_tot;
-        if (q < N) {
-            bf16_t* orow = out + ((int64_t)b * N + q) * ldo + head * hd;
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d = 32 * db + 8 * g + 4 * h;
-                    if (d < hd)
-                        store_quad<bf16_t>(orow + d, f32x4{o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv,
-                                                           o[db][4 * g + 3] * inv});
-                }
-            if (lse && h == 0) lse[((int64_t)b * H + head) * N + q] = (m_run + __builtin_amdgcn_logf(l_tot)) * LN2;
-        }
+        rows32_fwd_walk<HD>(Ks, Vs, 0, N, N, qf, sl, m_run, l_run, o, lane);
+        const float inv = rows32_softmax_finish(m_run, l_run, lse, ((int64_t)b * H + head) * N + q, h == 0 && q < N);
+        if (q < N) rows32_store_row<HD>(out + ((int64_t)b * N + q) * ldo + head * hd, o, inv, hd, h);
     }
 }
 
@@ -2019,14 +2094,7 @@ __global__ __launch_bounds__(NTHR) void attn_bwd_mid_kernel(const bf16_t* __rest
     const bf16_t* optr = out + (int64_t)b * N * ldo + head * hd;
     const int64_t bh = ((int64_t)b * H + head) * N;
     const float sl = scale * LOG2E;
-    {
-        SmallStage<HD, 2, MAXN, NTHR> st;
-        const bf16_t* const bases[2] = {qptr + Cdim, qptr + 2 * Cdim};
-        const int64_t ldv[2] = {ld, ld};
-        st.load(bases, ldv, N, hd, tid);
-        char* const tiles[2] = {T0, T1};
-        st.store(tiles, NR, tid, N, hd);
-    }
+    Rows32Stage<HD, 2, MAXN, NTHR>().fill({qptr + Cdim, qptr + 2 * Cdim}, {ld, ld}, {T0, T1}, NR, N, hd, tid);
     for (int i = tid; i < MAXN; i += NTHR) lse_s[i] = i < N ? lse[bh + i] * LOG2E : INFINITY;
     __syncthreads();
 
@@ -2036,54 +2104,17 @@ __global__ __launch_bounds__(NTHR) void attn_bwd_mid_kernel(const bf16_t* __rest
         const bool row_ok = row < N;
         const int rowc = row_ok ? row : N - 1;
         bf16x8 qf[C::NKK], dof[C::NKK];
-        float del = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < C::NKK; ++kk) {
-            const int d = (2 * kk + h) * 8;
-            const bool ok = d < hd;
-            const int dc = ok ? d : 0;
-            u32x4 rq = *reinterpret_cast<const u32x4*>(qptr + (int64_t)rowc * ld + dc);
-            u32x4 rd = *reinterpret_cast<const u32x4*>(doptr + (int64_t)rowc * lddo + dc);
-            u32x4 ro = *reinterpret_cast<const u32x4*>(optr + (int64_t)rowc * ldo + dc);
-            const bool keep = ok && row_ok;      // padded queries: zero fragments (P = 0 through lse = +inf as well)
-            rq = keep ? rq : zero4(); rd = keep ? rd : zero4(); ro = keep ? ro : zero4();
-            qf[kk] = *reinterpret_cast<bf16x8*>(&rq);
-            dof[kk] = *reinterpret_cast<bf16x8*>(&rd);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                del += __uint_as_float(ro[e] << 16) * __uint_as_float(rd[e] << 16) +
-                       __uint_as_float(ro[e] & 0xffff0000u) * __uint_as_float(rd[e] & 0xffff0000u);
-        }
-        del += __shfl_xor(del, 32, 64);
+        const float del = rows32_load_q_do_delta<HD>(qptr + (int64_t)rowc * ld, doptr + (int64_t)rowc * lddo, optr + (int64_t)rowc * ldo,
+                                                     row_ok, hd, h, qf, dof);
         if (h == 0) {
             del_s[row] = del;
             if (row_ok && delta) delta[bh + row] = del;
         }
         const float lse2 = lse_s[row];
         f32x16 dq[C::NDB];
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dq[db][r] = 0.f;
-        int t = 0;
-        for (; 32 * (t + 2) <= N; t += 2)
-            bwd_small_q_step<HD, 2, false>(T0 + 32 * t * C::RROW, T1 + 32 * t * C::RROW, 32 * t, N, qf, dof, sl, lse2, del, dq, lane);
-        if (t + 2 <= NS)
-            bwd_small_q_step<HD, 2, true>(T0 + 32 * t * C::RROW, T1 + 32 * t * C::RROW, 32 * t, N, qf, dof, sl, lse2, del, dq, lane);
-        else if (t < NS)
-            bwd_small_q_step<HD, 1, true>(T0 + 32 * t * C::RROW, T1 + 32 * t * C::RROW, 32 * t, N, qf, dof, sl, lse2, del, dq, lane);
-        if (row_ok) {
-            bf16_t* dqrow = dqkv + ((int64_t)b * N + row) * lddq + head * hd;
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d = 32 * db + 8 * g + 4 * h;
-                    if (d < hd)
-                        store_quad<bf16_t>(dqrow + d, f32x4{dq[db][4 * g] * scale, dq[db][4 * g + 1] * scale,
-                                                            dq[db][4 * g + 2] * scale, dq[db][4 * g + 3] * scale});
-                }
-        }
+        rows32_zero(dq);
+        rows32_dq_walk<HD>(T0, T1, 0, N, N, qf, dof, sl, lse2, del, dq, lane);
+        if (row_ok) rows32_store_row<HD>(dqkv + ((int64_t)b * N + row) * lddq + head * hd, dq, scale, hd, h);
     }
     // ---- hand-over: lift the K / V row fragments of my key groups, then refill the two tiles with Q / dO
     constexpr int MAXG = MAXN / 32 / NWAVE;      // 2
@@ -2099,14 +2130,7 @@ __global__ __launch_bounds__(NTHR) void attn_bwd_mid_kernel(const bf16_t* __rest
         }
     }
     __syncthreads();      // everyone is done with K / V (pass A loops and the lifts above); del_s is complete
-    {
-        SmallStage<HD, 2, MAXN, NTHR> st;
-        const bf16_t* const bases[2] = {qptr, doptr};
-        const int64_t ldv[2] = {ld, lddo};
-        st.load(bases, ldv, N, hd, tid);
-        char* const tiles[2] = {T0, T1};
-        st.store(tiles, NR, tid, N, hd);
-    }
+    Rows32Stage<HD, 2, MAXN, NTHR>().fill({qptr, doptr}, {ld, lddo}, {T0, T1}, NR, N, hd, tid);
     __syncthreads();
     // ---- pass B (Q / dO resident): dK, dV, a wave walks its 32-key groups
 #pragma unroll
@@ -2115,29 +2139,12 @@ __global__ __launch_bounds__(NTHR) void attn_bwd_mid_kernel(const bf16_t* __rest
         if (sub >= NS) break;      // wave-uniform
         const int row = 32 * sub + l31;
         f32x16 dk[C::NDB], dv[C::NDB];
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { dk[db][r] = 0.f; dv[db][r] = 0.f; }
-        int t = 0;
-        for (; t + 2 <= NS; t += 2)
-            bwd_small_kv_step<HD, 2>(T0 + 32 * t * C::RROW, T1 + 32 * t * C::RROW, lse_s + 32 * t, del_s + 32 * t, kf[g], vf[g], sl, dk, dv, lane);
-        if (t < NS)
-            bwd_small_kv_step<HD, 1>(T0 + 32 * t * C::RROW, T1 + 32 * t * C::RROW, lse_s + 32 * t, del_s + 32 * t, kf[g], vf[g], sl, dk, dv, lane);
+        rows32_zero(dk);
+        rows32_zero(dv);
+        rows32_dkdv_walk<HD>(T0, T1, lse_s, del_s, NS, kf[g], vf[g], sl, dk, dv, lane);
         if (row < N) {
             bf16_t* dkrow = dqkv + ((int64_t)b * N + row) * lddq + Cdim + head * hd;
-            bf16_t* dvrow = dkrow + Cdim;
-#pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const int d = 32 * db + 8 * gq + 4 * h;
-                    if (d < hd) {
-                        store_quad<bf16_t>(dkrow + d, f32x4{dk[db][4 * gq] * scale, dk[db][4 * gq + 1] * scale,
-                                                            dk[db][4 * gq + 2] * scale, dk[db][4 * gq + 3] * scale});
-                        store_quad<bf16_t>(dvrow + d, f32x4{dv[db][4 * gq], dv[db][4 * gq + 1], dv[db][4 * gq + 2], dv[db][4 * gq + 3]});
-                    }
-                }
+            rows32_store_row_pair<HD>(dkrow, dk, scale, dkrow + Cdim, dv, 1.0f, hd, h);
         }
     }
 }
@@ -2170,59 +2177,22 @@ __global__ __launch_bounds__(SM_THREADS) void attn_fwd_chunk_kernel(const bf16_t
     const bool active = blockIdx.x * CH_ROWS + 32 * wave < N;      // wave-uniform
     const int qrow = (q < N) ? q : N - 1;
     bf16x8 qf[C::NKK];
-#pragma unroll
-    for (int kk = 0; kk < C::NKK; ++kk) {
-        const int d = (2 * kk + h) * 8;
-        const bool ok = d < hd;
-        u32x4 raw = *reinterpret_cast<const u32x4*>(qptr + (int64_t)qrow * ld + (ok ? d : 0));
-        raw = ok ? raw : zero4();
-        qf[kk] = *reinterpret_cast<bf16x8*>(&raw);
-    }
+    rows32_load_q<HD>(qptr + (int64_t)qrow * ld, hd, h, qf);
     f32x16 o[C::NDB];
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+    rows32_zero(o);
     float m_run = -INFINITY, l_run = 0.f;
     const float sl = scale * LOG2E;
     for (int kv0 = 0; kv0 < N; kv0 += CH_ROWS) {
         const int rows = N - kv0 < CH_ROWS ? N - kv0 : CH_ROWS;
-        const int NSc = (rows + 31) >> 5;
         __syncthreads();      // the previous chunk is consumed
-        {
-            SmallStage<HD, 2> st;
-            const bf16_t* const bases[2] = {qptr + Cdim + (int64_t)kv0 * ld, qptr + 2 * Cdim + (int64_t)kv0 * ld};
-            const int64_t ldv[2] = {ld, ld};
-            st.load(bases, ldv, rows, hd, tid);
-            char* const tiles[2] = {Ks, Vs};
-            st.store(tiles, NSc * 32, tid, rows, hd);
-        }
+        Rows32Stage<HD, 2>().fill({qptr + Cdim + (int64_t)kv0 * ld, qptr + 2 * Cdim + (int64_t)kv0 * ld}, {ld, ld}, {Ks, Vs},
+                                  (rows + 31) / 32 * 32, rows, hd, tid);
         __syncthreads();
-        if (!active) continue;
-        int t = 0;
-        for (; 32 * (t + 2) <= rows; t += 2)
-            fwd_small_step<HD, 2, false>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, kv0 + 32 * t, N, qf, sl, m_run, l_run, o, lane);
-        if (t + 2 <= NSc)
-            fwd_small_step<HD, 2, true>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, kv0 + 32 * t, N, qf, sl, m_run, l_run, o, lane);
-        else if (t < NSc)
-            fwd_small_step<HD, 1, true>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, kv0 + 32 * t, N, qf, sl, m_run, l_run, o, lane);
+        if (active) rows32_fwd_walk<HD>(Ks, Vs, kv0, rows, N, qf, sl, m_run, l_run, o, lane);
     }
     if (!active) return;
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
-    if (q < N) {
-        bf16_t* orow = out + ((int64_t)b * N + q) * ldo + head * hd;
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = 32 * db + 8 * g + 4 * h;
-                if (d < hd)
-                    store_quad<bf16_t>(orow + d, f32x4{o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv,
-                                                       o[db][4 * g + 3] * inv});
-            }
-        if (lse && h == 0) lse[((int64_t)b * H + head) * N + q] = (m_run + __builtin_amdgcn_logf(l_tot)) * LN2;
-    }
+    const float inv = rows32_softmax_finish(m_run, l_run, lse, ((int64_t)b * H + head) * N + q, h == 0 && q < N);
+    if (q < N) rows32_store_row<HD>(out + ((int64_t)b * N + q) * ldo + head * hd, o, inv, hd, h);
 }
 
 // backward pass 1: delta and dQ for 256 queries; K/V stream in chunks
@@ -2250,66 +2220,22 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_dq_chunk_kernel(const bf1
     const bool row_ok = row < N;
     const int rowc = row_ok ? row : N - 1;
     bf16x8 qf[C::NKK], dof[C::NKK];
-    float del = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < C::NKK; ++kk) {
-        const int d = (2 * kk + h) * 8;
-        const bool ok = d < hd;
-        const int dc = ok ? d : 0;
-        u32x4 rq = *reinterpret_cast<const u32x4*>(qptr + (int64_t)rowc * ld + dc);
-        u32x4 rd = *reinterpret_cast<const u32x4*>(doptr + (int64_t)rowc * lddo + dc);
-        u32x4 ro = *reinterpret_cast<const u32x4*>(optr + (int64_t)rowc * ldo + dc);
-        const bool keep = ok && row_ok;
-        rq = keep ? rq : zero4(); rd = keep ? rd : zero4(); ro = keep ? ro : zero4();
-        qf[kk] = *reinterpret_cast<bf16x8*>(&rq);
-        dof[kk] = *reinterpret_cast<bf16x8*>(&rd);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            del += __uint_as_float(ro[e] << 16) * __uint_as_float(rd[e] << 16) +
-                   __uint_as_float(ro[e] & 0xffff0000u) * __uint_as_float(rd[e] & 0xffff0000u);
-    }
-    del += __shfl_xor(del, 32, 64);
+    const float del = rows32_load_q_do_delta<HD>(qptr + (int64_t)rowc * ld, doptr + (int64_t)rowc * lddo, optr + (int64_t)rowc * ldo, row_ok,
+                                                 hd, h, qf, dof);
     if (h == 0 && row_ok) delta[bh + row] = del;
     const float lse2 = row_ok ? lse[bh + row] * LOG2E : INFINITY;      // padded queries: P = 0
     const float sl = scale * LOG2E;
     f32x16 dq[C::NDB];
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dq[db][r] = 0.f;
+    rows32_zero(dq);
     for (int kv0 = 0; kv0 < N; kv0 += CH_ROWS) {
         const int rows = N - kv0 < CH_ROWS ? N - kv0 : CH_ROWS;
-        const int NSc = (rows + 31) >> 5;
         __syncthreads();
-        {
-            SmallStage<HD, 2> st;
-            const bf16_t* const bases[2] = {qptr + Cdim + (int64_t)kv0 * ld, qptr + 2 * Cdim + (int64_t)kv0 * ld};
-            const int64_t ldv[2] = {ld, ld};
-            st.load(bases, ldv, rows, hd, tid);
-            char* const tiles[2] = {Ks, Vs};
-            st.store(tiles, NSc * 32, tid, rows, hd);
-        }
+        Rows32Stage<HD, 2>().fill({qptr + Cdim + (int64_t)kv0 * ld, qptr + 2 * Cdim + (int64_t)kv0 * ld}, {ld, ld}, {Ks, Vs},
+                                  (rows + 31) / 32 * 32, rows, hd, tid);
         __syncthreads();
-        if (!active) continue;
-        int t = 0;
-        for (; 32 * (t + 2) <= rows; t += 2)
-            bwd_small_q_step<HD, 2, false>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, kv0 + 32 * t, N, qf, dof, sl, lse2, del, dq, lane);
-        if (t + 2 <= NSc)
-            bwd_small_q_step<HD, 2, true>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, kv0 + 32 * t, N, qf, dof, sl, lse2, del, dq, lane);
-        else if (t < NSc)
-            bwd_small_q_step<HD, 1, true>(Ks + 32 * t * C::RROW, Vs + 32 * t * C::RROW, kv0 + 32 * t, N, qf, dof, sl, lse2, del, dq, lane);
+        if (active) rows32_dq_walk<HD>(Ks, Vs, kv0, rows, N, qf, dof, sl, lse2, del, dq, lane);
     }
-    if (!active || !row_ok) return;
-    bf16_t* dqrow = dqkv + ((int64_t)b * N + row) * lddq + head * hd;
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d = 32 * db + 8 * g + 4 * h;
-            if (d < hd)
-                store_quad<bf16_t>(dqrow + d, f32x4{dq[db][4 * g] * scale, dq[db][4 * g + 1] * scale, dq[db][4 * g + 2] * scale,
-                                                    dq[db][4 * g + 3] * scale});
-        }
+    if (active && row_ok) rows32_store_row<HD>(dqkv + ((int64_t)b * N + row) * lddq + head * hd, dq, scale, hd, h);
 }
 
 // backward pass 2: dK and dV for 256 keys; Q / dO (and their lse / delta) stream in chunks
@@ -2351,49 +2277,24 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_dkdv_chunk_kernel(const b
     }
     const float sl = scale * LOG2E;
     f32x16 dk[C::NDB], dv[C::NDB];
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { dk[db][r] = 0.f; dv[db][r] = 0.f; }
+    rows32_zero(dk);
+    rows32_zero(dv);
     for (int q0 = 0; q0 < N; q0 += CH_ROWS) {
         const int rows = N - q0 < CH_ROWS ? N - q0 : CH_ROWS;
         const int NSc = (rows + 31) >> 5;
         __syncthreads();
-        {
-            SmallStage<HD, 2> st;
-            const bf16_t* const bases[2] = {qptr + (int64_t)q0 * ld, doptr + (int64_t)q0 * lddo};
-            const int64_t ldv[2] = {ld, lddo};
-            st.load(bases, ldv, rows, hd, tid);
-            char* const tiles[2] = {Qs, dOs};
-            st.store(tiles, NSc * 32, tid, rows, hd);
-        }
+        Rows32Stage<HD, 2>().fill({qptr + (int64_t)q0 * ld, doptr + (int64_t)q0 * lddo}, {ld, lddo}, {Qs, dOs}, NSc * 32, rows, hd, tid);
         if (tid < CH_ROWS) {
             const bool ok = tid < rows;
             lse_s[tid] = ok ? lse[bh + q0 + tid] * LOG2E : INFINITY;      // padded queries: P = 0
             del_s[tid] = ok ? delta[bh + q0 + tid] : 0.f;
         }
         __syncthreads();
-        if (!active) continue;
-        int t = 0;
-        for (; t + 2 <= NSc; t += 2)
-            bwd_small_kv_step<HD, 2>(Qs + 32 * t * C::RROW, dOs + 32 * t * C::RROW, lse_s + 32 * t, del_s + 32 * t, kf, vf, sl, dk, dv, lane);
-        if (t < NSc)
-            bwd_small_kv_step<HD, 1>(Qs + 32 * t * C::RROW, dOs + 32 * t * C::RROW, lse_s + 32 * t, del_s + 32 * t, kf, vf, sl, dk, dv, lane);
+        if (active) rows32_dkdv_walk<HD>(Qs, dOs, lse_s, del_s, NSc, kf, vf, sl, dk, dv, lane);
     }
     if (!active || !row_ok) return;
     bf16_t* dkrow = dqkv + ((int64_t)b * N + row) * lddq + Cdim + head * hd;
-    bf16_t* dvrow = dkrow + Cdim;
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d = 32 * db + 8 * g + 4 * h;
-            if (d < hd) {
-                store_quad<bf16_t>(dkrow + d, f32x4{dk[db][4 * g] * scale, dk[db][4 * g + 1] * scale, dk[db][4 * g + 2] * scale,
-                                                    dk[db][4 * g + 3] * scale});
-                store_quad<bf16_t>(dvrow + d, f32x4{dv[db][4 * g], dv[db][4 * g + 1], dv[db][4 * g + 2], dv[db][4 * g + 3]});
-            }
-        }
+    rows32_store_row_pair<HD>(dkrow, dk, scale, dkrow + Cdim, dv, 1.0f, hd, h);
 }
 
 constexpr size_t LDS_PER_CU = 160 * 1024;
@@ -2474,21 +2375,20 @@ template <typename F> int by_ns(const AttnRoute& r, F f) {
 template <int HD> int launch_fwd_small(const AttnCall& c) {
     typedef Cfg<bf16_t, HD> C;
     const auto p = c.as<bf16_t>();
-    const size_t smem = (size_t)(2 * ((c.N + 31) / 32 * 32) + SM_THREADS / 2) * C::RROW;      // {K, V} + per-wave [32][HD] scratch
+    auto lds = [](int n) { return (size_t)(2 * ((n + 31) / 32 * 32) + SM_THREADS / 2) * C::RROW; };      // {K, V} + per-wave [32][HD] scratch
+    const size_t smem = lds(c.N);
     const int64_t items = (int64_t)c.B * c.H;
     int per_cu = (int)(LDS_PER_CU / smem);
     per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    return attn_launch<attn_fwd_small_kernel<HD>>("me_attention_fwd(small)", dim3(persistent_grid(items, per_cu)), SM_THREADS, smem,
-                                                  (size_t)(2 * SM_MAXN + SM_THREADS / 2) * C::RROW, c.stream, p.qkv, c.ld, p.out, c.ldo, c.lse, c.N, c.H,
-                                                  c.hd, c.scale, (int)items);
+    return attn_launch<attn_fwd_small_kernel<HD>>("me_attention_fwd(small)", dim3(persistent_grid(items, per_cu)), SM_THREADS, smem, lds(SM_MAXN),
+                                                  c.stream, p.qkv, c.ld, p.out, c.ldo, c.lse, c.N, c.H, c.hd, c.scale, (int)items);
 }
 template <int HD> int launch_bwd_small(const AttnCall& c) {
     typedef Cfg<bf16_t, HD> C;
     const auto p = c.as<bf16_t>();
-    const size_t smem = (size_t)4 * ((c.N + 31) / 32 * 32) * C::RROW + 2 * SM_MAXN * sizeof(float);
-    return attn_launch<attn_bwd_small_kernel<HD>>("me_attention_bwd(small)", dim3(c.H, c.B), SM_THREADS, smem,
-                                                  (size_t)4 * SM_MAXN * C::RROW + 2 * SM_MAXN * sizeof(float), c.stream, p.qkv, c.ld, p.out, c.ldo, p.dout,
-                                                  c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
+    auto lds = [](int n) { return (size_t)4 * ((n + 31) / 32 * 32) * C::RROW + 2 * SM_MAXN * sizeof(float); };      // {Q, K, V, dO} + lse, delta
+    return attn_launch<attn_bwd_small_kernel<HD>>("me_attention_bwd(small)", dim3(c.H, c.B), SM_THREADS, lds(c.N), lds(SM_MAXN), c.stream, p.qkv, c.ld,
+                                                  p.out, c.ldo, p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
 }
 template <int HD, int NS> int launch_fwd_ring16(const AttnCall& c) {
     constexpr size_t smem = (size_t)4 * NS * 32 * RCfg<HD>::RB + (R16_THREADS / 64) * 16 * Cfg<bf16_t, HD>::RROW;
@@ -2535,16 +2435,16 @@ template <int HD> int launch_bwd_stream16(const AttnCall& c, const AttnRoute& r)
 template <int HD> int launch_fwd_mid(const AttnCall& c) {
     typedef Cfg<bf16_t, HD> C;
     const auto p = c.as<bf16_t>();
-    return attn_launch<attn_fwd_mid_kernel<HD, 512, MD_MAXN>>("me_attention_fwd(mid)", dim3(c.H, c.B), 512, (size_t)2 * ((c.N + 31) / 32 * 32) * C::RROW,
-                                                              (size_t)2 * MD_MAXN * C::RROW, c.stream, p.qkv, c.ld, p.out, c.ldo, c.lse, c.N, c.H, c.hd, c.scale);
+    auto lds = [](int n) { return (size_t)2 * ((n + 31) / 32 * 32) * C::RROW; };      // {K, V}
+    return attn_launch<attn_fwd_mid_kernel<HD, 512, MD_MAXN>>("me_attention_fwd(mid)", dim3(c.H, c.B), 512, lds(c.N), lds(MD_MAXN), c.stream, p.qkv, c.ld,
+                                                              p.out, c.ldo, c.lse, c.N, c.H, c.hd, c.scale);
 }
 template <int HD> int launch_bwd_mid(const AttnCall& c) {
     typedef Cfg<bf16_t, HD> C;
     const auto p = c.as<bf16_t>();
-    return attn_launch<attn_bwd_mid_kernel<HD, 512, MD_MAXN>>("me_attention_bwd(mid)", dim3(c.H, c.B), 512,
-                                                              (size_t)2 * ((c.N + 31) / 32 * 32) * C::RROW + 2 * MD_MAXN * sizeof(float),
-                                                              (size_t)2 * MD_MAXN * C::RROW + 2 * MD_MAXN * sizeof(float), c.stream, p.qkv, c.ld, p.out, c.ldo,
-                                                              p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
+    auto lds = [](int n) { return (size_t)2 * ((n + 31) / 32 * 32) * C::RROW + 2 * MD_MAXN * sizeof(float); };      // {K, V} then {Q, dO} + lse, delta
+    return attn_launch<attn_bwd_mid_kernel<HD, 512, MD_MAXN>>("me_attention_bwd(mid)", dim3(c.H, c.B), 512, lds(c.N), lds(MD_MAXN), c.stream, p.qkv, c.ld,
+                                                              p.out, c.ldo, p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
 }
 template <int HD> int launch_fwd_chunk(const AttnCall& c) {
     const size_t smem = (size_t)2 * CH_ROWS * Cfg<bf16_t, HD>::RROW;

@@ -204,6 +204,9 @@ def attn_ref(qkv, B, N, H, hd, scale):
 ATTN_SHAPES = [(2, 197, 12, 64), (1, 64, 2, 64), (3, 37, 2, 64), (2, 5, 2, 16), (2, 40, 32, 24), (1, 300, 4, 32),
                (1, 130, 2, 128), (1, 1, 1, 64), (1, 256, 2, 64), (2, 224, 3, 32), (2, 33, 1, 8),
                (1, 64, 2, 32), (2, 65, 2, 64), (1, 257, 2, 64), (1, 1568, 2, 64), (2, 512, 3, 64), (1, 400, 2, 64), (1, 513, 1, 64),
+               # the 32-row kernels: resident at HD = 32; a last chunk of 33 rows (masked two-sub-tile tail; 600 and 1568 take the
+               # one-sub-tile tail); three full chunks, no tail step
+               (2, 250, 2, 24), (1, 545, 2, 32), (1, 768, 1, 24),
                (2, 128, 32, 24), (1, 300, 32, 24), (1, 600, 4, 24),      # Graph: 32 heads x hd 24 on the resident / mid / chunked paths; both sides of the resident-sequence window
                # N <= 64: one wave per (batch, head) (attention_tiny.hip) -- Tabular (16 column tokens), Graph (~50 tokens, 32 x 24), every
                # (N class, head-dim class) pair with ragged N and head dims that are not tile multiples
@@ -450,21 +453,47 @@ def test_attention_generic_is_the_qkv_kernels(dev, N, hd, dt, p_drop):
         assert torch.equal(dqkv, res["dqkv"])
 
 
-def test_attention_route_padded_output_stride(dev):
-    """ld_out = C + 4 (the C entry; the Python wrapper passes dense strides): not a multiple of 8, so the forward at N = 300, head_dim 64
-    stays on the mid kernel where a dense output goes to the streaming one"""
-    B, N, H, hd = 2, 300, 2, 64
+@pytest.mark.parametrize("direction,N,form", [("fwd", 300, MID), ("fwd", 545, CHUNK), ("bwd", 545, CHUNK)])
+def test_attention_route_padded_output_stride(dev, direction, N, form):
+    """a row stride with 4 pad columns (the C entry; the Python wrappers pass dense strides): not a multiple of 8, which the streaming
+    kernels ask for.  Forward, ld_out = C + 4: at N = 300, head_dim 64 the call stays on the mid kernel, at N = 545 on the chunk kernel
+    (3 chunks, the last of 33 rows), where a dense output goes to the streaming one.  Backward, ld_dqkv = 3C + 4 with a dense out:
+    the two chunk kernels.  These are the only calls that launch the chunk kernels at head_dim 64."""
+    B, H, hd = 2, 2, 64
     C = H * hd
-    qkv = rnd(B * N, 3 * C, seed=300).bfloat16().to(dev)
-    out = torch.zeros(B * N, C + 4, dtype=torch.bfloat16, device=dev)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=dev)
+    scale = hd ** -0.5
+    lib = _capi.load()
+    qkv = rnd(B * N, 3 * C, seed=N).bfloat16()
+    if direction == "fwd":
+        out = torch.zeros(B * N, C + 4, dtype=torch.bfloat16, device=dev)
+        lse = torch.empty(B, H, N, dtype=torch.float32, device=dev)
+        qd = qkv.to(dev)
+
+        def body():
+            _capi.check(lib.me_attention_fwd(_capi.ptr(qd), 3 * C, _capi.ptr(out), C + 4, _capi.ptr(lse), B, N, H, hd, scale, _capi.ME_BF16,
+                                             0.0, 0, _capi.stream_ptr()), "me_attention_fwd")
+        assert _attention_plans(body) == [(_capi.ME_PROF_ATTN_FWD, form)]
+        ref, _ = attn_ref(qkv, B, N, H, hd, scale)
+        assert rel_err(out[:, :C].float(), ref) < 1.5e-2 and not bool(out[:, C:].any())
+        return
+    do = rnd(B * N, C, seed=77).bfloat16()
+    qr = qkv.double().requires_grad_(True)
+    ref, _ = attn_ref(qr, B, N, H, hd, scale)
+    ref.backward(do.double())
+    qd, dod = qkv.to(dev), do.to(dev)
+    out, lse = ops.attention_fwd(qd, B, N, H, hd, scale, True)
+    delta = torch.empty(B, H, N, dtype=torch.float32, device=dev)
+    dqkv = torch.zeros(B * N, 3 * C + 4, dtype=torch.bfloat16, device=dev)
 
     def body():
-        _capi.check(_capi.load().me_attention_fwd(_capi.ptr(qkv), 3 * C, _capi.ptr(out), C + 4, _capi.ptr(lse), B, N, H, hd, hd ** -0.5,
-                                                  _capi.ME_BF16, 0.0, 0, _capi.stream_ptr()), "me_attention_fwd")
-    assert _attention_plans(body) == [(_capi.ME_PROF_ATTN_FWD, MID)]
-    ref, _ = attn_ref(qkv.cpu(), B, N, H, hd, hd ** -0.5)
-    assert rel_err(out[:, :C].float(), ref) < 1.5e-2 and not bool(out[:, C:].any())
+        _capi.check(lib.me_attention_bwd(_capi.ptr(qd), 3 * C, _capi.ptr(out), C, _capi.ptr(dod), C, _capi.ptr(lse), _capi.ptr(delta),
+                                         _capi.ptr(dqkv), 3 * C + 4, B, N, H, hd, scale, _capi.ME_BF16, 0.0, 0, _capi.stream_ptr()),
+                    "me_attention_bwd")
+    assert _attention_plans(body) == [(_capi.ME_PROF_ATTN_BWD, form)]
+    assert not bool(dqkv[:, 3 * C:].any())
+    assert rel_err(dqkv[:, :3 * C].float(), qr.grad) < 3e-2
+    for j, nm in enumerate(("dQ", "dK", "dV")):      # each against its own scale, as in test_attention_bwd
+        check_close(dqkv[:, j * C:(j + 1) * C].float(), qr.grad[:, j * C:(j + 1) * C], 3e-2, f"attention backward {nm}, ld_dqkv = 3C + 4")
 
 
 @pytest.mark.parametrize("B,N,H,hd", [(32, 1568, 16, 64), (64, 592, 12, 64), (128, 512, 16, 64)])

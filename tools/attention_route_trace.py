@@ -4,8 +4,8 @@ two commits: run it at each, the two outputs must be byte-identical.
     python tools/attention_route_trace.py OUT                 # per case: sha256 of out, lse, dqkv
     python tools/attention_route_trace.py --host-time [CALLS]  # wall time of CALLS (2000) back-to-back forward + backward calls
 
-It uses only names that both sides of such a comparison have: ops.attention_fwd / ops.attention_bwd, and the ctypes entry for the
-case with a padded output stride.  Under `rocprofv3 --kernel-trace -- python tools/attention_route_trace.py OUT` the kernel
+It uses only names that both sides of such a comparison have: ops.attention_fwd / ops.attention_bwd, and the ctypes entries for the
+cases with a padded row stride.  Under `rocprofv3 --kernel-trace -- python tools/attention_route_trace.py OUT` the kernel
 sequence (name, grid, workgroup, LDS bytes) is the record of which kernel each case took.  The first cases are those of
 tests/test_gpu_ops.py::test_attention_route (profiles/attention_route_equivalence.txt holds the record made with them), the rest walk the
 generic route."""
@@ -32,7 +32,9 @@ CASES = [(64, 64, "bf16", 0.0, 2, 2), (64, 64, "fp32", 0.0, 2, 2), (65, 64, "bf1
          (1, 8, "fp32", 0.1, 2, 2), (65, 8, "fp32", 0.0, 2, 2), (129, 64, "fp32", 0.1, 2, 2), (130, 96, "fp32", 0.0, 2, 2),
          (130, 128, "fp32", 0.0, 2, 2), (257, 128, "fp32", 0.1, 2, 2), (37, 12, "fp32", 0.1, 2, 2),
          (65, 24, "bf16", 0.1, 2, 2), (129, 48, "bf16", 0.1, 2, 2), (130, 64, "bf16", 0.5, 2, 2), (257, 72, "bf16", 0.0, 2, 2),
-         (70, 96, "bf16", 0.0, 2, 2), (130, 128, "bf16", 0.1, 2, 2)]
+         (70, 96, "bf16", 0.0, 2, 2), (130, 128, "bf16", 0.1, 2, 2),
+         # the 32-row kernels: resident at HD = 32, a last chunk of 33 rows (masked two-sub-tile tail), three full chunks (no tail step)
+         (250, 24, "bf16", 0.0, 2, 2), (545, 32, "bf16", 0.0, 1, 2), (768, 24, "bf16", 0.0, 1, 1)]
 DT = {"bf16": torch.bfloat16, "fp32": torch.float32}
 
 
@@ -57,16 +59,27 @@ def trace(path):
         dqkv = ops.attention_bwd(qkv, out, dout, lse, B, N, H, hd, scale, p_drop=p, seed=7)
         torch.cuda.synchronize()
         out_f.write(f"== N={N} hd={hd} {dt} p_drop={p} B={B} H={H}\n  out: {sha(out)}\n  lse: {sha(lse)}\n  dqkv: {sha(dqkv)}\n")
-    # forward with ld_out = C + 4 (the Python wrappers always pass dense strides): the ctypes entry
-    B, N, H, hd = 2, 300, 2, 64
-    C = H * hd
-    qkv, _ = inputs(B, N, H, hd, "bf16", 200)
-    out = torch.zeros(B * N, C + 4, dtype=torch.bfloat16, device=dev)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=dev)
-    check(_capi.load().me_attention_fwd(ptr(qkv), 3 * C, ptr(out), C + 4, ptr(lse), B, N, H, hd, hd ** -0.5, dtype_code(torch.bfloat16), 0.0, 0,
-                                        stream_ptr()), "me_attention_fwd")
+    # padded row strides (the Python wrappers always pass dense ones): the ctypes entries
+    lib = _capi.load()
+    bf = dtype_code(torch.bfloat16)
+    # forward with ld_out = C + 4: the mid kernel at N = 300, the chunk kernel at N = 545 (the only forward that takes it at head_dim 64)
+    for N, seed in ((300, 200), (545, 201)):
+        B, H, hd = 2, 2, 64
+        C = H * hd
+        qkv, dout = inputs(B, N, H, hd, "bf16", seed)
+        out = torch.zeros(B * N, C + 4, dtype=torch.bfloat16, device=dev)
+        lse = torch.empty(B, H, N, dtype=torch.float32, device=dev)
+        check(lib.me_attention_fwd(ptr(qkv), 3 * C, ptr(out), C + 4, ptr(lse), B, N, H, hd, hd ** -0.5, bf, 0.0, 0, stream_ptr()), "me_attention_fwd")
+        torch.cuda.synchronize()
+        out_f.write(f"== N={N} hd={hd} bf16 ld_out=C+4 B={B} H={H} (forward only)\n  out: {sha(out)}\n  lse: {sha(lse)}\n")
+    # backward at N = 545 with a dense out and ld_dqkv = 3C + 4: the two chunk kernels at head_dim 64
+    out, lse = ops.attention_fwd(qkv, B, N, H, hd, hd ** -0.5, True)
+    delta = torch.empty(B, H, N, dtype=torch.float32, device=dev)
+    dqkv = torch.zeros(B * N, 3 * C + 4, dtype=torch.bfloat16, device=dev)
+    check(lib.me_attention_bwd(ptr(qkv), 3 * C, ptr(out), C, ptr(dout), C, ptr(lse), ptr(delta), ptr(dqkv), 3 * C + 4, B, N, H, hd, hd ** -0.5, bf,
+                               0.0, 0, stream_ptr()), "me_attention_bwd")
     torch.cuda.synchronize()
-    out_f.write(f"== N={N} hd={hd} bf16 ld_out=C+4 B={B} H={H} (forward only)\n  out: {sha(out)}\n  lse: {sha(lse)}\n")
+    out_f.write(f"== N={N} hd={hd} bf16 ld_dqkv=3C+4 B={B} H={H} (backward only)\n  delta: {sha(delta)}\n  dqkv: {sha(dqkv)}\n")
     out_f.close()
 
 
