@@ -28,6 +28,7 @@ namespace {
 // The per-wave pieces below (rows32_* and Rows32Stage: a wave owns 32 rows, 8 waves to a workgroup) are shared by seven
 // kernels: attn_fwd_small / attn_bwd_small here, attn_fwd_mid / attn_bwd_mid (N <= 512) and attn_fwd_chunk /
 // attn_bwd_dq_chunk / attn_bwd_dkdv_chunk (N > 512) further down.  Those differ only in what is resident in LDS and when.
+// acc_zero, row_frags_load and acc_store_row / acc_store_row_pair, which they share with the tiled kernels, are in attention_tile.h.
 // =====================================================================================================
 // developer instrumentation (tools/attn_trace.hip defines ME_ATTN_TRACE and includes this file): per-workgroup
 // s_memtime stamps at the phase boundaries; compiled out of libmetaenc.so
@@ -84,13 +85,6 @@ template <int HD, int NARR, int MAXN = SM_MAXN, int NTHR = SM_THREADS> struct Ro
     }
 };
 
-template <int NDB> __device__ __forceinline__ void rows32_zero(f32x16 (&acc)[NDB]) {
-#pragma unroll
-    for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[db][r] = 0.f;
-}
-
 // acc + a . b over the 8 bf16 of two 16-byte fragments, in element order (per dword: low half, high half).  The 16-row ring and
 // stream backward keep the same sum written out: through this function hipcc swaps the operands of their multiplies and adds (same
 // values, another instruction sequence), and those kernels are not to change
@@ -100,19 +94,6 @@ __device__ __forceinline__ float bf16x8_dot_acc(float acc, u32x4 a, u32x4 b) {
         acc += __uint_as_float(a[e] << 16) * __uint_as_float(b[e] << 16) +
                __uint_as_float(a[e] & 0xffff0000u) * __uint_as_float(b[e] & 0xffff0000u);
     return acc;
-}
-
-// Q fragments of one row straight from HBM (qrow: that row's head slice); chunks past hd are zeros
-template <int HD>
-__device__ __forceinline__ void rows32_load_q(const bf16_t* qrow, int hd, int h, bf16x8 (&qf)[Cfg<bf16_t, HD>::NKK]) {
-#pragma unroll
-    for (int kk = 0; kk < Cfg<bf16_t, HD>::NKK; ++kk) {
-        const int d = (2 * kk + h) * 8;
-        const bool ok = d < hd;
-        u32x4 raw = *reinterpret_cast<const u32x4*>(qrow + (ok ? d : 0));
-        raw = ok ? raw : zero4();
-        qf[kk] = *reinterpret_cast<bf16x8*>(&raw);
-    }
 }
 
 // {Q, dO} fragments of one row straight from HBM and delta = dO . O of that row (returned, summed over the two half-waves).
@@ -136,38 +117,6 @@ __device__ __forceinline__ float rows32_load_q_do_delta(const bf16_t* qrow, cons
         del = bf16x8_dot_acc(del, ro, rd);
     }
     return del + __shfl_xor(del, 32, 64);
-}
-
-// A lane's row of accumulators (transposed layout: lane = row l31, registers = d) times mul as bf16, 8 bytes per store.  grow: that
-// row's head slice; the caller has checked that the row exists.  The pair form stores dK and dV under one d < hd test per quad: as
-// two single calls it measured +33 / +64 instructions in attn_bwd_dkdv_chunk_kernel<32 / 64> and +77 / +145 in attn_bwd_mid_kernel
-// (pair: 0 / 0 and +15 / +25), all outside the loops (profiles/attention_rows32_refactor.txt)
-__device__ __forceinline__ void rows32_store_quad(bf16_t* p, const f32x16& acc, int g, float mul) {
-    store_quad<bf16_t>(p, f32x4{acc[4 * g] * mul, acc[4 * g + 1] * mul, acc[4 * g + 2] * mul, acc[4 * g + 3] * mul});
-}
-template <int HD>
-__device__ __forceinline__ void rows32_store_row(bf16_t* grow, const f32x16 (&acc)[Cfg<bf16_t, HD>::NDB], float mul, int hd, int h) {
-#pragma unroll
-    for (int db = 0; db < Cfg<bf16_t, HD>::NDB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d = 32 * db + 8 * g + 4 * h;
-            if (d < hd) rows32_store_quad(grow + d, acc[db], g, mul);
-        }
-}
-template <int HD>
-__device__ __forceinline__ void rows32_store_row_pair(bf16_t* grow0, const f32x16 (&acc0)[Cfg<bf16_t, HD>::NDB], float mul0, bf16_t* grow1,
-                                                      const f32x16 (&acc1)[Cfg<bf16_t, HD>::NDB], float mul1, int hd, int h) {
-#pragma unroll
-    for (int db = 0; db < Cfg<bf16_t, HD>::NDB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d = 32 * db + 8 * g + 4 * h;
-            if (d < hd) {
-                rows32_store_quad(grow0 + d, acc0[db], g, mul0);
-                rows32_store_quad(grow1 + d, acc1[db], g, mul1);
-            }
-        }
 }
 
 // End of a forward row: l summed over the two half-waves, lse (natural log) written where `write` holds; returns 1 / l
@@ -441,7 +390,7 @@ __global__ __launch_bounds__(SM_THREADS) void attn_fwd_small_kernel(const bf16_t
         issue(nxt, qn);
         if (active) {
             f32x16 o[C::NDB];
-            rows32_zero(o);
+            acc_zero(o);
             float m_run = -INFINITY, l_run = 0.f;
             rows32_fwd_walk<HD>(Ks, Vs, 0, N, N, qf, sl, m_run, l_run, o, lane);
             TRACE_STAMP(it, 1);
@@ -824,7 +773,7 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_small_kernel(const bf16_t
             if (row_ok && delta) delta[bh + row] = del;
         }
         const float lse2 = lse_s[row];      // +inf on padded queries -> P = 0
-        rows32_zero(dq);
+        acc_zero(dq);
         rows32_dq_walk<HD>(Ks, Vs, 0, N, N, qf, dof, sl, lse2, del, dq, lane);
     }
     TRACE_STAMP(trace_slot, 2);
@@ -849,8 +798,8 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_small_kernel(const bf16_t
     TRACE_STAMP(trace_slot, 4);
     // ---- phase B: dK and dV for the 32 keys of this wave
     f32x16 dk[C::NDB], dv[C::NDB];
-    rows32_zero(dk);
-    rows32_zero(dv);
+    acc_zero(dk);
+    acc_zero(dv);
     rows32_dkdv_walk<HD>(Qs, dOs, lse_s, del_s, NS, kf, vf, sl, dk, dv, lane);
     TRACE_STAMP(trace_slot, 5);
     store_rows_via_lds<HD>(scr0, dk, scale, grow0 + Cdim, lddq, N - 32 * wave, hd, lane);
@@ -2060,13 +2009,13 @@ __global__ __launch_bounds__(NTHR) void attn_fwd_mid_kernel(const bf16_t* __rest
         const int q = 32 * sub + l31;
         const int qrow = (q < N) ? q : N - 1;
         bf16x8 qf[C::NKK];
-        rows32_load_q<HD>(qptr + (int64_t)qrow * ld, hd, h, qf);
+        row_frags_load<HD>(qptr + (int64_t)qrow * ld, hd, h, qf);
         f32x16 o[C::NDB];
-        rows32_zero(o);
+        acc_zero(o);
         float m_run = -INFINITY, l_run = 0.f;
         rows32_fwd_walk<HD>(Ks, Vs, 0, N, N, qf, sl, m_run, l_run, o, lane);
         const float inv = rows32_softmax_finish(m_run, l_run, lse, ((int64_t)b * H + head) * N + q, h == 0 && q < N);
-        if (q < N) rows32_store_row<HD>(out + ((int64_t)b * N + q) * ldo + head * hd, o, inv, hd, h);
+        if (q < N) acc_store_row(out + ((int64_t)b * N + q) * ldo + head * hd, o, inv, hd, h);
     }
 }
 
@@ -2112,9 +2061,9 @@ __global__ __launch_bounds__(NTHR) void attn_bwd_mid_kernel(const bf16_t* __rest
         }
         const float lse2 = lse_s[row];
         f32x16 dq[C::NDB];
-        rows32_zero(dq);
+        acc_zero(dq);
         rows32_dq_walk<HD>(T0, T1, 0, N, N, qf, dof, sl, lse2, del, dq, lane);
-        if (row_ok) rows32_store_row<HD>(dqkv + ((int64_t)b * N + row) * lddq + head * hd, dq, scale, hd, h);
+        if (row_ok) acc_store_row(dqkv + ((int64_t)b * N + row) * lddq + head * hd, dq, scale, hd, h);
     }
     // ---- hand-over: lift the K / V row fragments of my key groups, then refill the two tiles with Q / dO
     constexpr int MAXG = MAXN / 32 / NWAVE;      // 2
@@ -2139,12 +2088,12 @@ __global__ __launch_bounds__(NTHR) void attn_bwd_mid_kernel(const bf16_t* __rest
         if (sub >= NS) break;      // wave-uniform
         const int row = 32 * sub + l31;
         f32x16 dk[C::NDB], dv[C::NDB];
-        rows32_zero(dk);
-        rows32_zero(dv);
+        acc_zero(dk);
+        acc_zero(dv);
         rows32_dkdv_walk<HD>(T0, T1, lse_s, del_s, NS, kf[g], vf[g], sl, dk, dv, lane);
         if (row < N) {
             bf16_t* dkrow = dqkv + ((int64_t)b * N + row) * lddq + Cdim + head * hd;
-            rows32_store_row_pair<HD>(dkrow, dk, scale, dkrow + Cdim, dv, 1.0f, hd, h);
+            acc_store_row_pair(dkrow, dk, scale, dkrow + Cdim, dv, 1.0f, hd, h);
         }
     }
 }
@@ -2177,9 +2126,9 @@ __global__ __launch_bounds__(SM_THREADS) void attn_fwd_chunk_kernel(const bf16_t
     const bool active = blockIdx.x * CH_ROWS + 32 * wave < N;      // wave-uniform
     const int qrow = (q < N) ? q : N - 1;
     bf16x8 qf[C::NKK];
-    rows32_load_q<HD>(qptr + (int64_t)qrow * ld, hd, h, qf);
+    row_frags_load<HD>(qptr + (int64_t)qrow * ld, hd, h, qf);
     f32x16 o[C::NDB];
-    rows32_zero(o);
+    acc_zero(o);
     float m_run = -INFINITY, l_run = 0.f;
     const float sl = scale * LOG2E;
     for (int kv0 = 0; kv0 < N; kv0 += CH_ROWS) {
@@ -2192,7 +2141,7 @@ __global__ __launch_bounds__(SM_THREADS) void attn_fwd_chunk_kernel(const bf16_t
     }
     if (!active) return;
     const float inv = rows32_softmax_finish(m_run, l_run, lse, ((int64_t)b * H + head) * N + q, h == 0 && q < N);
-    if (q < N) rows32_store_row<HD>(out + ((int64_t)b * N + q) * ldo + head * hd, o, inv, hd, h);
+    if (q < N) acc_store_row(out + ((int64_t)b * N + q) * ldo + head * hd, o, inv, hd, h);
 }
 
 // backward pass 1: delta and dQ for 256 queries; K/V stream in chunks
@@ -2226,7 +2175,7 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_dq_chunk_kernel(const bf1
     const float lse2 = row_ok ? lse[bh + row] * LOG2E : INFINITY;      // padded queries: P = 0
     const float sl = scale * LOG2E;
     f32x16 dq[C::NDB];
-    rows32_zero(dq);
+    acc_zero(dq);
     for (int kv0 = 0; kv0 < N; kv0 += CH_ROWS) {
         const int rows = N - kv0 < CH_ROWS ? N - kv0 : CH_ROWS;
         __syncthreads();
@@ -2235,7 +2184,7 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_dq_chunk_kernel(const bf1
         __syncthreads();
         if (active) rows32_dq_walk<HD>(Ks, Vs, kv0, rows, N, qf, dof, sl, lse2, del, dq, lane);
     }
-    if (active && row_ok) rows32_store_row<HD>(dqkv + ((int64_t)b * N + row) * lddq + head * hd, dq, scale, hd, h);
+    if (active && row_ok) acc_store_row(dqkv + ((int64_t)b * N + row) * lddq + head * hd, dq, scale, hd, h);
 }
 
 // backward pass 2: dK and dV for 256 keys; Q / dO (and their lse / delta) stream in chunks
@@ -2277,8 +2226,8 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_dkdv_chunk_kernel(const b
     }
     const float sl = scale * LOG2E;
     f32x16 dk[C::NDB], dv[C::NDB];
-    rows32_zero(dk);
-    rows32_zero(dv);
+    acc_zero(dk);
+    acc_zero(dv);
     for (int q0 = 0; q0 < N; q0 += CH_ROWS) {
         const int rows = N - q0 < CH_ROWS ? N - q0 : CH_ROWS;
         const int NSc = (rows + 31) >> 5;
@@ -2294,7 +2243,7 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_dkdv_chunk_kernel(const b
     }
     if (!active || !row_ok) return;
     bf16_t* dkrow = dqkv + ((int64_t)b * N + row) * lddq + Cdim + head * hd;
-    rows32_store_row_pair<HD>(dkrow, dk, scale, dkrow + Cdim, dv, 1.0f, hd, h);
+    acc_store_row_pair(dkrow, dk, scale, dkrow + Cdim, dv, 1.0f, hd, h);
 }
 
 constexpr size_t LDS_PER_CU = 160 * 1024;

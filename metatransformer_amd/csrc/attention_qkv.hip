@@ -24,7 +24,7 @@
 //   * causal: tiles entirely on the masked side of the diagonal are skipped (the loop bounds are block-uniform, a wave skips the
 //     compute of a tile none of its rows sees), the tiles the diagonal crosses are masked element-wise,
 //   * the dropout stream is indexed ((b*H + h)*Nq + q)*Nk + k.
-// Backward: a delta pass chosen by the entry point (dO . O, or from the tiles: attn_qkv_delta_kernel says when), dK / dV (a wave owns
+// Backward: a delta pass chosen by the entry point (dO . O, or from the tiles: qrows_bwd says when), dK / dV (a wave owns
 // 32 keys, walks query tiles), dQ (a wave owns 32 queries, walks key tiles).  No atomics, every output element is written exactly
 // once, two runs are bit-identical.
 #include "attention_host.h"
@@ -33,12 +33,9 @@
 
 namespace {
 
-// key kv is visible to query q
-__device__ __forceinline__ bool qkv_visible(int kv, int q, int Nk, int causal) { return kv < Nk && (!causal || kv <= q); }
-
-// fp32: the transposed [HD][64] copy of a tile written from the registers of its row-major stage.  RowStage<float> and TransStage<float> fetch
-// the same 16 bytes per item, so the backward kernels stage Q / dO / K once and store them twice instead of loading them twice
-// (a second register set for the transposed copy is what no longer fits beside the accumulators at HD 128).
+// fp32: the transposed [HD][64] copy of a tile written from the registers of its row-major stage (TRead<float> reads its operand from
+// it; bf16 reads the row tile with tr).  So a tile that is needed both ways is staged once and stored twice instead of loaded twice (a
+// second register set for the transposed copy is what no longer fits beside the accumulators at HD 128).
 template <int HD> __device__ __forceinline__ void store_transposed(const RowStage<float, HD>& st, char* lds, int tid) {
     typedef Cfg<float, HD> C;
 #pragma unroll
@@ -51,16 +48,93 @@ template <int HD> __device__ __forceinline__ void store_transposed(const RowStag
         }
     }
 }
-template <int HD> __device__ __forceinline__ void store_transposed(const RowStage<bf16_t, HD>&, char*, int) {}      // bf16 reads row tiles with tr
+
+// =====================================================================================================
+// The per-wave pieces of the four kernels.  A block is (128-row block x, head y, batch z), wave w owns rows [128 x + 32 w, + 32) of one
+// side (queries: forward, delta, dQ; keys: dK / dV), lane l31 one of them, and the other side walks by in 64-row LDS tiles.  With
+// acc_zero, row_frags_load and acc_store_row(_pair) of attention_tile.h each of these is written once.
+// =====================================================================================================
+
+// row `row` of batch item b, head `head` in a [B*N, ld] operand
+template <typename P> __device__ __forceinline__ P head_rows(P p, int64_t ld, int b, int N, int head, int hd, int row = 0) {
+    return p + ((int64_t)b * N + row) * ld + head * hd;
+}
+
+// The score matrix of one (batch, head): which entries exist, what the backward recomputes of them, and their dropout stream
+struct Scores {
+    int Nq, Nk, causal;
+    float scale, p_drop, keep;      // keep = 1 / (1 - p_drop)
+    uint64_t seed, bh;              // bh = b * H + head
+    // key kv is visible to query q
+    __device__ __forceinline__ bool visible(int kv, int q) const { return kv < Nk && (!causal || kv <= q); }
+    // P[q][kv] from the raw score and the row's lse; 0 where the key is masked
+    __device__ __forceinline__ float prob(float s, float lse, int kv, int q) const { return visible(kv, q) ? __expf(s * scale - lse) : 0.f; }
+    // x at probability (q, kv) after dropout: the stream is indexed ((b*H + h)*Nq + q)*Nk + kv = drop_row(q) + kv, what is kept is
+    // scaled by `keep`
+    __device__ __forceinline__ uint64_t drop_row(int q) const { return (bh * (uint64_t)Nq + (uint64_t)q) * (uint64_t)Nk; }
+    __device__ __forceinline__ float dropped(float x, uint64_t row, int kv) const {
+        return u01_hash(seed, row + (uint64_t)kv) >= p_drop ? x * keep : 0.f;
+    }
+    // P and dS of register r of a sub-tile from lse / delta under the mask and the dropout stream: s[r] (raw score) becomes the dropped
+    // P, which dV consumes, and dp[r] (dP) becomes dS = P (dropped dP - delta) scale -- the forward's mask on both
+    __device__ __forceinline__ void p_ds(f32x16& s, f32x16& dp, int r, float lse, float delta, int kv, int q) const {
+        const float p = prob(s[r], lse, kv, q);
+        float pm = p, dpm = dp[r];
+        if (p_drop > 0.f) { pm = dropped(p, drop_row(q), kv); dpm = dropped(dpm, drop_row(q), kv); }
+        s[r] = pm;
+        dp[r] = p * (dpm - delta) * scale;
+    }
+};
+__device__ __forceinline__ Scores scores_of(const me_attn_qkv_desc& d, int b, int head) {
+    return Scores{d.Nq, d.Nk, d.causal, d.scale, d.p_drop, 1.0f / (1.0f - d.p_drop), d.seed, (uint64_t)b * d.H + head};
+}
+
+// 64-key tiles a block of queries walks.  causal: tiles that start beyond the block's last query are all masked (block-uniform)
+__device__ __forceinline__ int key_tiles(int Nq, int Nk, int causal) {
+    int ntiles = (Nk + KVT - 1) / KVT;
+    if (causal) {
+        const int qlast = min(blockIdx.x * QPB + QPB - 1, Nq - 1);
+        ntiles = min(ntiles, qlast / KVT + 1);
+    }
+    return ntiles;
+}
+
+// The walk over tiles j0 .. ntiles - 1 of the other side.  load(r0) fetches the tile that starts at row r0 into registers, park() writes
+// the fetched tile to LDS, use(j) is the wave's work on tile j; it returns at once where no row of the wave sees the tile (a
+// wave-uniform test, after the barriers and the prefetch).  The next tile's global loads fly during this tile's MFMAs.
+// The three are lambdas of the kernel marked INLINED: they become part of the kernel before anything is optimised, as if written in
+// the loop (left to the inliner they are optimised on their own first, with every captured value unknown).
+#define INLINED __attribute__((always_inline))
+template <typename Load, typename Park, typename Use>
+__device__ __forceinline__ void walk_tiles(int j0, int ntiles, Load load, Park park, Use use) {
+    load(j0 * KVT);
+    for (int j = j0; j < ntiles; ++j) {
+        __syncthreads();
+        park();
+        __syncthreads();
+        if (j + 1 < ntiles) load((j + 1) * KVT);
+        use(j);
+    }
+}
+
+// Rows [32 u, 32 u + 32) of a row-major LDS tile times the lane's row fragments.  For a wave that owns queries that is S^T = K Q^T or
+// dP^T = V dO^T of the sub-tile, for one that owns keys S = Q K^T or dP = dO V^T.  -> lane: the wave's row, register r: tile row
+// 32 u + acc_row(r, h)
+template <typename T, int HD>
+__device__ __forceinline__ f32x16 subtile_product(const char* tile, int u, int lane, const typename Chunk<T>::type (&f)[Cfg<T, HD>::NKK]) {
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < Cfg<T, HD>::NKK; ++kk)
+        acc = mma_chunk(rtile_chunk<T, HD>(tile, 32 * u + (lane & 31), 2 * kk + (lane >> 5)), f[kk], acc);
+    return acc;
+}
 
 // =====================================================================================================
 // forward
 // =====================================================================================================
-template <typename T, int HD>
-__global__ __launch_bounds__(AT_THREADS) void attn_qkv_fwd_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ k, int64_t ldk,
-                                                                  const T* __restrict__ v, int64_t ldv, T* __restrict__ out, int64_t ldo,
-                                                                  float* __restrict__ lse, int Nq, int Nk, int H, int hd, float scale,
-                                                                  int causal, float p_drop, uint64_t seed) {
+template <typename T, int HD> __global__ __launch_bounds__(AT_THREADS) void attn_qkv_fwd_kernel(const me_attn_qkv_desc d) {
     typedef Cfg<T, HD> C;
     typedef typename Chunk<T>::type chunk_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -70,122 +144,86 @@ __global__ __launch_bounds__(AT_THREADS) void attn_qkv_fwd_kernel(const T* __res
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
     const int b = blockIdx.z, head = blockIdx.y;
+    const int Nq = d.Nq, Nk = d.Nk, hd = d.head_dim;
     const int qbase = blockIdx.x * QPB + wave * 32;
-    const T* qptr = q + (int64_t)b * Nq * ldq + head * hd;
-    const T* kptr = k + (int64_t)b * Nk * ldk + head * hd;
-    const T* vptr = v + (int64_t)b * Nk * ldv + head * hd;
+    const Scores sc = scores_of(d, b, head);
+    const T* kptr = head_rows((const T*)d.k, d.ld_k, b, Nk, head, hd);
+    const T* vptr = head_rows((const T*)d.v, d.ld_v, b, Nk, head, hd);
 
-    chunk_t qf[C::NKK];
-    {
-        const int qrow = (qbase + l31 < Nq) ? qbase + l31 : Nq - 1;      // out-of-range rows read the last row and are never stored
-#pragma unroll
-        for (int kk = 0; kk < C::NKK; ++kk) {
-            const int d = (2 * kk + h) * C::E;
-            u32x4 raw = (d < hd) ? *reinterpret_cast<const u32x4*>(qptr + (int64_t)qrow * ldq + d) : zero4();
-            qf[kk] = *reinterpret_cast<chunk_t*>(&raw);
-        }
-    }
+    chunk_t qf[C::NKK];      // out-of-range rows read the last row and are never stored
+    row_frags_load<HD>(head_rows((const T*)d.q, d.ld_q, b, Nq, head, hd) + (int64_t)min(qbase + l31, Nq - 1) * d.ld_q, hd, h, qf);
     f32x16 o[C::NDB];
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+    acc_zero(o);
     float m_run = -INFINITY, l_run = 0.f;
     const bool active = qbase < Nq;      // wave-uniform
     const int qi = qbase + l31;          // this lane's query (unclamped: a row past Nq only sees more keys)
-    int ntiles = (Nk + KVT - 1) / KVT;
-    if (causal) {                        // block-uniform: key tiles that start beyond the block's last query are all masked
-        const int qlast = min(blockIdx.x * QPB + QPB - 1, Nq - 1);
-        ntiles = min(ntiles, qlast / KVT + 1);
-    }
 
-    RowStage<T, HD> ks, vrs;
-    TransStage<T, HD> vts;
-    ks.load(kptr, ldk, 0, Nk, hd, tid);
-    if (TT) vts.load(vptr, ldv, 0, Nk, hd, tid); else vrs.load(vptr, ldv, 0, Nk, hd, tid);
-    for (int j = 0; j < ntiles; ++j) {
-        __syncthreads();
-        ks.store(Ks, tid);
-        if (TT) vts.store(Vs, tid); else vrs.store(Vs, tid);
-        __syncthreads();
-        if (j + 1 < ntiles) {
-            ks.load(kptr, ldk, (j + 1) * KVT, Nk, hd, tid);
-            if (TT) vts.load(vptr, ldv, (j + 1) * KVT, Nk, hd, tid); else vrs.load(vptr, ldv, (j + 1) * KVT, Nk, hd, tid);
-        }
-        const int kv0 = j * KVT;
-        if (!active || (causal && kv0 > qbase + 31)) continue;      // wave-uniform: no row of this wave sees the tile
-        f32x16 s[2];
+    RowStage<T, HD> ks, vs;
+    walk_tiles(
+        0, key_tiles(Nq, Nk, d.causal),
+        [&](int kv0) INLINED {
+            ks.load(kptr, d.ld_k, kv0, Nk, hd, tid);
+            vs.load(vptr, d.ld_v, kv0, Nk, hd, tid);
+        },
+        [&]() INLINED {
+            ks.store(Ks, tid);
+            if constexpr (TT) store_transposed<HD>(vs, Vs, tid); else vs.store(Vs, tid);
+        },
+        [&](int j) INLINED {
+            const int kv0 = j * KVT;
+            if (!active || (d.causal && kv0 > qbase + 31)) return;      // wave-uniform: no row of this wave sees the tile
+            f32x16 s[2];
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[u][r] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < C::NKK; ++kk)
-                s[u] = mma_chunk(rtile_chunk<T, HD>(Ks, 32 * u + l31, 2 * kk + h), qf[kk], s[u]);
-        }
-        float mt = -INFINITY;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int kv = kv0 + 32 * u + acc_row(r, h);
-                const float sv = qkv_visible(kv, qi, Nk, causal) ? s[u][r] * scale : -INFINITY;
-                s[u][r] = sv;
-                mt = fmaxf(mt, sv);
-            }
-        // One lane holds half of the tile's keys, and on a tile the diagonal crosses all of them may be masked: mt = -inf here.  After
-        // the fold with the partner lane it is finite on EVERY tile that gets this far: kv0 < Nk always, and under `causal` kv0 and qbase
-        // are multiples of 32 with kv0 <= qbase + 31, hence kv0 <= qbase <= qi -- key kv0 is visible to every row of the wave.  So m_new is
-        // finite, exp(-inf - m_new) = 0 for the masked entries, and m_run - m_new is -inf - finite (alpha = 0) on the first processed tile
-        // (tile 0: it is never skipped) and finite - finite afterwards: -inf - (-inf) cannot occur.
-        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-        const float m_new = fmaxf(m_run, mt);
-        const float alpha = __expf(m_run - m_new);
-        float ps = 0.f;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = __expf(s[u][r] - m_new);
-                s[u][r] = p;
-                ps += p;
-            }
-        l_run = l_run * alpha + ps;
-        m_run = m_new;
-        if (p_drop > 0.f) {      // FullAttention's dropout acts on the NORMALISED probabilities -- the row sum stays unmasked
-            const float keep = 1.0f / (1.0f - p_drop);
-            const uint64_t rowbase = (((uint64_t)b * H + head) * Nq + (uint64_t)qi) * (uint64_t)Nk;
+            for (int u = 0; u < 2; ++u) s[u] = subtile_product<T, HD>(Ks, u, lane, qf);
+            float mt = -INFINITY;
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    s[u][r] = u01_hash(seed, rowbase + (uint64_t)(kv0 + 32 * u + acc_row(r, h))) >= p_drop ? s[u][r] * keep : 0.f;
-        }
+                for (int r = 0; r < 16; ++r) {
+                    const float sv = sc.visible(kv0 + 32 * u + acc_row(r, h), qi) ? s[u][r] * sc.scale : -INFINITY;
+                    s[u][r] = sv;
+                    mt = fmaxf(mt, sv);
+                }
+            // One lane holds half of the tile's keys, and on a tile the diagonal crosses all of them may be masked: mt = -inf here.  After
+            // the fold with the partner lane it is finite on EVERY tile that gets this far: kv0 < Nk always, and under `causal` kv0 and
+            // qbase are multiples of 32 with kv0 <= qbase + 31, hence kv0 <= qbase <= qi -- key kv0 is visible to every row of the wave.
+            // So m_new is finite, exp(-inf - m_new) = 0 for the masked entries, and m_run - m_new is -inf - finite (alpha = 0) on the first
+            // processed tile (tile 0: it is never skipped) and finite - finite afterwards: -inf - (-inf) cannot occur.
+            mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+            const float m_new = fmaxf(m_run, mt);
+            const float alpha = __expf(m_run - m_new);
+            float ps = 0.f;
 #pragma unroll
-        for (int db = 0; db < C::NDB; ++db) o[db] *= alpha;
+            for (int u = 0; u < 2; ++u)
 #pragma unroll
-        for (int c = 0; c < C::NPC; ++c) {
-            const chunk_t pb = pack_chunk((const T*)nullptr, s, c);
+                for (int r = 0; r < 16; ++r) {
+                    const float p = __expf(s[u][r] - m_new);
+                    s[u][r] = p;
+                    ps += p;
+                }
+            l_run = l_run * alpha + ps;
+            m_run = m_new;
+            if (sc.p_drop > 0.f) {      // FullAttention's dropout acts on the NORMALISED probabilities -- the row sum stays unmasked
+                const uint64_t row = sc.drop_row(qi);
 #pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-                o[db] = mma_chunk(TRead<T, HD>::chunk(Vs, Vs, db, c, lane), pb, o[db]);
-        }
-    }
+                for (int u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) s[u][r] = sc.dropped(s[u][r], row, kv0 + 32 * u + acc_row(r, h));
+            }
+#pragma unroll
+            for (int db = 0; db < C::NDB; ++db) o[db] *= alpha;
+#pragma unroll
+            for (int c = 0; c < C::NPC; ++c) {
+                const chunk_t pb = pack_chunk((const T*)nullptr, s, c);
+#pragma unroll
+                for (int db = 0; db < C::NDB; ++db) o[db] = mma_chunk(TRead<T, HD>::chunk(Vs, Vs, db, c, lane), pb, o[db]);
+            }
+        });
     if (!active) return;
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
     if (qi < Nq) {
-        T* orow = out + ((int64_t)b * Nq + qi) * ldo + head * hd;
-#pragma unroll
-        for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = 32 * db + 8 * g + 4 * h;
-                if (d < hd)
-                    store_quad<T>(orow + d, f32x4{o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv,
-                                                  o[db][4 * g + 3] * inv});
-            }
-        if (lse && h == 0) lse[((int64_t)b * H + head) * Nq + qi] = m_run + __logf(l_tot);
+        acc_store_row(head_rows((T*)d.out, d.ld_out, b, Nq, head, hd, qi), o, 1.0f / l_tot, hd, h);
+        if (d.lse && h == 0) d.lse[(int64_t)sc.bh * Nq + qi] = m_run + __logf(l_tot);
     }
 }
 
@@ -202,16 +240,12 @@ __global__ __launch_bounds__(AT_THREADS) void attn_qkv_fwd_kernel(const T* __res
 // DB0 on: all of them in one launch, except fp32 at HD 128 -- there the K and V rows (128 registers) and a full dK / dV accumulator pair (128)
 // leave no room for S, dP and the staged tile without spilling, so two launches take two d blocks each (S and dP are formed in both).
 template <typename T, int HD, int DB0, int NDBO>
-__global__ __launch_bounds__(AT_THREADS) void attn_qkv_bwd_dkdv_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ k, int64_t ldk,
-                                                                       const T* __restrict__ v, int64_t ldv, const T* __restrict__ dout,
-                                                                       int64_t lddo, const float* __restrict__ lse,
-                                                                       const float* __restrict__ delta, T* __restrict__ dk_out, int64_t lddk,
-                                                                       T* __restrict__ dv_out, int64_t lddv, int Nq, int Nk, int H, int hd,
-                                                                       float scale, int causal, float p_drop, uint64_t seed) {
+__global__ __launch_bounds__(AT_THREADS) void attn_qkv_bwd_dkdv_kernel(const me_attn_qkv_desc d) {
     typedef Cfg<T, HD> C;
     typedef typename Chunk<T>::type chunk_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int TB = TRead<T, HD>::kNeedsTransposedTile ? C::T_BYTES : 0;   // bf16 reads the row tiles transposed (tr)
+    constexpr bool TT = TRead<T, HD>::kNeedsTransposedTile;
+    constexpr int TB = TT ? C::T_BYTES : 0;      // bf16 reads the row tiles transposed (tr)
     char* Qs = smem;                           // [64 q][HD]
     char* dOs = Qs + C::R_BYTES;               // [64 q][HD]
     char* QTs = dOs + C::R_BYTES;              // [HD][64 q]   (fp32 only)
@@ -221,320 +255,177 @@ __global__ __launch_bounds__(AT_THREADS) void attn_qkv_bwd_dkdv_kernel(const T* 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
     const int b = blockIdx.z, head = blockIdx.y;
+    const int Nq = d.Nq, Nk = d.Nk, hd = d.head_dim;
     const int kblock = blockIdx.x;
     const int kvbase = kblock * QPB + wave * 32;
-    const T* qptr = q + (int64_t)b * Nq * ldq + head * hd;
-    const T* kptr = k + (int64_t)b * Nk * ldk + head * hd;
-    const T* vptr = v + (int64_t)b * Nk * ldv + head * hd;
-    const T* doptr = dout + (int64_t)b * Nq * lddo + head * hd;
-    const float* lse_bh = lse + ((int64_t)b * H + head) * Nq;
-    const float* del_bh = delta + ((int64_t)b * H + head) * Nq;
+    const Scores sc = scores_of(d, b, head);
+    const T* qptr = head_rows((const T*)d.q, d.ld_q, b, Nq, head, hd);
+    const T* doptr = head_rows((const T*)d.dout, d.ld_dout, b, Nq, head, hd);
+    const float* lse_bh = d.lse + (int64_t)sc.bh * Nq;
+    const float* del_bh = d.delta + (int64_t)sc.bh * Nq;
 
     chunk_t kf[C::NKK], vf[C::NKK];
-    {
-        const int kvrow = (kvbase + l31 < Nk) ? kvbase + l31 : Nk - 1;
-#pragma unroll
-        for (int kk = 0; kk < C::NKK; ++kk) {
-            const int d = (2 * kk + h) * C::E;
-            u32x4 rk = (d < hd) ? *reinterpret_cast<const u32x4*>(kptr + (int64_t)kvrow * ldk + d) : zero4();
-            u32x4 rv = (d < hd) ? *reinterpret_cast<const u32x4*>(vptr + (int64_t)kvrow * ldv + d) : zero4();
-            kf[kk] = *reinterpret_cast<chunk_t*>(&rk);
-            vf[kk] = *reinterpret_cast<chunk_t*>(&rv);
-        }
-    }
+    const int kvrow = min(kvbase + l31, Nk - 1);
+    row_frags_load<HD>(head_rows((const T*)d.k, d.ld_k, b, Nk, head, hd) + (int64_t)kvrow * d.ld_k, hd, h, kf);
+    row_frags_load<HD>(head_rows((const T*)d.v, d.ld_v, b, Nk, head, hd) + (int64_t)kvrow * d.ld_v, hd, h, vf);
     f32x16 dk[NDBO], dv[NDBO];
-#pragma unroll
-    for (int db = 0; db < NDBO; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { dk[db][r] = 0.f; dv[db][r] = 0.f; }
+    acc_zero(dk);
+    acc_zero(dv);
     const bool active = kvbase < Nk;
     const int kvi = kvbase + l31;
-    const bool kv_ok = kvi < Nk;
-    const int ntiles = (Nq + KVT - 1) / KVT;
     // causal (Nq == Nk): query tiles that end before the block's first key see none of its keys.  Block-uniform; kblock * QPB < Nk = Nq,
     // so j0 < ntiles and the first staged tile exists.
-    const int j0 = causal ? (kblock * QPB) / KVT : 0;
+    const int j0 = d.causal ? (kblock * QPB) / KVT : 0;
 
-    constexpr bool TT = TRead<T, HD>::kNeedsTransposedTile;
     RowStage<T, HD> qs, dos;
     float lse_r = INFINITY, del_r = 0.f;
-    auto gload = [&](int q0) {
-        qs.load(qptr, ldq, q0, Nq, hd, tid);
-        dos.load(doptr, lddo, q0, Nq, hd, tid);
-        if (tid < KVT) {
-            const int qq = q0 + tid;
-            lse_r = (qq < Nq) ? lse_bh[qq] : INFINITY;          // exp(s - inf) = 0 masks padded queries
-            del_r = (qq < Nq) ? del_bh[qq] : 0.f;
-        }
-    };
-    gload(j0 * KVT);
-    for (int j = j0; j < ntiles; ++j) {
-        __syncthreads();
-        qs.store(Qs, tid);
-        dos.store(dOs, tid);
-        if (TT) {
-            store_transposed<HD>(qs, QTs, tid);
-            store_transposed<HD>(dos, dOTs, tid);
-        }
-        if (tid < KVT) {
-            lse_s[tid] = lse_r;
-            del_s[tid] = del_r;
-        }
-        __syncthreads();
-        if (j + 1 < ntiles) gload((j + 1) * KVT);            // next tile's global loads fly during this tile's MFMAs
-        if (!active || (causal && j * KVT + KVT - 1 < kvbase)) continue;      // wave-uniform: the tile's last query precedes the wave's first key
-        f32x16 s[2], dp[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[u][r] = 0.f; dp[u][r] = 0.f; }
-#pragma unroll
-            for (int kk = 0; kk < C::NKK; ++kk) {
-                s[u] = mma_chunk(rtile_chunk<T, HD>(Qs, 32 * u + l31, 2 * kk + h), kf[kk], s[u]);      // S[q][kv]
-                dp[u] = mma_chunk(rtile_chunk<T, HD>(dOs, 32 * u + l31, 2 * kk + h), vf[kk], dp[u]);   // dP[q][kv]
+    walk_tiles(
+        j0, (Nq + KVT - 1) / KVT,
+        [&](int q0) INLINED {
+            qs.load(qptr, d.ld_q, q0, Nq, hd, tid);
+            dos.load(doptr, d.ld_dout, q0, Nq, hd, tid);
+            if (tid < KVT) {
+                const int qq = q0 + tid;
+                lse_r = (qq < Nq) ? lse_bh[qq] : INFINITY;          // exp(s - inf) = 0 masks padded queries
+                del_r = (qq < Nq) ? del_bh[qq] : 0.f;
             }
-            // lane: kv = l31 (fixed), regs: q = 32u + acc_row(r,h)
+        },
+        [&]() INLINED {
+            qs.store(Qs, tid);
+            dos.store(dOs, tid);
+            if constexpr (TT) {
+                store_transposed<HD>(qs, QTs, tid);
+                store_transposed<HD>(dos, dOTs, tid);
+            }
+            if (tid < KVT) {
+                lse_s[tid] = lse_r;
+                del_s[tid] = del_r;
+            }
+        },
+        [&](int j) INLINED {
+            if (!active || (d.causal && j * KVT + KVT - 1 < kvbase)) return;      // wave-uniform: the tile's last query precedes the wave's first key
+            f32x16 s[2], dp[2];
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 L = *reinterpret_cast<const f32x4*>(lse_s + 32 * u + 8 * g + 4 * h);
-                const f32x4 D = *reinterpret_cast<const f32x4*>(del_s + 32 * u + 8 * g + 4 * h);
+            for (int u = 0; u < 2; ++u) {
+                s[u] = subtile_product<T, HD>(Qs, u, lane, kf);         // S[q][kv]
+                dp[u] = subtile_product<T, HD>(dOs, u, lane, vf);       // dP[q][kv]
+                // lane: kv = l31 (fixed), regs: q = 32u + acc_row(r,h)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = 4 * g + e;
-                    const int qq = j * KVT + 32 * u + acc_row(r, h);
-                    const float p = (kv_ok && (!causal || kvi <= qq)) ? __expf(s[u][r] * scale - L[e]) : 0.f;
-                    float pm = p, dpm = dp[u][r];
-                    if (p_drop > 0.f) {      // same mask as forward: dV sees the dropped P, dS the dropped dP
-                        const uint64_t idx = (((uint64_t)b * H + head) * Nq + (uint64_t)qq) * (uint64_t)Nk + (uint64_t)kvi;
-                        const float keep = u01_hash(seed, idx) >= p_drop ? 1.0f / (1.0f - p_drop) : 0.f;
-                        pm *= keep; dpm *= keep;
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 L = *reinterpret_cast<const f32x4*>(lse_s + 32 * u + 8 * g + 4 * h);
+                    const f32x4 D = *reinterpret_cast<const f32x4*>(del_s + 32 * u + 8 * g + 4 * h);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        sc.p_ds(s[u], dp[u], 4 * g + e, L[e], D[e], kvi, j * KVT + 32 * u + acc_row(4 * g + e, h));
+                }
+                // this 32-query half goes into dV / dK before the other half's S and dP are formed (chunks still in ascending order, with
+                // half the S / dP registers live)
+#pragma unroll
+                for (int c = u * (C::NPC / 2); c < (u + 1) * (C::NPC / 2); ++c) {
+                    const chunk_t pb = pack_chunk((const T*)nullptr, s, c);
+                    const chunk_t dsb = pack_chunk((const T*)nullptr, dp, c);
+#pragma unroll
+                    for (int db = 0; db < NDBO; ++db) {
+                        dv[db] = mma_chunk(TRead<T, HD>::chunk(dOTs, dOs, DB0 + db, c, lane), pb, dv[db]);   // dV^T[d][kv]
+                        dk[db] = mma_chunk(TRead<T, HD>::chunk(QTs, Qs, DB0 + db, c, lane), dsb, dk[db]);  // dK^T[d][kv]
                     }
-                    s[u][r] = pm;                                  // (dropped) P
-                    dp[u][r] = p * (dpm - D[e]) * scale;           // dS
                 }
             }
-            // this 32-query half goes into dV / dK before the other half's S and dP are formed (chunks still in ascending order, with half
-            // the S / dP registers live)
-#pragma unroll
-            for (int c = u * (C::NPC / 2); c < (u + 1) * (C::NPC / 2); ++c) {
-                const chunk_t pb = pack_chunk((const T*)nullptr, s, c);
-                const chunk_t dsb = pack_chunk((const T*)nullptr, dp, c);
-#pragma unroll
-                for (int db = 0; db < NDBO; ++db) {
-                    dv[db] = mma_chunk(TRead<T, HD>::chunk(dOTs, dOs, DB0 + db, c, lane), pb, dv[db]);   // dV^T[d][kv]
-                    dk[db] = mma_chunk(TRead<T, HD>::chunk(QTs, Qs, DB0 + db, c, lane), dsb, dk[db]);  // dK^T[d][kv]
-                }
-            }
-        }
-    }
-    if (!active || !kv_ok) return;
-    T* dkrow = dk_out + ((int64_t)b * Nk + kvi) * lddk + head * hd;
-    T* dvrow = dv_out + ((int64_t)b * Nk + kvi) * lddv + head * hd;
-#pragma unroll
-    for (int db = 0; db < NDBO; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d = 32 * (DB0 + db) + 8 * g + 4 * h;
-            if (d < hd) {
-                store_quad<T>(dkrow + d, f32x4{dk[db][4 * g], dk[db][4 * g + 1], dk[db][4 * g + 2], dk[db][4 * g + 3]});
-                store_quad<T>(dvrow + d, f32x4{dv[db][4 * g], dv[db][4 * g + 1], dv[db][4 * g + 2], dv[db][4 * g + 3]});
-            }
-        }
+        });
+    if (!active || kvi >= Nk) return;
+    acc_store_row_pair<DB0>(head_rows((T*)d.dk, d.ld_dk, b, Nk, head, hd, kvi), dk, 1.0f,
+                            head_rows((T*)d.dv, d.ld_dv, b, Nk, head, hd, kvi), dv, 1.0f, hd, h);
 }
 
-// ---- delta for bf16: delta[q] = sum_k P~[q,k] dP[q,k] (P~: the dropped probabilities) from the tiles, in fp32.  In exact arithmetic this is
-// dO . O, which is how the fp32 path (and me_attention_bwd) forms it; in bf16 that O is the rounded output of a forward that rounded P
-// too, and in the first rows of a causal call, where a few keys carry large probabilities, the error reaches dS undamped (measured: dQ
-// off by 0.5 % of max|dQ| at N = 129, head_dim 96).  Formed here, dS sums to zero over the keys as it should.  Same walk as the dQ kernel.
-template <typename T, int HD>
-__global__ __launch_bounds__(AT_THREADS) void attn_qkv_delta_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ k, int64_t ldk,
-                                                                    const T* __restrict__ v, int64_t ldv, const T* __restrict__ dout,
-                                                                    int64_t lddo, const float* __restrict__ lse, float* __restrict__ delta,
-                                                                    int Nq, int Nk, int H, int hd, float scale, int causal, float p_drop,
-                                                                    uint64_t seed) {
+// ---- dQ, and delta for bf16: a wave owns 32 queries and walks the 64-key tiles they see, recomputing S^T and dP^T.  Two consumers:
+//   dQ (DELTA false): dS^T from lse / delta, dQ^T += K^T dS^T.
+//   delta (DELTA true): delta[q] = sum_k P~[q,k] dP[q,k] (P~: the dropped probabilities) from the tiles, in fp32.  In exact arithmetic this is
+//   dO . O, which is how the fp32 path (and me_attention_bwd) forms it; in bf16 that O is the rounded output of a forward that rounded P
+//   too, and in the first rows of a causal call, where a few keys carry large probabilities, the error reaches dS undamped (measured: dQ
+//   off by 0.5 % of max|dQ| at N = 129, head_dim 96).  Formed here, dS sums to zero over the keys as it should.
+template <typename T, int HD, bool DELTA> __device__ __forceinline__ void qrows_bwd(const me_attn_qkv_desc& d) {
     typedef Cfg<T, HD> C;
     typedef typename Chunk<T>::type chunk_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr bool TT = !DELTA && TRead<T, HD>::kNeedsTransposedTile;
     char* Ks = smem;                    // [64 kv][HD]
     char* Vs = Ks + C::R_BYTES;         // [64 kv][HD]
+    char* KTs = Vs + C::R_BYTES;        // [HD][64 kv]   (dQ, fp32 only)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
     const int b = blockIdx.z, head = blockIdx.y;
+    const int Nq = d.Nq, Nk = d.Nk, hd = d.head_dim;
     const int qbase = blockIdx.x * QPB + wave * 32;
-    const T* qptr = q + (int64_t)b * Nq * ldq + head * hd;
-    const T* kptr = k + (int64_t)b * Nk * ldk + head * hd;
-    const T* vptr = v + (int64_t)b * Nk * ldv + head * hd;
-    const T* doptr = dout + (int64_t)b * Nq * lddo + head * hd;
+    const Scores sc = scores_of(d, b, head);
+    const T* kptr = head_rows((const T*)d.k, d.ld_k, b, Nk, head, hd);
+    const T* vptr = head_rows((const T*)d.v, d.ld_v, b, Nk, head, hd);
 
     const int qi = qbase + l31;
     const bool q_ok = qi < Nq;
     const int qrow = q_ok ? qi : Nq - 1;
     chunk_t qf[C::NKK], dof[C::NKK];
-#pragma unroll
-    for (int kk = 0; kk < C::NKK; ++kk) {
-        const int d = (2 * kk + h) * C::E;
-        u32x4 rq = (d < hd) ? *reinterpret_cast<const u32x4*>(qptr + (int64_t)qrow * ldq + d) : zero4();
-        u32x4 rd = (d < hd) ? *reinterpret_cast<const u32x4*>(doptr + (int64_t)qrow * lddo + d) : zero4();
-        qf[kk] = *reinterpret_cast<chunk_t*>(&rq);
-        dof[kk] = *reinterpret_cast<chunk_t*>(&rd);
-    }
-    const float lse_q = lse[((int64_t)b * H + head) * Nq + qrow];
-    const bool active = qbase < Nq;
-    int ntiles = (Nk + KVT - 1) / KVT;
-    if (causal) {                        // block-uniform, as in the forward
-        const int qlast = min(blockIdx.x * QPB + QPB - 1, Nq - 1);
-        ntiles = min(ntiles, qlast / KVT + 1);
-    }
+    row_frags_load<HD>(head_rows((const T*)d.q, d.ld_q, b, Nq, head, hd) + (int64_t)qrow * d.ld_q, hd, h, qf);
+    row_frags_load<HD>(head_rows((const T*)d.dout, d.ld_dout, b, Nq, head, hd) + (int64_t)qrow * d.ld_dout, hd, h, dof);
+    const float lse_q = d.lse[(int64_t)sc.bh * Nq + qrow];
+    const float del_q = DELTA ? 0.f : d.delta[(int64_t)sc.bh * Nq + qrow];
+    f32x16 dq[DELTA ? 1 : C::NDB];
+    acc_zero(dq);
     float acc = 0.f;
-    RowStage<T, HD> ks, vs;
-    auto gload = [&](int kv0) {
-        ks.load(kptr, ldk, kv0, Nk, hd, tid);
-        vs.load(vptr, ldv, kv0, Nk, hd, tid);
-    };
-    gload(0);
-    for (int j = 0; j < ntiles; ++j) {
-        const int kv0 = j * KVT;
-        __syncthreads();
-        ks.store(Ks, tid);
-        vs.store(Vs, tid);
-        __syncthreads();
-        if (j + 1 < ntiles) gload((j + 1) * KVT);
-        if (!active || (causal && kv0 > qbase + 31)) continue;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            f32x16 s, dp;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-            for (int kk = 0; kk < C::NKK; ++kk) {
-                s = mma_chunk(rtile_chunk<T, HD>(Ks, 32 * u + l31, 2 * kk + h), qf[kk], s);       // S^T[kv][q]
-                dp = mma_chunk(rtile_chunk<T, HD>(Vs, 32 * u + l31, 2 * kk + h), dof[kk], dp);    // dP^T[kv][q]
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int kv = kv0 + 32 * u + acc_row(r, h);
-                const float p = qkv_visible(kv, qi, Nk, causal) ? __expf(s[r] * scale - lse_q) : 0.f;
-                float dpm = dp[r];
-                if (p_drop > 0.f) {
-                    const uint64_t idx = (((uint64_t)b * H + head) * Nq + (uint64_t)qi) * (uint64_t)Nk + (uint64_t)kv;
-                    dpm = u01_hash(seed, idx) >= p_drop ? dpm * (1.0f / (1.0f - p_drop)) : 0.f;
-                }
-                acc += p * dpm;
-            }
-        }
-    }
-    if (!active) return;
-    acc += __shfl_xor(acc, 32, 64);
-    if (q_ok && h == 0) delta[((int64_t)b * H + head) * Nq + qi] = acc;
-}
-
-// ---- dQ: a wave owns 32 queries and walks the 64-key tiles they see
-template <typename T, int HD>
-__global__ __launch_bounds__(AT_THREADS) void attn_qkv_bwd_dq_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ k, int64_t ldk,
-                                                                     const T* __restrict__ v, int64_t ldv, const T* __restrict__ dout,
-                                                                     int64_t lddo, const float* __restrict__ lse,
-                                                                     const float* __restrict__ delta, T* __restrict__ dq_out, int64_t lddq,
-                                                                     int Nq, int Nk, int H, int hd, float scale, int causal, float p_drop,
-                                                                     uint64_t seed) {
-    typedef Cfg<T, HD> C;
-    typedef typename Chunk<T>::type chunk_t;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Ks = smem;                    // [64 kv][HD]
-    char* Vs = Ks + C::R_BYTES;         // [64 kv][HD]
-    char* KTs = Vs + C::R_BYTES;        // [HD][64 kv]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int b = blockIdx.z, head = blockIdx.y;
-    const int qbase = blockIdx.x * QPB + wave * 32;
-    const T* qptr = q + (int64_t)b * Nq * ldq + head * hd;
-    const T* kptr = k + (int64_t)b * Nk * ldk + head * hd;
-    const T* vptr = v + (int64_t)b * Nk * ldv + head * hd;
-    const T* doptr = dout + (int64_t)b * Nq * lddo + head * hd;
-
-    const int qi = qbase + l31;
-    const bool q_ok = qi < Nq;
-    const int qrow = q_ok ? qi : Nq - 1;
-    chunk_t qf[C::NKK], dof[C::NKK];
-#pragma unroll
-    for (int kk = 0; kk < C::NKK; ++kk) {
-        const int d = (2 * kk + h) * C::E;
-        u32x4 rq = (d < hd) ? *reinterpret_cast<const u32x4*>(qptr + (int64_t)qrow * ldq + d) : zero4();
-        u32x4 rd = (d < hd) ? *reinterpret_cast<const u32x4*>(doptr + (int64_t)qrow * lddo + d) : zero4();
-        qf[kk] = *reinterpret_cast<chunk_t*>(&rq);
-        dof[kk] = *reinterpret_cast<chunk_t*>(&rd);
-    }
-    const float lse_q = lse[((int64_t)b * H + head) * Nq + qrow];
-    const float del_q = delta[((int64_t)b * H + head) * Nq + qrow];
-    f32x16 dq[C::NDB];
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dq[db][r] = 0.f;
     const bool active = qbase < Nq;
-    int ntiles = (Nk + KVT - 1) / KVT;
-    if (causal) {                        // block-uniform, as in the forward
-        const int qlast = min(blockIdx.x * QPB + QPB - 1, Nq - 1);
-        ntiles = min(ntiles, qlast / KVT + 1);
-    }
 
-    constexpr bool TT = TRead<T, HD>::kNeedsTransposedTile;
     RowStage<T, HD> ks, vs;
-    auto gload = [&](int kv0) {
-        ks.load(kptr, ldk, kv0, Nk, hd, tid);
-        vs.load(vptr, ldv, kv0, Nk, hd, tid);
-    };
-    gload(0);
-    for (int j = 0; j < ntiles; ++j) {
-        const int kv0 = j * KVT;
-        __syncthreads();
-        ks.store(Ks, tid);
-        vs.store(Vs, tid);
-        if (TT) store_transposed<HD>(ks, KTs, tid);
-        __syncthreads();
-        if (j + 1 < ntiles) gload((j + 1) * KVT);
-        if (!active || (causal && kv0 > qbase + 31)) continue;
-        f32x16 s[2], dp[2];
+    walk_tiles(
+        0, key_tiles(Nq, Nk, d.causal),
+        [&](int kv0) INLINED {
+            ks.load(kptr, d.ld_k, kv0, Nk, hd, tid);
+            vs.load(vptr, d.ld_v, kv0, Nk, hd, tid);
+        },
+        [&]() INLINED {
+            ks.store(Ks, tid);
+            vs.store(Vs, tid);
+            if constexpr (TT) store_transposed<HD>(ks, KTs, tid);
+        },
+        [&](int j) INLINED {
+            const int kv0 = j * KVT;
+            if (!active || (d.causal && kv0 > qbase + 31)) return;      // wave-uniform: no row of this wave sees the tile
+            f32x16 s[2], dp[2];
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
+            for (int u = 0; u < 2; ++u) {
+                s[u] = subtile_product<T, HD>(Ks, u, lane, qf);         // S^T[kv][q]
+                dp[u] = subtile_product<T, HD>(Vs, u, lane, dof);       // dP^T[kv][q]
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { s[u][r] = 0.f; dp[u][r] = 0.f; }
-#pragma unroll
-            for (int kk = 0; kk < C::NKK; ++kk) {
-                s[u] = mma_chunk(rtile_chunk<T, HD>(Ks, 32 * u + l31, 2 * kk + h), qf[kk], s[u]);      // S^T[kv][q]
-                dp[u] = mma_chunk(rtile_chunk<T, HD>(Vs, 32 * u + l31, 2 * kk + h), dof[kk], dp[u]);   // dP^T[kv][q]
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int kv = kv0 + 32 * u + acc_row(r, h);
-                const float p = qkv_visible(kv, qi, Nk, causal) ? __expf(s[u][r] * scale - lse_q) : 0.f;
-                float dpm = dp[u][r];
-                if (p_drop > 0.f) {
-                    const uint64_t idx = (((uint64_t)b * H + head) * Nq + (uint64_t)qi) * (uint64_t)Nk + (uint64_t)kv;
-                    dpm = u01_hash(seed, idx) >= p_drop ? dpm * (1.0f / (1.0f - p_drop)) : 0.f;
+                for (int r = 0; r < 16; ++r) {
+                    const int kv = kv0 + 32 * u + acc_row(r, h);
+                    if constexpr (DELTA) {
+                        const float p = sc.prob(s[u][r], lse_q, kv, qi);
+                        acc += p * (sc.p_drop > 0.f ? sc.dropped(dp[u][r], sc.drop_row(qi), kv) : dp[u][r]);
+                    } else {
+                        sc.p_ds(s[u], dp[u], r, lse_q, del_q, kv, qi);      // dp: dS^T
+                    }
                 }
-                dp[u][r] = p * (dpm - del_q) * scale;          // dS^T
             }
+            if constexpr (!DELTA) {
 #pragma unroll
-        for (int c = 0; c < C::NPC; ++c) {
-            const chunk_t dsb = pack_chunk((const T*)nullptr, dp, c);
+                for (int c = 0; c < C::NPC; ++c) {
+                    const chunk_t dsb = pack_chunk((const T*)nullptr, dp, c);
 #pragma unroll
-            for (int db = 0; db < C::NDB; ++db)
-                dq[db] = mma_chunk(TRead<T, HD>::chunk(KTs, Ks, db, c, lane), dsb, dq[db]);   // dQ^T[d][q]
-        }
+                    for (int db = 0; db < C::NDB; ++db) dq[db] = mma_chunk(TRead<T, HD>::chunk(KTs, Ks, db, c, lane), dsb, dq[db]);   // dQ^T[d][q]
+                }
+            }
+        });
+    if (!active) return;
+    if constexpr (DELTA) {
+        acc += __shfl_xor(acc, 32, 64);
+        if (q_ok && h == 0) d.delta[(int64_t)sc.bh * Nq + qi] = acc;
+    } else {
+        if (q_ok) acc_store_row(head_rows((T*)d.dq, d.ld_dq, b, Nq, head, hd, qi), dq, 1.0f, hd, h);
     }
-    if (!active || !q_ok) return;
-    T* dqrow = dq_out + ((int64_t)b * Nq + qi) * lddq + head * hd;
-#pragma unroll
-    for (int db = 0; db < C::NDB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d = 32 * db + 8 * g + 4 * h;
-            if (d < hd)
-                store_quad<T>(dqrow + d, f32x4{dq[db][4 * g], dq[db][4 * g + 1], dq[db][4 * g + 2], dq[db][4 * g + 3]});
-        }
+}
+template <typename T, int HD> __global__ __launch_bounds__(AT_THREADS) void attn_qkv_delta_kernel(const me_attn_qkv_desc d) {
+    qrows_bwd<T, HD, true>(d);
+}
+template <typename T, int HD> __global__ __launch_bounds__(AT_THREADS) void attn_qkv_bwd_dq_kernel(const me_attn_qkv_desc d) {
+    qrows_bwd<T, HD, false>(d);
 }
 
 // ---- delta = dO . O
@@ -583,25 +474,23 @@ __global__ __launch_bounds__(256) void attn_delta_vec_kernel(const bf16_t* __res
     }
 }
 
-// ---- host
+// ---- host: every kernel takes the checked descriptor by value
+// blocks of 128 rows x heads x batch items
+dim3 row_blocks(int N, const me_attn_qkv_desc& d) { return dim3((N + QPB - 1) / QPB, d.H, d.B); }
+
 template <typename T, int HD> int launch_fwd(const me_attn_qkv_desc& d, hipStream_t stream) {
     typedef Cfg<T, HD> C;
     const size_t smem = C::R_BYTES + (C::T_BYTES > C::R_BYTES ? C::T_BYTES : C::R_BYTES);   // V tile: transposed (fp32) or row-major (bf16)
-    return attn_launch<attn_qkv_fwd_kernel<T, HD>>("attention tiled fwd", dim3((d.Nq + QPB - 1) / QPB, d.H, d.B), AT_THREADS, smem, smem, stream,
-                                                   (const T*)d.q, d.ld_q, (const T*)d.k, d.ld_k, (const T*)d.v, d.ld_v, (T*)d.out, d.ld_out, d.lse,
-                                                   d.Nq, d.Nk, d.H, d.head_dim, d.scale, d.causal, d.p_drop, d.seed);
+    return attn_launch<attn_qkv_fwd_kernel<T, HD>>("attention tiled fwd", row_blocks(d.Nq, d), AT_THREADS, smem, smem, stream, d);
 }
 template <typename T, int HD> int launch_bwd(const me_attn_qkv_desc& d, hipStream_t stream) {
     typedef Cfg<T, HD> C;
     constexpr size_t TB = TRead<T, HD>::kNeedsTransposedTile ? C::T_BYTES : 0;
     const size_t smem1 = 2 * C::R_BYTES + 2 * TB + 2 * KVT * sizeof(float);
     const size_t smem2 = 2 * C::R_BYTES + TB;
-    const dim3 gridk((d.Nk + QPB - 1) / QPB, d.H, d.B);
     auto dkdv = [&](auto DB0, auto NDBO) {
-        return attn_launch<attn_qkv_bwd_dkdv_kernel<T, HD, DB0(), NDBO()>>("attention tiled bwd (dkdv)", gridk, AT_THREADS, smem1, smem1, stream,
-                                                                           (const T*)d.q, d.ld_q, (const T*)d.k, d.ld_k, (const T*)d.v, d.ld_v,
-                                                                           (const T*)d.dout, d.ld_dout, d.lse, d.delta, (T*)d.dk, d.ld_dk, (T*)d.dv,
-                                                                           d.ld_dv, d.Nq, d.Nk, d.H, d.head_dim, d.scale, d.causal, d.p_drop, d.seed);
+        return attn_launch<attn_qkv_bwd_dkdv_kernel<T, HD, DB0(), NDBO()>>("attention tiled bwd (dkdv)", row_blocks(d.Nk, d), AT_THREADS, smem1, smem1,
+                                                                           stream, d);
     };
     // fp32 at head_dim > 64: two launches of two d blocks each, no scratch, S and dP formed in both -- against ONE launch of
     // attn_qkv_bwd_dkdv_kernel<float, 128, 0, 4> (440 bytes of scratch per lane), same bits.  NOT TIMED against each other: the rule
@@ -613,17 +502,12 @@ template <typename T, int HD> int launch_bwd(const me_attn_qkv_desc& d, hipStrea
     } else {
         if (int rc = dkdv(Int<0>(), Int<C::NDB>())) return rc;
     }
-    return attn_launch<attn_qkv_bwd_dq_kernel<T, HD>>("attention tiled bwd (dq)", dim3((d.Nq + QPB - 1) / QPB, d.H, d.B), AT_THREADS, smem2, smem2, stream,
-                                                      (const T*)d.q, d.ld_q, (const T*)d.k, d.ld_k, (const T*)d.v, d.ld_v, (const T*)d.dout, d.ld_dout,
-                                                      d.lse, d.delta, (T*)d.dq, d.ld_dq, d.Nq, d.Nk, d.H, d.head_dim, d.scale, d.causal, d.p_drop, d.seed);
+    return attn_launch<attn_qkv_bwd_dq_kernel<T, HD>>("attention tiled bwd (dq)", row_blocks(d.Nq, d), AT_THREADS, smem2, smem2, stream, d);
 }
-// bf16 delta of me_attention_qkv_bwd: from the tiles (attn_qkv_delta_kernel, which says why)
+// bf16 delta of me_attention_qkv_bwd: from the tiles (qrows_bwd, which says why)
 template <int HD> int launch_qkv_delta_bf16(const me_attn_qkv_desc& d, hipStream_t stream) {
-    typedef bf16_t T;
-    constexpr size_t smem = 2 * Cfg<T, HD>::R_BYTES;
-    return attn_launch<attn_qkv_delta_kernel<T, HD>>("me_attention_qkv_bwd(delta)", dim3((d.Nq + QPB - 1) / QPB, d.H, d.B), AT_THREADS, smem, smem, stream,
-                                                     (const T*)d.q, d.ld_q, (const T*)d.k, d.ld_k, (const T*)d.v, d.ld_v, (const T*)d.dout, d.ld_dout,
-                                                     d.lse, d.delta, d.Nq, d.Nk, d.H, d.head_dim, d.scale, d.causal, d.p_drop, d.seed);
+    constexpr size_t smem = 2 * Cfg<bf16_t, HD>::R_BYTES;
+    return attn_launch<attn_qkv_delta_kernel<bf16_t, HD>>("me_attention_qkv_bwd(delta)", row_blocks(d.Nq, d), AT_THREADS, smem, smem, stream, d);
 }
 
 // f(Int<HD>) for the instantiated head width

@@ -1,6 +1,9 @@
 // attention_tile.h -- device pieces shared by the tiled attention kernels of attention_qkv.hip and the sequence-resident kernels of
 // attention.hip: tile geometry, global -> LDS staging, MFMA operand reads.  Device code only.  Included inside no namespace;
 // everything here has internal linkage.
+// Both families (the four tiled kernels and the 32-row kernels, rows32_* of attention.hip) use Cfg, zero4, rtile_chunk, tr_chunk,
+// pack_chunk and the per-lane pieces at the end: acc_zero, row_frags_load, acc_store_row / acc_store_row_pair (on store_quad).  RowStage,
+// TRead and the fp32 ttile_chunk serve the tiled kernels alone (the 32-row kernels are bf16 and stage through Rows32Stage).
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -22,9 +25,6 @@ template <typename T, int HD> struct Cfg {
     static constexpr int T_BYTES = HD * TROW;                // [HD][64] transposed tile
     static constexpr int NPC = KVT / (2 * E);                // P chunks per 64-key tile (4 bf16 / 8 fp32)
     static constexpr int R_ITEMS = (KVT * CPR + AT_THREADS - 1) / AT_THREADS;
-    static constexpr int T_ITEMS = sizeof(T) == 2 ? ((KVT / 2) * CPR + AT_THREADS - 1) / AT_THREADS
-                                                  : (KVT * CPR + AT_THREADS - 1) / AT_THREADS;
-    static constexpr int T_REGS = sizeof(T) == 2 ? 2 * T_ITEMS : T_ITEMS;
 };
 
 __device__ __forceinline__ u32x4 zero4() { return u32x4{0u, 0u, 0u, 0u}; }
@@ -52,83 +52,15 @@ template <typename T, int HD> struct RowStage {
     }
 };
 
-// ---- transposed [HD][64] tile (rows = d, 64 keys/queries contiguous): global -> regs -> LDS
-template <typename T, int HD> struct TransStage;
-template <int HD> struct TransStage<bf16_t, HD> {
-    typedef Cfg<bf16_t, HD> C;
-    u32x4 v[C::T_REGS];
-    __device__ __forceinline__ void load(const bf16_t* __restrict__ base, int64_t ld, int r0, int nrows, int hd, int tid) {
-#pragma unroll
-        for (int i = 0; i < C::T_ITEMS; ++i) {
-            const int it = tid + AT_THREADS * i;
-            const int chunk = it % C::CPR, p = it / C::CPR;
-            const int row = r0 + 2 * p;
-            const bool okc = (p < KVT / 2) && (chunk * 8 < hd);
-            v[2 * i] = (okc && row < nrows) ? *reinterpret_cast<const u32x4*>(base + (int64_t)row * ld + chunk * 8) : zero4();
-            v[2 * i + 1] = (okc && row + 1 < nrows) ? *reinterpret_cast<const u32x4*>(base + (int64_t)(row + 1) * ld + chunk * 8) : zero4();
-        }
-    }
-    __device__ __forceinline__ void store(char* lds, int tid) const {
-#pragma unroll
-        for (int i = 0; i < C::T_ITEMS; ++i) {
-            const int it = tid + AT_THREADS * i;
-            const int chunk = it % C::CPR, p = it / C::CPR;
-            if (p < KVT / 2) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const uint32_t w0 = v[2 * i][e >> 1], w1 = v[2 * i + 1][e >> 1];
-                    const uint32_t lo = (e & 1) ? (w0 >> 16) : (w0 & 0xffffu);
-                    const uint32_t hi = (e & 1) ? (w1 & 0xffff0000u) : (w1 << 16);
-                    *reinterpret_cast<uint32_t*>(lds + (chunk * 8 + e) * C::TROW + p * 4) = lo | hi;
-                }
-            }
-        }
-    }
-};
-template <int HD> struct TransStage<float, HD> {
-    typedef Cfg<float, HD> C;
-    u32x4 v[C::T_REGS];
-    __device__ __forceinline__ void load(const float* __restrict__ base, int64_t ld, int r0, int nrows, int hd, int tid) {
-#pragma unroll
-        for (int i = 0; i < C::T_ITEMS; ++i) {
-            const int it = tid + AT_THREADS * i;
-            const int chunk = it % C::CPR, row = it / C::CPR;
-            const bool ok = (row < KVT) && (r0 + row < nrows) && (chunk * 4 < hd);
-            v[i] = ok ? *reinterpret_cast<const u32x4*>(base + (int64_t)(r0 + row) * ld + chunk * 4) : zero4();
-        }
-    }
-    __device__ __forceinline__ void store(char* lds, int tid) const {
-#pragma unroll
-        for (int i = 0; i < C::T_ITEMS; ++i) {
-            const int it = tid + AT_THREADS * i;
-            const int chunk = it % C::CPR, row = it / C::CPR;
-            if (row < KVT) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    *reinterpret_cast<uint32_t*>(lds + (chunk * 4 + e) * C::TROW + row * 4) = v[i][e];
-            }
-        }
-    }
-};
-
 // A-operand chunk from a row-major tile: row, d-chunk index (2*kk + h)
 template <typename T, int HD>
 __device__ __forceinline__ typename Chunk<T>::type rtile_chunk(const char* lds, int row, int chunk) {
     return *reinterpret_cast<const typename Chunk<T>::type*>(lds + row * Cfg<T, HD>::RROW + chunk * 16);
 }
-// A-operand chunk from a transposed tile: row d, P-chunk c (0..NPC-1) of the 64-wide tile, half h.
-// Element e of the chunk is reduction index (within the 64-tile):
-//   bf16: 16c + 4h + (e&3) + 8(e>>2)        fp32: 8c + 4h + e
-// which is exactly the index that accumulator register (E*(c % (NPC/2)) + e) of 32-subtile u = c / (NPC/2)
-// holds in half h (acc_row), so S/P registers feed the next MFMA without any cross-lane movement.
-template <int HD>
-__device__ __forceinline__ bf16x8 ttile_chunk(const bf16_t*, const char* lds, int d, int c, int h) {
-    const char* base = lds + d * Cfg<bf16_t, HD>::TROW;
-    union { u32x2 w[2]; bf16x8 b; } u;
-    u.w[0] = *reinterpret_cast<const u32x2*>(base + (16 * c + 4 * h) * 2);
-    u.w[1] = *reinterpret_cast<const u32x2*>(base + (16 * c + 8 + 4 * h) * 2);
-    return u.b;
-}
+// fp32 A-operand chunk from a transposed [HD][64] tile: row d, P-chunk c (0..NPC-1) of the 64-wide tile, half h.
+// Element e of the chunk is reduction index 8c + 4h + e within the 64-tile, which is exactly the index that accumulator register
+// (4*(c % 4) + e) of 32-subtile u = c / 4 holds in half h (acc_row), so S/P registers feed the next MFMA without any cross-lane
+// movement.  (bf16, tr_chunk below: 16c + 4h + (e&3) + 8(e>>2), registers 8*(c % 2) + e of u = c / 2.)
 template <int HD>
 __device__ __forceinline__ f32x4 ttile_chunk(const float*, const char* lds, int d, int c, int h) {
     return *reinterpret_cast<const f32x4*>(lds + d * Cfg<float, HD>::TROW + (8 * c + 4 * h) * 4);
@@ -186,6 +118,61 @@ template <> __device__ __forceinline__ void store_quad<bf16_t>(bf16_t* p, f32x4 
     bf16x4 o;
     o[0] = (bf16_t)v[0]; o[1] = (bf16_t)v[1]; o[2] = (bf16_t)v[2]; o[3] = (bf16_t)v[3];
     *reinterpret_cast<bf16x4*>(p) = o;
+}
+
+// ---- per-lane pieces of a wave that owns 32 rows: lane = row l31 = lane & 31, half h = lane >> 5 (common.h)
+template <int NDB> __device__ __forceinline__ void acc_zero(f32x16 (&acc)[NDB]) {
+#pragma unroll
+    for (int db = 0; db < NDB; ++db)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[db][r] = 0.f;
+}
+
+// The B-operand fragments of one row straight from HBM (row: that row's head slice); chunks past hd are zeros.  Branch-free: a chunk
+// past hd reads a clamped (valid) address and is zeroed after the load
+template <int HD, typename T>
+__device__ __forceinline__ void row_frags_load(const T* row, int hd, int h, typename Chunk<T>::type (&f)[Cfg<T, HD>::NKK]) {
+#pragma unroll
+    for (int kk = 0; kk < Cfg<T, HD>::NKK; ++kk) {
+        const int d = (2 * kk + h) * Cfg<T, HD>::E;
+        const bool ok = d < hd;
+        u32x4 raw = *reinterpret_cast<const u32x4*>(row + (ok ? d : 0));
+        raw = ok ? raw : zero4();
+        f[kk] = *reinterpret_cast<typename Chunk<T>::type*>(&raw);
+    }
+}
+
+// A lane's row of accumulators (transposed layout: lane = row l31, registers = d) times mul, four elements per store.  grow: that row's
+// head slice; the caller has checked that the row exists.  acc holds the NDBO 32-wide d blocks from DB0 on.  The pair form stores two
+// rows (dK and dV) under one d < hd test per quad: as two single calls it measured +33 / +64 instructions in
+// attn_bwd_dkdv_chunk_kernel<32 / 64> and +77 / +145 in attn_bwd_mid_kernel (pair: 0 / 0 and +15 / +25), all outside the loops
+// (profiles/attention_rows32_refactor.txt)
+template <typename T> __device__ __forceinline__ void acc_store_quad(T* p, const f32x16& acc, int g, float mul) {
+    store_quad<T>(p, f32x4{acc[4 * g] * mul, acc[4 * g + 1] * mul, acc[4 * g + 2] * mul, acc[4 * g + 3] * mul});
+}
+template <int DB0 = 0, typename T, int NDBO>
+__device__ __forceinline__ void acc_store_row(T* grow, const f32x16 (&acc)[NDBO], float mul, int hd, int h) {
+#pragma unroll
+    for (int db = 0; db < NDBO; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int d = 32 * (DB0 + db) + 8 * g + 4 * h;
+            if (d < hd) acc_store_quad(grow + d, acc[db], g, mul);
+        }
+}
+template <int DB0 = 0, typename T, int NDBO>
+__device__ __forceinline__ void acc_store_row_pair(T* grow0, const f32x16 (&acc0)[NDBO], float mul0, T* grow1, const f32x16 (&acc1)[NDBO],
+                                                   float mul1, int hd, int h) {
+#pragma unroll
+    for (int db = 0; db < NDBO; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int d = 32 * (DB0 + db) + 8 * g + 4 * h;
+            if (d < hd) {
+                acc_store_quad(grow0 + d, acc0[db], g, mul0);
+                acc_store_quad(grow1 + d, acc1[db], g, mul1);
+            }
+        }
 }
 
 }  // namespace

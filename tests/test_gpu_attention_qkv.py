@@ -121,18 +121,22 @@ def test_attention_qkv_causality(dev, t, dt):
     assert bool(torch.isfinite(dq).all() and torch.isfinite(dk).all() and torch.isfinite(dv).all())
 
 
-@pytest.mark.parametrize("Nq,Nk,causal", tc.QKV_DROPOUT)
-def test_attention_qkv_dropout_exact_mask(dev, Nq, Nk, causal):
-    """p = 0.1 in fp32: forward and gradients against float64 with the mask restated on the host (index ((b*H + h)*Nq + q)*Nk + k)"""
-    p, seed, hd = 0.1, 0x5DEECE66D, 24
+@pytest.mark.parametrize("dt", DTYPES, ids=["f32", "bf16"])
+@pytest.mark.parametrize("Nq,Nk,causal,hd", tc.QKV_DROPOUT)
+def test_attention_qkv_dropout_exact_mask(dev, Nq, Nk, causal, hd, dt):
+    """p = 0.1: forward and gradients against float64 on the dtype-rounded operands with the mask restated on the host (index
+    ((b*H + h)*Nq + q)*Nk + k).  bf16 takes the delta pass of attn_qkv_delta_kernel under dropout; this is its check against a reference."""
+    p, seed = 0.1, 0x5DEECE66D
     keep = tc.qkv_keep(seed, B, H, Nq, Nk, p)
     assert 0.85 < keep.mean() < 0.95
-    (out, lse, grads), (ref, lse_ref, gref) = run_case(dev, Nq, Nk, causal, hd, "q_kv2", torch.float32, p_drop=p, seed=seed)
-    what = f"attention_qkv dropout {Nq}x{Nk} causal={causal}"
-    check_close(out, ref, TOL_F32, what + " out")
-    check_close(lse, lse_ref, TOL_F32, what + " lse (unmasked row sum)")
-    check_grads(grads, gref, TOL_F32, what)
-    (o_other, _, _), _ = run_case(dev, Nq, Nk, causal, hd, "q_kv2", torch.float32, p_drop=p, seed=seed + 1)
+    (out, lse, grads), (ref, lse_ref, gref) = run_case(dev, Nq, Nk, causal, hd, "q_kv2", dt, p_drop=p, seed=seed)
+    what = f"attention_qkv dropout {Nq}x{Nk} causal={causal} hd={hd} {dt}"
+    for nm, g, w in (("out", out, ref), ("lse", lse, lse_ref)) + tuple(zip(("dQ", "dK", "dV"), grads, gref)):
+        print(f"{what} {nm}: max-abs error {float((g.detach().double().cpu() - w).abs().max() / w.abs().max()):.3e} of max|ref|")
+    check_close(out.float(), ref, tol(dt), what + " out")
+    check_close(lse, lse_ref, tol(dt), what + " lse (unmasked row sum)")
+    check_grads(grads, gref, tol(dt), what)
+    (o_other, _, _), _ = run_case(dev, Nq, Nk, causal, hd, "q_kv2", dt, p_drop=p, seed=seed + 1)
     assert not torch.equal(out, o_other)
 
 

@@ -25,7 +25,8 @@ QKV_CAUSAL = [1, 31, 64, 65, 129, 144, 200]
 QKV_HEAD_DIMS = {torch.float32: [4, 8, 24, 64, 96, 128], torch.bfloat16: [8, 24, 64, 96, 128]}
 QKV_LAYOUTS = ["packed3", "q_kv2", "separate_padded"]
 QKV_CAUSALITY_N, QKV_CAUSALITY_T = 144, [0, 63, 64, 100]
-QKV_DROPOUT = [(33, 65, False), (65, 65, True)]                                                       # (Nq, Nk, causal), fp32, p = 0.1
+# (Nq, Nk, causal, head_dim), each in both dtypes, p = 0.1
+QKV_DROPOUT = [(33, 65, False, 24), (65, 65, True, 24), (129, 129, True, 96), (70, 17, False, 64)]
 QKV_EQUIV = [(64, 24), (129, 64), (200, 128)]                                                         # (N, head_dim) against me_attention_*
 
 
@@ -53,6 +54,14 @@ def assert_coverage() -> None:
             assert any(lo < h <= hi for h in hds), (dt, hi)
         assert 96 in hds and 128 in hds and min(hds) == (4 if dt == torch.float32 else 8)
     assert set(QKV_CAUSALITY_T) >= {0, KEY_TILE - 1, KEY_TILE} and QKV_CAUSALITY_N > max(QKV_CAUSALITY_T)
+    # dropout: both variants; a causal case past a key tile and a query block at a head_dim above 64 (the HD 128 instantiations, both
+    # fp32 dK / dV launches); every instantiated width; head_dims that both dtypes take
+    dr = QKV_DROPOUT
+    assert any(c for _, _, c, _ in dr) and any(not c and a != b for a, b, c, _ in dr)
+    assert any(c and a > BLOCK_ROWS and b > KEY_TILE and hd > 64 for a, b, c, hd in dr)
+    for lo, hi in ((0, 32), (32, 64), (64, 128)):
+        assert any(lo < hd <= hi for _, _, _, hd in dr), hi
+    assert all(hd % 8 == 0 for _, _, _, hd in dr)
 
 
 def qkv_cases(dt: torch.dtype):

@@ -1,14 +1,14 @@
-"""Trace of the attention entry points (me_attention_fwd / me_attention_bwd) over every kernel form their route has, for comparing
-two commits: run it at each, the two outputs must be byte-identical.
+"""Trace of the attention entry points (me_attention_fwd / me_attention_bwd, then me_attention_qkv_fwd / _bwd) over every kernel form
+their route has, for comparing two commits: run it at each, the two outputs must be byte-identical.
 
-    python tools/attention_route_trace.py OUT                 # per case: sha256 of out, lse, dqkv
+    python tools/attention_route_trace.py OUT                 # per case: sha256 of out, lse, dqkv (qkv entries: out, lse, dq, dk, dv)
     python tools/attention_route_trace.py --host-time [CALLS]  # wall time of CALLS (2000) back-to-back forward + backward calls
 
-It uses only names that both sides of such a comparison have: ops.attention_fwd / ops.attention_bwd, and the ctypes entries for the
-cases with a padded row stride.  Under `rocprofv3 --kernel-trace -- python tools/attention_route_trace.py OUT` the kernel
+It uses only names that both sides of such a comparison have: ops.attention_fwd / ops.attention_bwd, ops.attention_qkv_fwd /
+ops.attention_qkv_bwd (since 1005188), and the ctypes entries for the cases with a padded row stride.  Under `rocprofv3 --kernel-trace -- python tools/attention_route_trace.py OUT` the kernel
 sequence (name, grid, workgroup, LDS bytes) is the record of which kernel each case took.  The first cases are those of
 tests/test_gpu_ops.py::test_attention_route (profiles/attention_route_equivalence.txt holds the record made with them), the rest walk the
-generic route."""
+generic route, and the records of the qkv entry points come last."""
 import hashlib
 import sys
 import time
@@ -36,6 +36,20 @@ CASES = [(64, 64, "bf16", 0.0, 2, 2), (64, 64, "fp32", 0.0, 2, 2), (65, 64, "bf1
          # the 32-row kernels: resident at HD = 32, a last chunk of 33 rows (masked two-sub-tile tail), three full chunks (no tail step)
          (250, 24, "bf16", 0.0, 2, 2), (545, 32, "bf16", 0.0, 1, 2), (768, 24, "bf16", 0.0, 1, 1)]
 DT = {"bf16": torch.bfloat16, "fp32": torch.float32}
+# me_attention_qkv_*: (Nq, Nk, causal) -- causal N and two-length pairs on every edge of the tiling (one row, a 64-key tile and + 1, a
+# 128-query block + 1, two blocks).  qkv_cases() gives each shape two head_dims, both layouts and both dropout settings, per dtype
+QKV_SHAPES = [(n, n, True) for n in (1, 64, 65, 129, 200)] + [(a, b, False) for a, b in ((1, 65), (33, 1), (129, 65), (144, 96), (70, 17))]
+QKV_HDS = [8, 24, 64, 96, 128]
+
+
+def qkv_cases():
+    """[(Nq, Nk, causal, head_dim, dtype, p_drop, layout)], B = H = 2"""
+    out = []
+    for dt in ("fp32", "bf16"):
+        for rot in (0, 2):
+            for i, (a, b, c) in enumerate(QKV_SHAPES):
+                out.append((a, b, c, QKV_HDS[(i + rot) % 5], dt, 0.1 if (i + rot // 2) % 3 == 0 else 0.0, ("q_kv2", "padded")[(i + rot // 2) % 2]))
+    return out
 
 
 def sha(t):
@@ -80,7 +94,37 @@ def trace(path):
                                0.0, 0, stream_ptr()), "me_attention_bwd")
     torch.cuda.synchronize()
     out_f.write(f"== N={N} hd={hd} bf16 ld_dqkv=3C+4 B={B} H={H} (backward only)\n  delta: {sha(delta)}\n  dqkv: {sha(dqkv)}\n")
+    trace_qkv(out_f)
     out_f.close()
+
+
+def trace_qkv(out_f):
+    """layouts: q_kv2 = a dense Q and K | V as the halves of one [B*Nk, 2C]; padded = three tensors with a row stride of C + 8.  The
+    gradients are written into views of the same layout"""
+    B, H = 2, 2
+    for i, (Nq, Nk, causal, hd, dt, p, layout) in enumerate(qkv_cases()):
+        C = H * hd
+        g = torch.Generator().manual_seed(300 + i)
+        q, k, v, dout = (torch.randn(B * n, C, generator=g).to(dev, DT[dt]) for n in (Nq, Nk, Nk, Nq))
+
+        def place(vals):
+            if layout == "q_kv2":
+                kv = torch.zeros(B * Nk, 2 * C, dtype=DT[dt], device=dev)
+                views = (torch.zeros(B * Nq, C, dtype=DT[dt], device=dev), kv[:, :C], kv[:, C:])
+            else:
+                views = tuple(torch.zeros(x.shape[0], C + 8, dtype=DT[dt], device=dev)[:, :C] for x in vals)
+            for dst, src in zip(views, vals):
+                dst.copy_(src)
+            return views
+
+        qd, kd, vd = place((q, k, v))
+        scale = hd ** -0.5
+        out, lse = ops.attention_qkv_fwd(qd, kd, vd, B, Nq, Nk, H, hd, scale, causal=causal, need_lse=True, p_drop=p, seed=7)
+        dq, dk, dv = ops.attention_qkv_bwd(qd, kd, vd, out, dout, lse, B, Nq, Nk, H, hd, scale, causal=causal, p_drop=p, seed=7,
+                                           grads=place((torch.zeros_like(q), torch.zeros_like(k), torch.zeros_like(v))))
+        torch.cuda.synchronize()
+        out_f.write(f"== qkv Nq={Nq} Nk={Nk} causal={int(causal)} hd={hd} {dt} p_drop={p} {layout} B={B} H={H}\n  out: {sha(out)}\n  lse: {sha(lse)}\n"
+                    f"  dq: {sha(dq)}\n  dk: {sha(dk)}\n  dv: {sha(dv)}\n")
 
 
 def host_time(calls):
