@@ -10,6 +10,7 @@ import torch
 from conftest import TOL_BF16_OP, TOL_F32, check_close
 
 import ts_decoder_cases as tc
+from guarded import Guarded
 from metatransformer_amd import _capi, ops
 
 pytestmark = pytest.mark.gpu
@@ -72,6 +73,62 @@ def test_attention_qkv_fwd_bwd(dev, dt, case):
     check_close(out.float(), ref, tol(dt), what + " out")
     check_close(lse, lse_ref, tol(dt), what + " lse")
     check_grads(grads, gref, tol(dt), what)
+
+
+# the three smallest shapes of test_gpu_ops.TILED_CASES (self-attention: causal) and one cross-attention shape
+GUARDED_QKV = [(1, 1, 8, torch.float32), (64, 64, 128, torch.bfloat16), (65, 65, 8, torch.float32), (65, 65, 24, torch.bfloat16),
+               (70, 33, 64, torch.float32), (70, 33, 64, torch.bfloat16)]
+
+
+@pytest.mark.parametrize("Nq,Nk,hd,dt", GUARDED_QKV, ids=[f"{a}x{b}-hd{c}-{'f32' if d == torch.float32 else 'bf16'}" for a, b, c, d in GUARDED_QKV])
+def test_attention_qkv_operands_in_guard_bands(dev, Nq, Nk, hd, dt):
+    """every operand and every gradient is a column view of a padded buffer between guards (tests/guarded.py): Q | K | V in one
+    [B*N, 3C] buffer with 8 pad columns when Nq == Nk, else Q alone and K | V in one [B*Nk, 2C] buffer; out and dout with ld = C + 8.
+    Inputs (out and lse included, for the backward) between NaN guards with NaN pad columns, outputs between sentinel guards: a key
+    row read past Nk or a pad column read as data shows as NaN, a store outside an extent as a changed sentinel."""
+    lib = _capi.load()
+    causal = Nq == Nk
+    C, scale, code = H * hd, hd ** -0.5, _capi.dtype_code(dt)
+    q, k, v, do = tc.qkv_values(B, Nq, Nk, H, hd, dt, seed=Nq * 1000 + Nk + hd)
+    qr, kr, vr = (t.double().requires_grad_(True) for t in (q, k, v))
+    ref, lse_ref = tc.qkv_ref(qr, kr, vr, B, Nq, Nk, H, hd, scale, causal)
+    ref.backward(do.double())
+    es = q.element_size()
+    if causal:
+        IN = [Guarded.input(torch.cat([q, k, v], 1).to(dev), 3 * C + 8)]
+        GR = [Guarded.output(B * Nq, 3 * C, 3 * C + 8, dt, dev)]
+        place = lambda bufs: ((bufs[0], 0), (bufs[0], C), (bufs[0], 2 * C))
+    else:
+        IN = [Guarded.input(q.to(dev), C + 8), Guarded.input(torch.cat([k, v], 1).to(dev), 2 * C + 8)]
+        GR = [Guarded.output(B * Nq, C, C + 8, dt, dev), Guarded.output(B * Nk, 2 * C, 2 * C + 8, dt, dev)]
+        place = lambda bufs: ((bufs[0], 0), (bufs[1], 0), (bufs[1], C))
+    OUT, LSE = Guarded.output(B * Nq, C, C + 8, dt, dev), Guarded.output_vec(B * H * Nq, torch.float32, dev)
+    d = _capi.AttnQkvDesc()
+    (d.q, d.ld_q), (d.k, d.ld_k), (d.v, d.ld_v) = ((g.ptr() + off * es, g.ld) for g, off in place(IN))
+    d.out, d.ld_out, d.lse = OUT.ptr(), OUT.ld, LSE.ptr()
+    d.B, d.Nq, d.Nk, d.H, d.head_dim, d.dtype, d.causal, d.scale = B, Nq, Nk, H, hd, code, int(causal), scale
+    _capi.check(lib.me_attention_qkv_fwd(ctypes.byref(d), _capi.stream_ptr()), "me_attention_qkv_fwd")
+    torch.cuda.synchronize()
+    what = f"guarded attention_qkv {Nq}x{Nk} hd {hd} {dt}"
+    OUT.check(what + " out")
+    LSE.check(what + " lse")
+    assert OUT.untouched_interior() == 0 and LSE.untouched_interior() == 0
+    assert not bool(torch.isnan(OUT.t).any()) and not bool(torch.isnan(LSE.t).any())
+    check_close(OUT.t.float(), ref.detach(), tol(dt), what + " out")
+    check_close(LSE.vec().reshape(B, H, Nq), lse_ref.detach(), tol(dt), what + " lse")
+    O_IN, LSE_IN, DO = Guarded.input(OUT.t, C + 8), Guarded.input(LSE.vec()), Guarded.input(do.to(dev), C + 8)
+    DELTA = Guarded.output_vec(B * H * Nq, torch.float32, dev)
+    d.out, d.ld_out, d.lse = O_IN.ptr(), O_IN.ld, LSE_IN.ptr()
+    d.dout, d.ld_dout, d.delta = DO.ptr(), DO.ld, DELTA.ptr()
+    (d.dq, d.ld_dq), (d.dk, d.ld_dk), (d.dv, d.ld_dv) = ((g.ptr() + off * es, g.ld) for g, off in place(GR))
+    _capi.check(lib.me_attention_qkv_bwd(ctypes.byref(d), _capi.stream_ptr()), "me_attention_qkv_bwd")
+    torch.cuda.synchronize()
+    DELTA.check(what + " delta")
+    for g in GR:
+        g.check(what + " gradients")
+        assert g.untouched_interior() == 0 and not bool(torch.isnan(g.t).any())
+    grads = [g.t[:, off:off + C] for g, off in place(GR)]
+    check_grads(grads, (qr.grad, kr.grad, vr.grad), tol(dt), what)
 
 
 @pytest.mark.parametrize("dt", DTYPES, ids=["f32", "bf16"])

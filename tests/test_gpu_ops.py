@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from conftest import TOL_BF16_OP, TOL_F32, check_close, rel_err
+from guarded import Guarded
 from metatransformer_amd import _capi, ops
 from oracle import block_oracle as bo
 from oracle import tokenizer_oracle as to
@@ -494,6 +495,63 @@ def test_attention_route_padded_output_stride(dev, direction, N, form):
     assert rel_err(dqkv[:, :3 * C].float(), qr.grad) < 3e-2
     for j, nm in enumerate(("dQ", "dK", "dV")):      # each against its own scale, as in test_attention_bwd
         check_close(dqkv[:, j * C:(j + 1) * C].float(), qr.grad[:, j * C:(j + 1) * C], 3e-2, f"attention backward {nm}, ld_dqkv = 3C + 4")
+
+
+# one shape per forward / backward form: the smallest N ROUTE_CASES has for it (B = H = 2, no dropout)
+GUARD_ROUTE_KEYS = [(64, 64, "bf16"), (65, 64, "bf16"), (225, 64, "bf16"), (257, 64, "bf16"), (257, 32, "bf16"), (513, 64, "bf16"),
+                    (513, 32, "bf16"), (592, 64, "bf16"), (64, 128, "bf16"), (65, 64, "fp32")]
+GUARD_ROUTE_CASES = [c for c in ROUTE_CASES if c[:3] in GUARD_ROUTE_KEYS and c[3] == 0.0 and c[4:6] == (2, 2)]
+assert len(GUARD_ROUTE_CASES) == len(GUARD_ROUTE_KEYS)
+assert {f for c in GUARD_ROUTE_CASES for f in c[6:]} == {TINY, RING16, RESIDENT, STREAM16, MID, CHUNK, STREAM16 | DKDV32, GENERIC}
+
+
+@pytest.mark.parametrize("N,hd,dt,p_drop,B,H,fwd,bwd", GUARD_ROUTE_CASES)
+def test_attention_operands_in_guard_bands(dev, N, hd, dt, p_drop, B, H, fwd, bwd):
+    """the raw packed entry with every row stride padded by 8 elements (ld_qkv = 3C + 8, ld_out = ld_dout = C + 8, ld_dqkv = 3C + 8):
+    qkv, out, dout and lse sit between NaN guards with NaN pad columns, out / lse / delta / dqkv between sentinel guards
+    (tests/guarded.py) -- a key row read past N, a pad column read as data or a store past an extent shows as NaN or as a changed
+    sentinel.  Values against float64 at the bounds of test_attention_fwd / _bwd.  A pad of 8 keeps every alignment the special forms
+    ask for (16-byte rows), so the route is the dense one of ROUTE_CASES; a pad of 4 moves calls to other forms
+    (test_attention_route_padded_output_stride)."""
+    lib = _capi.load()
+    dtype = torch.bfloat16 if dt == "bf16" else torch.float32
+    code = _capi.ME_BF16 if dt == "bf16" else _capi.ME_F32
+    C, scale = H * hd, hd ** -0.5
+    qkv = rnd(B * N, 3 * C, seed=N + hd).to(dtype)
+    do = rnd(B * N, C, seed=N + hd + 1).to(dtype)
+    qr = qkv.double().requires_grad_(True)
+    ref, lse_ref = attn_ref(qr, B, N, H, hd, scale)
+    ref.backward(do.double())
+    QKV, DO = Guarded.input(qkv.to(dev), 3 * C + 8), Guarded.input(do.to(dev), C + 8)
+    OUT, LSE = Guarded.output(B * N, C, C + 8, dtype, dev), Guarded.output_vec(B * H * N, torch.float32, dev)
+
+    def fwd_call():
+        _capi.check(lib.me_attention_fwd(QKV.ptr(), QKV.ld, OUT.ptr(), OUT.ld, LSE.ptr(), B, N, H, hd, scale, code, 0.0, 0,
+                                         _capi.stream_ptr()), "me_attention_fwd")
+    assert _attention_plans(fwd_call) == [(_capi.ME_PROF_ATTN_FWD, fwd)]
+    torch.cuda.synchronize()
+    OUT.check("attention out")
+    LSE.check("attention lse")
+    assert OUT.untouched_interior() == 0 and LSE.untouched_interior() == 0
+    assert not bool(torch.isnan(OUT.t).any()) and not bool(torch.isnan(LSE.t).any())
+    f32 = dtype == torch.float32
+    check_close(OUT.t.float(), ref.detach(), 2e-5 if f32 else 1.5e-2, f"guarded attention forward {N}x{hd} {dt}")
+    assert rel_err(LSE.vec().reshape(B, H, N), lse_ref.detach()) < (1e-5 if f32 else 5e-3)
+    # backward reads out and lse as inputs: between NaN guards, like every other operand
+    O_IN, LSE_IN = Guarded.input(OUT.t, C + 8), Guarded.input(LSE.vec())
+    DELTA, DQKV = Guarded.output_vec(B * H * N, torch.float32, dev), Guarded.output(B * N, 3 * C, 3 * C + 8, dtype, dev)
+
+    def bwd_call():
+        _capi.check(lib.me_attention_bwd(QKV.ptr(), QKV.ld, O_IN.ptr(), O_IN.ld, DO.ptr(), DO.ld, LSE_IN.ptr(), DELTA.ptr(), DQKV.ptr(), DQKV.ld,
+                                         B, N, H, hd, scale, code, 0.0, 0, _capi.stream_ptr()), "me_attention_bwd")
+    assert _attention_plans(bwd_call) == [(_capi.ME_PROF_ATTN_BWD, bwd)]
+    torch.cuda.synchronize()
+    DQKV.check("attention dqkv")
+    DELTA.check("attention delta")
+    assert DQKV.untouched_interior() == 0 and not bool(torch.isnan(DQKV.t).any())
+    for j, nm in enumerate(("dQ", "dK", "dV")):
+        check_close(DQKV.t[:, j * C:(j + 1) * C].float(), qr.grad[:, j * C:(j + 1) * C], 5e-5 if f32 else 3e-2,
+                    f"guarded attention backward {nm} {N}x{hd} {dt}")
 
 
 @pytest.mark.parametrize("B,N,H,hd", [(32, 1568, 16, 64), (64, 592, 12, 64), (128, 512, 16, 64)])
