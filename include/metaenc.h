@@ -690,6 +690,45 @@ int me_graph_tokens_bwd(const me_graph_desc* d, const float* dout, float* d_atom
                         float* d_null, float* d_order, float* dZ, float* d_perturb, int parts, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ hyperspectral tokenizer (SpectralFormer band-neighbourhood embed)
+ * Hyper-spectrum/train.py:80-125 (mirror_hsi, gain_neighborhood_pixel, gain_neighborhood_band) and the tokenizer half of
+ * Hyper-spectrum/metatransformer.py:146-159, on the device and per batch.  All pointers are DEVICE pointers.
+ *   cube [H, W, bands] (ME_F32 or ME_BF16), bands contiguous, row_stride / pix_stride in elements; points int32 [B, 2] = (row, col)
+ *   of the window centre in the unpadded cube; patch p and band_patch bp odd, p / 2 <= min(H, W), bp <= bands; K = p p bp.
+ *   refl(i, n) = -i - 1 below 0, 2 n - 1 - i from n on (np.pad mode "symmetric").  Token (b, j), j in [0, bands), feature
+ *   k = g p p + dy p + dx:   cube[refl(r + dy - p / 2, H), refl(c + dx - p / 2, W), (j + s(g)) mod bands],   nn = bp / 2,
+ *   s(g) = g - nn for p == 1; for p > 1 s(g) = -(g + 1) below nn, 0 at nn, g - nn above (the reference's own group order).
+ *   A point outside the cube is a precondition failure: it is clamped for the read (no fault), the rows are then unspecified.
+ * me_hsi_gather: out [B bands, K] (row stride ld_out elements) = the reference's gathered tensor; an integer-indexed copy
+ *   (bit-exact when out_dtype is the cube's).
+ * me_hsi_embed_fwd: out [B (bands + 1), C] (ME_F32 or ME_BF16, row stride ld_out): row (b, 0) = cls + pos[0], row (b, j + 1) =
+ *   token(b, j) . weight^T + bias + pos[j + 1].  weight [C, K] (row stride ld_w; any K, never padded in memory) fixes the
+ *   arithmetic: ME_BF16 -> v_mfma_f32_16x16x32_bf16 on the cube rounded to bf16, fp32 accumulation; ME_F32 -> an fp32 FMA chain in
+ *   ascending k.  bias [C], cls [C], pos [bands + 1, C] (row stride ld_pos) are fp32; bias may be NULL.  C a multiple of 8;
+ *   out, bias, cls, pos 16-byte aligned, ld_out and ld_pos multiples of 4.  The gathered matrix is never written.
+ * me_hsi_embed_wgrad: from dy [B (bands + 1), C] (ME_F32 or ME_BF16, row stride ld_dy) the fp32 gradients
+ *   dw [C, K] (row stride ld_dw) = sum_{b, j} dy[b, j + 1]^T token(b, j),  dpos [bands + 1, C] (row stride ld_dpos) = sum_b dy[b],
+ *   dbias [C] = sum_{j >= 1} dpos[j],  dcls [C] = dpos[0];  each = beta * old + sum (beta == 0: old is not read); any may be NULL.
+ *   The tokens are regenerated from the cube (fp32 arithmetic for either dy dtype).  Deterministic, no float atomics: the pixels
+ *   are cut into min(B, 32) contiguous runs (run i = pixels [i B / n, (i + 1) B / n)), a run sums its pixels and tokens in
+ *   ascending order, then the runs are summed in ascending order; dpos sums b ascending, dbias j ascending.  Two runs are
+ *   bit-identical.  workspace: me_hsi_embed_wgrad_workspace(d, C) bytes, 16-byte aligned.  The cube gets no gradient. */
+typedef struct me_hsi_desc {
+    const void* cube;
+    int32_t cube_dtype;
+    int64_t row_stride, pix_stride;
+    int32_t H, W, bands;
+    const int32_t* points;
+    int32_t B, patch, band_patch;
+} me_hsi_desc;
+int me_hsi_gather(const me_hsi_desc* d, void* out, int out_dtype, int64_t ld_out, void* stream);
+int me_hsi_embed_fwd(const me_hsi_desc* d, const void* weight, int w_dtype, int64_t ld_w, const float* bias, const float* cls,
+                     const float* pos, int64_t ld_pos, void* out, int out_dtype, int64_t ld_out, int C, void* stream);
+size_t me_hsi_embed_wgrad_workspace(const me_hsi_desc* d, int C);
+int me_hsi_embed_wgrad(const me_hsi_desc* d, const void* dy, int dy_dtype, int64_t ld_dy, int C, float* dw, int64_t ld_dw,
+                       float* dbias, float* dcls, float* dpos, int64_t ld_dpos, float beta, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ position-embedding table resize
  * Replaces TIMMVisionTransformer.resize_pos_embed (Image/detection/mmdet_custom/models/backbones/base/vit.py:459-486,
  * also vit_adapter.py:73-78): the [h*w, cols] grid part of a pos-embed table resampled to [H*W, cols] with

@@ -16,6 +16,7 @@ from .adapter import (ConvFFN, DWConv, Extractor, Injector, InteractionBlock, MS
 from .data2seq import (AcousticPatchEmbed, Data2Seq, DataEmbedding, GraphFeatureTokenizer, PatchEmbed, VideoPatchEmbed,  # noqa: F401
                        sinusoid_table, video_sinusoid_table)
 from .timeseries import AttentionLayer, Decoder, DecoderLayer, Forecaster, FullAttention  # noqa: F401
+from .hyperspectral import HyperSpectralClassifier, HyperSpectralEmbed, neighborhood_tokens  # noqa: F401
 
 __all__ = ["Block", "Attention", "Mlp", "build_encoder", "set_fp32_mode", "encoder_flops_per_sample", "encoder_forward_inference", "Data2Seq", "PatchEmbed",
            "AcousticPatchEmbed", "VideoPatchEmbed", "DataEmbedding", "MetaEncError", "load_library",
@@ -24,4 +25,5 @@ __all__ = ["Block", "Attention", "Mlp", "build_encoder", "set_fp32_mode", "encod
            "FeaturePropogation", "PointViTDecoder", "PointViTPartDecoder", "SegHead", "three_nn", "three_interpolation", "load_encoder_checkpoint", "save_encoder_checkpoint", "pack_encoder",
            "ms_deform_attn", "MSDeformAttn", "Injector", "Extractor", "ConvFFN", "DWConv", "InteractionBlock", "deform_inputs", "get_reference_points",
            "conv3x3_rows", "max_pool3x3s2_rows", "resize_rows_batched", "conv_transpose2x2_rows", "SpatialPriorModule", "ViTAdapter",
-           "GraphFeatureTokenizer", "FullAttention", "AttentionLayer", "DecoderLayer", "Decoder", "Forecaster"]
+           "GraphFeatureTokenizer", "FullAttention", "AttentionLayer", "DecoderLayer", "Decoder", "Forecaster",
+           "HyperSpectralEmbed", "HyperSpectralClassifier", "neighborhood_tokens"]

@@ -81,6 +81,13 @@ class GraphDesc(ctypes.Structure):
                 + [(n, c_int32) for n in ("B", "T", "C", "Fn", "Fe", "Sn", "Se", "max_n", "atom_rows", "edge_rows")])
 
 
+class HsiDesc(ctypes.Structure):
+    """Mirror of ``struct me_hsi_desc`` (include/metaenc.h)."""
+    _fields_ = ([("cube", c_void_p), ("cube_dtype", c_int32), ("row_stride", c_int64), ("pix_stride", c_int64)]
+                + [(n, c_int32) for n in ("H", "W", "bands")] + [("points", c_void_p)]
+                + [(n, c_int32) for n in ("B", "patch", "band_patch")])
+
+
 class AttnQkvDesc(ctypes.Structure):
     """Mirror of ``struct me_attn_qkv_desc`` (include/metaenc.h)."""
     _fields_ = ([("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("ld_q", c_int64), ("ld_k", c_int64), ("ld_v", c_int64),
@@ -241,7 +248,13 @@ SIGNATURES = {
     "me_graph_tokens_bwd_workspace": (c_size_t, [POINTER(GraphDesc)]),
     "me_graph_tokens_bwd": (c_int, [POINTER(GraphDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_size_t, c_void_p]),
-    "me_pool_tokens": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "me_hsi_gather": (c_int, [POINTER(HsiDesc), c_void_p, c_int, c_int64, c_void_p]),
+    "me_hsi_embed_fwd": (c_int, [POINTER(HsiDesc), c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64,
+                                 c_int, c_void_p]),
+    "me_hsi_embed_wgrad_workspace": (c_size_t, [POINTER(HsiDesc), c_int]),
+    "me_hsi_embed_wgrad": (c_int, [POINTER(HsiDesc), c_void_p, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                   c_float, c_void_p, c_size_t, c_void_p]),
+    "me_pool_tokens": (c_int,[c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "me_pool_tokens_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "me_resize_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "me_conv3x3_gather": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),

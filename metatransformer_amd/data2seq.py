@@ -17,8 +17,10 @@ modalities whose tokenizers are on the north-star path (SURVEY.md 8a rows a12-a1
                collator -- stays with the caller)
 
 Parameter names follow the reference modules (``proj.weight`` / ``proj.bias``;
-``value_embedding.tokenConv.weight``; ``atom_encoder.weight`` ...), so their state_dicts interchange.  The text and
-hyper-spectral tokenizers of the reference are CLIP / broken glue and are out of scope.
+``value_embedding.tokenConv.weight``; ``atom_encoder.weight`` ...), so their state_dicts interchange.  ``Data2Seq("hyper", dim,
+bands=, patch=, near_band=)`` builds hyperspectral.HyperSpectralEmbed (the working tokenizer of Hyper-spectrum/train.py and
+metatransformer.py; Data2Seq/Hyper_Spectrum.py itself is broken glue).  The text tokenizer of the reference is CLIP and out of scope
+(SURVEY.md 2.1 row 1).
 """
 from __future__ import annotations
 
@@ -711,8 +713,14 @@ class Data2Seq(nn.Module):
             self.embed = DataEmbedding(c_in=kw.pop("c_in", 1), d_model=dim, **kw)
         elif modality == "graph":       # Data2Seq/Data2Seq.py:32: both identifier widths follow dim, everything else default
             self.embed = GraphFeatureTokenizer(rand_node_id_dim=dim, orf_node_id_dim=dim, **kw)
+        elif modality == "hyper":       # Hyper-spectrum/metatransformer.py:111-118; the reference's defaults there are not runnable
+            from .hyperspectral import HyperSpectralEmbed
+            missing = [k for k in ("bands", "patch", "near_band") if k not in kw]
+            if missing:
+                raise MetaEncError(f"Data2Seq('hyper', dim): keyword(s) {missing} required (bands, patch, near_band)")
+            self.embed = HyperSpectralEmbed(embed_dim=dim, **kw)
         else:
-            raise MetaEncError(f"modality '{modality}' has no HIP tokenizer (in scope: image, audio, video, time-series, graph)")
+            raise MetaEncError(f"modality '{modality}' has no HIP tokenizer (in scope: image, audio, video, time-series, graph, hyper)")
 
     def forward(self, data, *args, **kw):
         return self.embed(data, *args, **kw)
