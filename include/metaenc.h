@@ -232,7 +232,9 @@ size_t me_colsum_workspace(int64_t cols);
 int me_colsum(const void* x, int x_dtype, int64_t ldx, int64_t rows, int64_t cols,
               float* out, int accumulate, void* workspace, void* stream);
 /* out[c] = sum_r x[r,c] * y[r,c] -- gradient of a per-channel scale: d gamma1/gamma2 of the layer-scale Block variant
- * (Image/detection/mmdet_custom/models/backbones/base/vit.py:313-316) = colsum(dy * branch_output).  Same workspace. */
+ * (Image/detection/mmdet_custom/models/backbones/base/vit.py:313-316) = colsum(dy * branch_output).  Same workspace.
+ * cols, ldx, ldy multiples of 4; x and y aligned to four elements of their type (16 bytes fp32, 8 bytes bf16), the workspace to 16
+ * bytes: ME_ERR_ARG otherwise. */
 int me_colsum_mul(const void* x, int x_dtype, int64_t ldx, const void* y, int y_dtype, int64_t ldy,
                   int64_t rows, int64_t cols, float* out, int accumulate, void* workspace, void* stream);
 
@@ -400,7 +402,8 @@ int me_encoder_fwd(const me_block_desc* blocks, int n_blocks, const void* x, voi
                    size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ element-wise helpers */
-/* dst = (dst_dtype) src, n elements */
+/* dst = (dst_dtype) src, n elements.  Any element-aligned src / dst: pointers aligned to four elements of their type take the
+ * 4-wide kernel, others (a slice that starts inside a buffer) an element-wise one, same values. */
 int me_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);
 /* fp32 [rows, cols] (row stride ld_src elements) -> ME_BF16X3 [rows, 3 * cols] bf16 (dense): right_operand = 0 writes [hi | lo | hi]
  * (activations / gradients: the A operand of an NT GEMM, and -- plane by plane -- both operands of a TN weight-gradient GEMM),
@@ -422,7 +425,8 @@ int me_transpose_cast_batched(const me_tc_batch* b, void* stream);
  * dgrad GEMMs' B operand) -- every ME_BF16X3 compute copy of an encoder's weights after an optimizer step in two launches. */
 int me_split3_batched(const me_tc_batch* b, int transposed, int right_operand, void* stream);
 /* y = x + pos (pos broadcast over batch: row m uses pos row m % pos_rows); PointCloud re-injects pos before
- * every block (PointCloud/openpoints/models/backbone/metatransformer.py:161-163). */
+ * every block (PointCloud/openpoints/models/backbone/metatransformer.py:161-163).  cols % 4 == 0; x, pos and y aligned to
+ * four elements of their type (16 bytes fp32, 8 bytes bf16): ME_ERR_ARG otherwise. */
 int me_add_rows(const void* x, int x_dtype, const void* pos, int pos_dtype, void* y, int y_dtype,
                 int64_t rows, int64_t pos_rows, int cols, void* stream);
 
@@ -443,7 +447,8 @@ int me_window_rows(const void* src, void* dst, int dtype, int B, int H, int W, i
  * DropPath (PointCloud/openpoints/models/layers/drop.py:135-152).  The masks are a counter-based hash of (seed, index):
  * calling again with the same seed on the incoming gradient (res = NULL) is the backward.  The RNG stream differs
  * from torch's; distribution and scaling are the reference's.  colscale ([cols] fp32 or NULL) multiplies the masked value
- * per channel (layer-scale gamma applied outside the GEMM when its un-scaled branch output must be kept for d gamma). */
+ * per channel (layer-scale gamma applied outside the GEMM when its un-scaled branch output must be kept for d gamma).
+ * cols % 4 == 0; v, res, out and colscale aligned to four elements of their type (16 bytes fp32, 8 bytes bf16): ME_ERR_ARG otherwise. */
 int me_dropout_add(const void* v, int v_dtype, const void* res, int res_dtype, void* out, int out_dtype,
                    int64_t rows, int cols, int64_t rows_per_sample, float p_drop, float p_path, uint64_t seed,
                    const float* colscale, void* stream);
@@ -553,7 +558,8 @@ int me_adamw_step_segments(float* param, const float* grad, float* exp_avg, floa
  * [B, N, C] tokens -> [B, C] fp32 features: x.mean(1) ahead of fc_norm / x[:, 0] (Video/models/modeling_finetune.py:445-454),
  * and the 'max' / 'avg' global features of the PointCloud ClsHead (openpoints/models/classification/cls_base.py:126-133).
  * ME_POOL_MAX also writes the arg-max token per (b, c) (first index on ties; may be NULL in inference).
- * me_pool_tokens_bwd scatters dy [B, C] back to dx [B, N, C] (every element written). */
+ * me_pool_tokens_bwd scatters dy [B, C] back to dx [B, N, C] (every element written).
+ * C % 4 == 0; x, out, dy and dx aligned to four elements of their type (16 bytes fp32, 8 bytes bf16): ME_ERR_ARG otherwise. */
 enum { ME_POOL_MEAN = 0, ME_POOL_MAX = 1, ME_POOL_FIRST = 2 };
 int me_pool_tokens(const void* x, int x_dtype, float* out, int32_t* argmax, int B, int N, int C, int mode, void* stream);
 int me_pool_tokens_bwd(const float* dy, const int32_t* argmax, void* dx, int dx_dtype, int B, int N, int C, int mode,
@@ -733,7 +739,8 @@ int me_hsi_embed_wgrad(const me_hsi_desc* d, const void* dy, int dy_dtype, int64
  * Replaces TIMMVisionTransformer.resize_pos_embed (Image/detection/mmdet_custom/models/backbones/base/vit.py:459-486,
  * also vit_adapter.py:73-78): the [h*w, cols] grid part of a pos-embed table resampled to [H*W, cols] with
  * F.interpolate(mode, align_corners=False) semantics, on the token-major layout (rows = grid positions).  The caller keeps
- * the cls row(s) as the reference does (cat).  fp32 arithmetic; modes: */
+ * the cls row(s) as the reference does (cat).  fp32 arithmetic; cols % 4 == 0, src and dst aligned to four elements of their type
+ * (16 bytes fp32, 8 bytes bf16): ME_ERR_ARG otherwise.  Modes: */
 enum { ME_RESIZE_BILINEAR = 0, ME_RESIZE_BICUBIC = 1 };
 int me_resize_rows(const void* src, int src_dtype, void* dst, int dst_dtype, int h, int w, int H, int W, int cols,
                    int mode, void* stream);

@@ -904,6 +904,9 @@ __global__ __launch_bounds__(EW_THREADS) void group_rel_kernel(const float* __re
     }
 }
 
+// the 4-wide kernels read and write four elements per access: 16 bytes of fp32, 8 of bf16
+inline bool aligned4(const void* p, int dt) { return (uintptr_t)p % (4 * me_dtype_size(dt)) == 0; }
+
 }  // namespace
 
 extern "C" int me_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream_) {
@@ -911,7 +914,7 @@ extern "C" int me_cast(const void* src, int src_dtype, void* dst, int dst_dtype,
     ME_CHECK_ARG(src && dst && n >= 0, "me_cast: bad args");
     ME_CHECK_ARG(me_storage_dtype_ok(src_dtype) && me_storage_dtype_ok(dst_dtype), "me_cast: bad dtype");
     if (n == 0) return ME_OK;
-    if (src_dtype == ME_F16 || dst_dtype == ME_F16) {
+    if (src_dtype == ME_F16 || dst_dtype == ME_F16 || !aligned4(src, src_dtype) || !aligned4(dst, dst_dtype)) {      // (a slice that starts off a four-element boundary: element by element)
         hipLaunchKernelGGL(cast_any_kernel, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, stream, src, src_dtype, dst, dst_dtype, n);
         ME_CHECK_LAUNCH("me_cast");
         return ME_OK;
@@ -983,6 +986,8 @@ extern "C" int me_add_rows(const void* x, int x_dtype, const void* pos, int pos_
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     ME_CHECK_ARG(x && pos && y && rows > 0 && pos_rows > 0 && cols > 0 && cols % 4 == 0, "me_add_rows: bad args");
     ME_CHECK_ARG(me_dtype_ok(x_dtype) && me_dtype_ok(pos_dtype) && me_dtype_ok(y_dtype), "me_add_rows: bad dtype");
+    ME_CHECK_ARG(aligned4(x, x_dtype) && aligned4(pos, pos_dtype) && aligned4(y, y_dtype),
+                 "me_add_rows: x, pos and y must be aligned to four elements of their type");
     hipLaunchKernelGGL(add_rows_kernel, dim3(ew_blocks(rows * (cols / 4))), dim3(EW_THREADS), 0, stream, x, x_dtype, pos,
                        pos_dtype, y, y_dtype, rows, pos_rows, cols);
     ME_CHECK_LAUNCH("me_add_rows");
@@ -995,6 +1000,7 @@ extern "C" int me_resize_rows(const void* src, int src_dtype, void* dst, int dst
     ME_CHECK_ARG(src && dst && h > 0 && w > 0 && H > 0 && W > 0 && cols > 0 && cols % 4 == 0, "me_resize_rows: bad args");
     ME_CHECK_ARG(me_dtype_ok(src_dtype) && me_dtype_ok(dst_dtype), "me_resize_rows: bad dtype");
     ME_CHECK_ARG(mode == ME_RESIZE_BILINEAR || mode == ME_RESIZE_BICUBIC, "me_resize_rows: mode %d (bilinear / bicubic only)", mode);
+    ME_CHECK_ARG(aligned4(src, src_dtype) && aligned4(dst, dst_dtype), "me_resize_rows: src and dst must be aligned to four elements of their type");
     hipLaunchKernelGGL(resize_rows_kernel, dim3(ew_blocks((int64_t)H * W * (cols / 4))), dim3(EW_THREADS), 0, stream, src,
                        src_dtype, dst, dst_dtype, h, w, H, W, cols, mode);
     ME_CHECK_LAUNCH("me_resize_rows");
@@ -1006,6 +1012,7 @@ extern "C" int me_pool_tokens(const void* x, int x_dtype, float* out, int32_t* a
     ME_CHECK_ARG(x && out && B > 0 && N > 0 && C > 0 && C % 4 == 0, "me_pool_tokens: bad args");
     ME_CHECK_ARG(me_dtype_ok(x_dtype), "me_pool_tokens: bad dtype");
     ME_CHECK_ARG(mode == ME_POOL_MEAN || mode == ME_POOL_MAX || mode == ME_POOL_FIRST, "me_pool_tokens: bad mode %d", mode);
+    ME_CHECK_ARG(aligned4(x, x_dtype) && aligned4(out, ME_F32), "me_pool_tokens: x and out must be aligned to four elements of their type");
     hipLaunchKernelGGL(pool_tokens_kernel, dim3(ew_blocks((int64_t)B * (C / 4))), dim3(EW_THREADS), 0, stream, x, x_dtype, out,
                        argmax, B, N, C, mode);
     ME_CHECK_LAUNCH("me_pool_tokens");
@@ -1019,6 +1026,7 @@ extern "C" int me_pool_tokens_bwd(const float* dy, const int32_t* argmax, void* 
     ME_CHECK_ARG(me_dtype_ok(dx_dtype), "me_pool_tokens_bwd: bad dtype");
     ME_CHECK_ARG(mode == ME_POOL_MEAN || mode == ME_POOL_FIRST || (mode == ME_POOL_MAX && argmax),
                  "me_pool_tokens_bwd: bad mode %d (max needs the forward's argmax)", mode);
+    ME_CHECK_ARG(aligned4(dy, ME_F32) && aligned4(dx, dx_dtype), "me_pool_tokens_bwd: dy and dx must be aligned to four elements of their type");
     hipLaunchKernelGGL(pool_tokens_bwd_kernel, dim3(ew_blocks((int64_t)B * N * (C / 4))), dim3(EW_THREADS), 0, stream, dy, argmax, dx,
                        dx_dtype, B, N, C, mode);
     ME_CHECK_LAUNCH("me_pool_tokens_bwd");
@@ -1117,6 +1125,8 @@ extern "C" int me_colsum_mul(const void* x, int x_dtype, int64_t ldx, const void
     ME_CHECK_ARG(x && y && out && workspace && rows > 0 && cols > 0, "me_colsum_mul: bad args");
     ME_CHECK_ARG(me_dtype_ok(x_dtype) && me_dtype_ok(y_dtype), "me_colsum_mul: bad dtype");
     ME_CHECK_ARG(cols % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "me_colsum_mul: cols and row strides must be multiples of 4");
+    ME_CHECK_ARG(aligned4(x, x_dtype) && aligned4(y, y_dtype) && aligned4(workspace, ME_F32),
+                 "me_colsum_mul: x and y must be aligned to four elements of their type, the workspace to 16 bytes");
     float* partial = reinterpret_cast<float*>(workspace);
     dim3 grid((unsigned)((cols + 255) / 256), CS_SPLITS);
     hipLaunchKernelGGL(colsum_mul_partial_kernel, grid, dim3(256), 0, stream, x, x_dtype, ldx, y, y_dtype, ldy, rows, cols, partial);
@@ -1312,6 +1322,8 @@ extern "C" int me_dropout_add(const void* v, int v_dtype, const void* res, int r
     ME_CHECK_ARG(v && out && rows > 0 && cols > 0 && cols % 4 == 0 && rows_per_sample > 0, "me_dropout_add: bad args");
     ME_CHECK_ARG(me_dtype_ok(v_dtype) && me_dtype_ok(out_dtype) && (!res || me_dtype_ok(res_dtype)), "me_dropout_add: bad dtype");
     ME_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f && p_path >= 0.f && p_path < 1.f, "me_dropout_add: probabilities must be in [0, 1)");
+    ME_CHECK_ARG(aligned4(v, v_dtype) && (!res || aligned4(res, res_dtype)) && aligned4(out, out_dtype) && aligned4(colscale, ME_F32),
+                 "me_dropout_add: v, res, out and colscale must be aligned to four elements of their type");
     hipLaunchKernelGGL(dropout_add_kernel, dim3(ew_blocks(rows * (cols / 4))), dim3(EW_THREADS), 0, stream, v, v_dtype, res,
                        res_dtype, out, out_dtype, rows, cols, rows_per_sample, p_drop, p_path, seed, colscale);
     ME_CHECK_LAUNCH("me_dropout_add");

@@ -364,7 +364,8 @@ extern "C" int me_patch_embed(const me_patch_embed_desc* d, void* stream_) {
     if (!pe_fusable(d, s)) {
         // two passes: gather into the workspace (converted to the compute dtype on the way), then the ordinary GEMM
         const size_t cols_bytes = ((size_t)s.M * (size_t)s.K * (size_t)me_dtype_size(d->w_dtype) + 255) & ~(size_t)255;
-        ME_CHECK_ARG(d->workspace && (size_t)d->workspace_bytes >= cols_bytes,
+        // (the whole queried size, not only the gathered columns: a caller one byte short is told so before anything is written)
+        ME_CHECK_ARG(d->workspace && (size_t)d->workspace_bytes >= me_patch_embed_workspace_bytes(d),
                      "me_patch_embed: this geometry / dtype needs a workspace of me_patch_embed_workspace_bytes()");
         rc = me_patchify(d->x, d->x_dtype, d->workspace, d->w_dtype, d->B, d->Cin, d->T, d->H, d->W, d->kt, d->kh, d->kw, d->st, d->sh, d->sw, stream_);
         if (rc) return rc;
