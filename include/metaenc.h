@@ -735,6 +735,52 @@ int me_hsi_embed_wgrad(const me_hsi_desc* d, const void* dy, int dy_dtype, int64
                        float* dbias, float* dcls, float* dpos, int64_t ld_dpos, float beta, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ video masked pre-training (VideoMAE)
+ * The work around the Blocks of Video/models/modeling_pretrain.py:124-139, 340-360 and the target and loss of
+ * Video/engine_for_pretraining.py:66-105.  All pointers are DEVICE pointers; index lists are int32.  video [B, Cin, T, H, W]
+ * (ME_F32 or ME_BF16, contiguous); the tubelet grid is [T / kt, H / kh, W / kw] and token n of a sample is (t', h', w') in row-major
+ * order (Video/models/modeling_finetune.py:277-297).  Index VALUES in range (tokens: [0, (T / kt)(H / kh)(W / kw)), table rows:
+ * [0, rows)) are a precondition, as for me_graph_tokens_fwd: a value out of range is clamped for the read (no fault) and the row's
+ * content is then unspecified.  B, Nsel, Nvis or Ndec = 0: ME_OK, the empty part is not touched.
+ * me_tubelet_gather: out [B Nsel, K = Cin kt kh kw] (row stride ld_out; columns from K on are left as they are), row (b, j) = the
+ *   tubelet of token idx[b, j]: column ((c kt + dt) kh + dh) kw + dw = video[b, c, t' kt + dt, h' kh + dh, w' kw + dw], the order of
+ *   the flattened Conv3d weight.  A copy: bit-exact when out_dtype is the video's; ME_F32 to ME_BF16 rounds once, as me_cast does.
+ * me_take_rows: out [B Nsel, C] (row stride ld_out), row (b, j) = table[idx[b, j]] (+ add, fp32 [C], when not NULL); table
+ *   [rows, C] (row stride ld_table), ME_F32 or ME_BF16; the sum is formed in fp32.
+ * me_mae_assemble_fwd: out [B, Nvis + Ndec, Cd] (row stride ld_out): row (b, j) = xv[b, j] + pos[vis_idx[b, j]] for j < Nvis,
+ *   mask_token + pos[dec_idx[b, j - Nvis]] behind.  xv [B Nvis, Cd] (row stride ld_xv), pos fp32 [rows, Cd] (row stride ld_pos),
+ *   mask_token fp32 [Cd]; sums in fp32, one rounding to out_dtype.
+ * me_mae_assemble_bwd: from dx_full [B, Nvis + Ndec, Cd] (row stride ld_dx): dxv [B Nvis, Cd] (row stride ld_dxv) = its first Nvis
+ *   rows per sample, dmask_token fp32 [Cd] = the sum of the other rows; either may be NULL.  Deterministic, no float atomics: the
+ *   B Ndec mask rows m = b Ndec + j are cut into n = min(B Ndec, 256) runs (run i = rows [i M / n, (i + 1) M / n)), a run sums its
+ *   rows in ascending order, then the runs are summed in ascending order; two runs of the call are bit-identical.  Ndec = 0:
+ *   dmask_token = 0.  workspace: me_mae_assemble_bwd_workspace(B, Ndec, Cd) bytes, 4-byte aligned.
+ * me_mae_loss: for every decoded token (b, j) = token dec_idx[b, j], in one pass over those patches only: the pixels u = x std[c] +
+ *   mean[c] (mean, std fp32 [Cin]); per channel over the n = kt kh kw pixels of the patch the mean m and M2 = sum (u - m)^2 (two
+ *   passes, fp32), label = (u - m) / (sqrt(M2 / (n - 1)) + 1e-6) -- or label = u when normalize_target is 0; label column
+ *   ((dt kh + dh) kw + dw) Cin + c.  tok_loss[b, j] (fp32 [B Ndec]) = mean over the kt kh kw Cin columns of (pred - label)^2, pred
+ *   [B Ndec, kt kh kw Cin] ME_F32 or ME_BF16 (row stride ld_pred).  scalars (fp32 [2], never NULL): scalars[1] = sum of w (fp32
+ *   [B Ndec]), scalars[0] = sum w tok_loss / sum w, or 0 when sum w = 0 (written when tok_loss is not NULL).  labels (fp32, row
+ *   stride ld_labels) and dpred (pred's dtype, row stride ld_dpred) = g 2 w (pred - label) / (kt kh kw Cin sum w), g = *grad_scale
+ *   or 1 when that is NULL, exact zeros when sum w = 0, are written in the same pass when not NULL.  Both sums over (b, j) are
+ *   taken by one workgroup in a fixed order (thread t: elements t, t + 256, ... ascending; then the threads): no atomics, no host
+ *   synchronisation, two runs bit-identical.  Cin <= 16, kt kh kw Cin <= 16320 (the patch in 64 KiB of LDS; ME_ERR_UNSUPPORTED beyond); normalize_target needs
+ *   kt kh kw >= 2. */
+int me_tubelet_gather(const void* video, int video_dtype, const int32_t* idx, void* out, int out_dtype, int64_t ld_out, int B, int Cin,
+                      int T, int H, int W, int kt, int kh, int kw, int Nsel, void* stream);
+int me_take_rows(const void* table, int table_dtype, int64_t ld_table, int rows, const int32_t* idx, const float* add, void* out,
+                 int out_dtype, int64_t ld_out, int B, int Nsel, int C, void* stream);
+int me_mae_assemble_fwd(const void* xv, int xv_dtype, int64_t ld_xv, const float* pos, int64_t ld_pos, int rows, const int32_t* vis_idx,
+                        const int32_t* dec_idx, const float* mask_token, void* out, int out_dtype, int64_t ld_out, int B, int Nvis,
+                        int Ndec, int Cd, void* stream);
+size_t me_mae_assemble_bwd_workspace(int B, int Ndec, int Cd);
+int me_mae_assemble_bwd(const void* dx_full, int dx_dtype, int64_t ld_dx, void* dxv, int dxv_dtype, int64_t ld_dxv, float* dmask_token,
+                        int B, int Nvis, int Ndec, int Cd, void* workspace, size_t workspace_bytes, void* stream);
+int me_mae_loss(const void* video, int video_dtype, int B, int Cin, int T, int H, int W, int kt, int kh, int kw, const float* mean,
+                const float* stdv, const int32_t* dec_idx, const float* w, int Ndec, const void* pred, int pred_dtype, int64_t ld_pred,
+                int normalize_target, const float* grad_scale, float* tok_loss, float* scalars, float* labels, int64_t ld_labels,
+                void* dpred, int64_t ld_dpred, void* stream);
+
 /* ------------------------------------------------------------------ position-embedding table resize
  * Replaces TIMMVisionTransformer.resize_pos_embed (Image/detection/mmdet_custom/models/backbones/base/vit.py:459-486,
  * also vit_adapter.py:73-78): the [h*w, cols] grid part of a pos-embed table resampled to [H*W, cols] with

@@ -17,6 +17,8 @@ from .data2seq import (AcousticPatchEmbed, Data2Seq, DataEmbedding, GraphFeature
                        sinusoid_table, video_sinusoid_table)
 from .timeseries import AttentionLayer, Decoder, DecoderLayer, Forecaster, FullAttention  # noqa: F401
 from .hyperspectral import HyperSpectralClassifier, HyperSpectralEmbed, neighborhood_tokens  # noqa: F401
+from .video_mae import (PretrainVisionTransformer, PretrainVisionTransformerDecoder, PretrainVisionTransformerEncoder,  # noqa: F401
+                        mae_reconstruction_loss)
 
 __all__ = ["Block", "Attention", "Mlp", "build_encoder", "set_fp32_mode", "encoder_flops_per_sample", "encoder_forward_inference", "Data2Seq", "PatchEmbed",
            "AcousticPatchEmbed", "VideoPatchEmbed", "DataEmbedding", "MetaEncError", "load_library",
@@ -26,4 +28,5 @@ __all__ = ["Block", "Attention", "Mlp", "build_encoder", "set_fp32_mode", "encod
            "ms_deform_attn", "MSDeformAttn", "Injector", "Extractor", "ConvFFN", "DWConv", "InteractionBlock", "deform_inputs", "get_reference_points",
            "conv3x3_rows", "max_pool3x3s2_rows", "resize_rows_batched", "conv_transpose2x2_rows", "SpatialPriorModule", "ViTAdapter",
            "GraphFeatureTokenizer", "FullAttention", "AttentionLayer", "DecoderLayer", "Decoder", "Forecaster",
-           "HyperSpectralEmbed", "HyperSpectralClassifier", "neighborhood_tokens"]
+           "HyperSpectralEmbed", "HyperSpectralClassifier", "neighborhood_tokens",
+           "PretrainVisionTransformerEncoder", "PretrainVisionTransformerDecoder", "PretrainVisionTransformer", "mae_reconstruction_loss"]

@@ -254,6 +254,15 @@ SIGNATURES = {
     "me_hsi_embed_wgrad_workspace": (c_size_t, [POINTER(HsiDesc), c_int]),
     "me_hsi_embed_wgrad": (c_int, [POINTER(HsiDesc), c_void_p, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_float, c_void_p, c_size_t, c_void_p]),
+    "me_tubelet_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64] + [c_int] * 9 + [c_void_p]),
+    "me_take_rows": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p]),
+    "me_mae_assemble_fwd": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                                    c_int, c_int, c_int, c_int, c_void_p]),
+    "me_mae_assemble_bwd_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "me_mae_assemble_bwd": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                    c_void_p]),
+    "me_mae_loss": (c_int, [c_void_p, c_int] + [c_int] * 8 + [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "me_pool_tokens": (c_int,[c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "me_pool_tokens_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "me_resize_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -103,10 +103,13 @@ class Comm:
             pass
 
 
-def no_decay_rule(name: str, p: torch.nn.Parameter) -> bool:
-    """The reference fine-tuning recipes exempt 1-D parameters and biases from weight decay
-    (Video/optim_factory.py:67-73: `len(param.shape) == 1 or name.endswith(".bias")`)."""
-    return p.dim() == 1 or name.endswith(".bias")
+def no_decay_rule(name: str, p: torch.nn.Parameter, skip=()) -> bool:
+    """The reference recipes exempt 1-D parameters, biases, `.scale` parameters and the names of the model's `no_weight_decay()` set
+    from weight decay (Video/optim_factory.py:67-68: `len(param.shape) == 1 or name.endswith(".bias") or name.endswith(".scale") or
+    name in skip_list`).  `skip`: that set, e.g. `functools.partial(no_decay_rule, skip=model.no_weight_decay())`.  The `.scale` clause
+    holds for the default call too: a user model's parameter named `*.scale` is exempt whatever its shape, as in the reference (no
+    parameter of this package is named so)."""
+    return p.dim() == 1 or name.endswith(".bias") or name.endswith(".scale") or name in skip
 
 
 def layer_id_for_vit(name: str, num_layers: int) -> int:
