@@ -110,7 +110,14 @@ int me_layernorm_bwd(const void* dy, int dy_dtype, const void* x, int x_dtype,
  * with res_row(m) = res_row_mod ? m % res_row_mod : m   (pos-embed broadcast over the batch) and
  * out_row(m) = out_group_rows ? (m / out_group_rows) * out_group_stride + m % out_group_rows + out_row_offset : m
  * (patch tokens written behind a cls token).  Requirements: K % (16/sizeof(A elt)) == 0, N % 4 == 0,
- * 16-byte aligned rows. */
+ * 16-byte aligned rows.
+ * Non-finite pre-activations (pinned by tests/test_gpu_gemm_epilogue_values.py, the same in every kernel family): the plain, bias, row-operand
+ * and factor forms propagate NaN and +-inf like the fp32 arithmetic they are, and so do the erf forms of GELU and gelu' (fp32 C, the
+ * ME_GEMM_SAVE_GELU_GRAD pair; an ME_GG8 byte of a NaN is 0).  The polynomial forms used when the result is stored as bf16 do NOT return
+ * NaN for a NaN: their clamp min(|x|, 4) and ramp max(x, 0) drop a quiet NaN, so act = GELU gives 4 P(4) = -9.7e-5 and gelu'(aux) gives
+ * 1/2 +- 4 Q(4) = 1.0001 or -9.7e-5 by the NaN's sign bit.  Inside a Block the residual stream still carries the NaN of a token to that
+ * token's output row (and to its sample's gradients); a caller that needs NaN out of a lone bf16 GELU GEMM must look at the saved
+ * pre-activation. */
 enum { ME_GEMM_NT = 0, ME_GEMM_TN = 1 };
 enum { ME_ACT_NONE = 0, ME_ACT_GELU = 1 };
 /* me_gemm_desc.flags.  The GELU of Mlp.forward (mlp.py:31) needs gelu'(h) in backward; a forward that saves gelu'(h)
