@@ -87,6 +87,15 @@ static inline bool me_dtype_ok(int dt) { return dt == ME_F32 || dt == ME_BF16; }
 static inline bool me_storage_dtype_ok(int dt) { return me_dtype_ok(dt) || dt == ME_F16; }          // me_cast only
 static inline bool me_out_dtype_ok(int dt) { return me_dtype_ok(dt) || dt == ME_BF16X3; }           // me_layernorm_fwd y (and me_gemm C, which also takes ME_BF16X2)
 static inline bool me_is_planes(int dt) { return dt == ME_BF16X3 || dt == ME_BF16X2; }             // fp32 values stored as bf16 hi / lo planes
+// the 4-wide kernels read and write four elements per access: 16 bytes of fp32, 8 of bf16
+static inline bool aligned4(const void* p, int dt) { return (uintptr_t)p % (4 * me_dtype_size(dt)) == 0; }
+// the element-wise kernels run grid-stride loops in workgroups of EW_THREADS: the grid for work_items of them
+constexpr int EW_THREADS = 256;
+static inline unsigned grid_blocks(int64_t work_items) {
+    int64_t b = (work_items + EW_THREADS - 1) / EW_THREADS;
+    const int64_t cap = 256 * 8;   // 256 CUs x 8 blocks, grid-stride the rest
+    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
 
 // ---- LayerNorm backward with the dgamma / dbeta fold deferred (layernorm.hip; me_block_bwd folds both LayerNorms of a block in one launch)
 constexpr int LN_FOLD_SETS = 4;

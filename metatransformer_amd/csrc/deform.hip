@@ -340,7 +340,7 @@ extern "C" int me_ms_deform_attn_bwd(const float* value, const int32_t* spatial_
         char* ws = static_cast<char*>(workspace);
         auto I = [&](size_t at) { return reinterpret_cast<int32_t*>(ws + at); };
         const int64_t samples = pairs * L * P;
-        hipLaunchKernelGGL(msda_corner_rows_kernel, dim3(pt_blocks(samples)), dim3(MSDA_THREADS), 0, stream, loc, I(w.idx), lv, L, M, P,
+        hipLaunchKernelGGL(msda_corner_rows_kernel, dim3(grid_blocks(samples)), dim3(MSDA_THREADS), 0, stream, loc, I(w.idx), lv, L, M, P,
                            samples);
         const int rc = invert_lists(I(w.idx), N, (int64_t)Lq * M * L * P * 4, S * M, I(w.off), I(w.cur), I(w.ent), I(w.srt), stream,
                                     "me_ms_deform_attn_bwd (inverted lists)");

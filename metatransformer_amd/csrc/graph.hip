@@ -326,7 +326,7 @@ extern "C" int me_graph_tokens_bwd(const me_graph_desc* d, const float* dout, fl
     if (parts & ME_GRAPH_BWD_INDEX) {
         const int64_t work = (int64_t)d->Sn + d->Se + p.SnF + p.SeF;
         if (work > 0)
-            hipLaunchKernelGGL(gt_index_kernel, dim3(pt_blocks(work)), dim3(GT_THREADS), 0, stream, *d, p.NC, I(p.nrow), I(p.erow), I(p.idx));
+            hipLaunchKernelGGL(gt_index_kernel, dim3(grid_blocks(work)), dim3(GT_THREADS), 0, stream, *d, p.NC, I(p.nrow), I(p.erow), I(p.idx));
         const int rc = invert_lists(I(p.idx), 1, p.L, (int)p.N, I(p.off), I(p.cur), I(p.ent), I(p.srt), stream, "me_graph_tokens_bwd (inverted lists)");
         if (rc != ME_OK) return rc;
         hipLaunchKernelGGL(gt_nseg_kernel, dim3((p.Rt + GT_THREADS - 1) / GT_THREADS), dim3(GT_THREADS), 0, stream, I(p.off), base, p.NC, p.Rt,

@@ -9,11 +9,6 @@
 namespace {
 
 constexpr int PT_THREADS = 256;
-inline unsigned pt_blocks(int64_t work_items) {
-    int64_t b = (work_items + PT_THREADS - 1) / PT_THREADS;
-    const int64_t cap = 256 * 8;   // 256 CUs x 8 blocks, grid-stride the rest
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
 
 // cnt[b * n + v] = occurrences of v in idx[b, :] (integer atomics: exact)
 __global__ __launch_bounds__(PT_THREADS) void inv_count_kernel(const int32_t* __restrict__ idx, int64_t L, int64_t total, int n,
@@ -82,10 +77,10 @@ int invert_lists(const int32_t* idx, int B, int64_t L, int n, int32_t* off, int3
                  hipStream_t stream, const char* what = "me_group_features_bwd (inverted lists)") {
     const int64_t N = (int64_t)B * n, total = (int64_t)B * L;
     if (hipMemsetAsync(cur, 0, (size_t)N * 4, stream) != hipSuccess) { me_set_error("%s: memset failed", what); return ME_ERR_HIP; }
-    hipLaunchKernelGGL(inv_count_kernel, dim3(pt_blocks(total)), dim3(PT_THREADS), 0, stream, idx, L, total, n, cur);
+    hipLaunchKernelGGL(inv_count_kernel, dim3(grid_blocks(total)), dim3(PT_THREADS), 0, stream, idx, L, total, n, cur);
     hipLaunchKernelGGL(inv_scan_kernel, dim3(1), dim3(1024), 0, stream, cur, off, N);
-    hipLaunchKernelGGL(inv_fill_kernel, dim3(pt_blocks(total)), dim3(PT_THREADS), 0, stream, idx, L, total, n, off, cur, ent);
-    hipLaunchKernelGGL(inv_sort_kernel, dim3(pt_blocks(N * 64)), dim3(PT_THREADS), 0, stream, off, ent, srt, N);
+    hipLaunchKernelGGL(inv_fill_kernel, dim3(grid_blocks(total)), dim3(PT_THREADS), 0, stream, idx, L, total, n, off, cur, ent);
+    hipLaunchKernelGGL(inv_sort_kernel, dim3(grid_blocks(N * 64)), dim3(PT_THREADS), 0, stream, off, ent, srt, N);
     ME_CHECK_LAUNCH(what);
     return ME_OK;
 }

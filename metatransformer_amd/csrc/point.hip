@@ -1,5 +1,7 @@
 // point.hip -- the point-cloud grouping of P3Embed (openpoints group_embed.py:176-286) at room scale, and the feature
 // propagation of the point segmentation decoders (PointNet++ three_nn + three_interpolate, layers/upsampling.py):
+//   * me_fps / me_knn / me_group_relative: the tokenizer front end of PointPatchEmbed -- farthest point sampling, the k nearest
+//     neighbours with the distances resident in LDS (n <= 10 240) and the relative-xyz neighbourhood rows;
 //   * me_knn_stream: k nearest support points for clouds of any size (me_knn's LDS-resident form holds n <= 10 240);
 //   * me_group_features / me_group_features_bwd: the grouped GEMM operand rows [dp | f-part | 0 ...] and their
 //     deterministic backward onto the token-major features;
@@ -9,6 +11,164 @@
 #include "inv_lists.h"
 
 namespace {
+
+// ---- point-cloud tokenizer front end: farthest point sampling, k nearest neighbours, neighbourhood gather.
+// Replaces, for PointPatchEmbed (PointCloud/openpoints/models/layers/group_embed.py:138-172):
+//   furthest_point_sample  -> furthest_point_sampling_kernel (openpoints/cpp/pointnet2_batch/src/sampling_gpu.cu:101-210)
+//   KNNGroup / KNN         -> torch.cdist + topk(largest=False) (openpoints/models/layers/group.py:12-28, 297-320)
+//   grouping_operation + "relative_xyz"  (group.py:310-313)
+// Index arithmetic is integer; the sampled / neighbour INDICES are what the parity tests compare bit-exactly.
+//
+// FPS.  What the reference kernel computes per round -- the next sample is the point that maximises min(d(p, last sample),
+// temp[p]) -- is an arg-max with a SPECIFIC order among equal values, fixed by its thread-strided scan and its shared-memory
+// tree (thread t = k mod T walks k = t, t + T, ... keeping the first strict maximum; partners (t, t + s), s = T/2 .. 1, fold
+// with `v2 > v1 ? i2 : i1`): the winner is the candidate with the largest value, then the smallest BIT-REVERSED thread id,
+// then the smallest k.  That is a total order, so here it is one 64-bit key per candidate
+//     key = value bits (a non-negative float: monotone as an integer) << 32 | ~(bitrev(t) << ibits | k / T)
+// and the arg-max is an unsigned maximum, taken in any association:
+//   * one workgroup per cloud, T = the reference's thread count (opt_n_threads: largest power of two <= n, <= 1024), thread t
+//     owns the same points k = t + i T as there -- but holds them, and their running minimum distances, in REGISTERS for all
+//     m rounds (x, y, z, temp: 4 registers per point, up to 24 points per lane = 24 576 points; the reference re-reads
+//     12 n bytes and read-modify-writes 4 n bytes of global memory every round);
+//   * a lane's own scan is the reference's (first strict maximum in slot order); across the lanes of a wave the keys meet in
+//     four DPP steps (quad_perm, row_half_mirror, row_mirror) + four v_readlane + scalar maxima, across the <= 16 waves in
+//     one LDS word pair per wave and ONE barrier per round (slots alternate by round parity), against log2(T) + 1 barriers;
+//   * larger clouds (n > 24 576) run the same rounds with the points and temp left in memory (FPS_MEM).
+// The distance is evaluated exactly as hipcc evaluates the reference's expression (x2-x1)*(x2-x1) + (y2-y1)*(y2-y1) +
+// (z2-z1)*(z2-z1) on gfx950 -- fma(dy, dy, dx*dx) + dz*dz, read off the ISA of the reference kernel built for this GPU -- so that the indices
+// agree with the reference kernel built for this GPU bit for bit, not only on tie-rich lattices (tests/test_gpu_pointcloud_ref.py).
+__device__ __forceinline__ float fps_dist(float dx, float dy, float dz) {
+#pragma clang fp contract(off)
+    const float xx = dx * dx, zz = dz * dz;
+    const float xy = __builtin_fmaf(dy, dy, xx);
+    return xy + zz;
+}
+template <int CTRL> __device__ __forceinline__ unsigned long long fps_dpp_max(unsigned long long v) {
+    const unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+    const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp((int)lo, (int)lo, CTRL, 0xf, 0xf, false);
+    const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp((int)hi, (int)hi, CTRL, 0xf, 0xf, false);
+    const unsigned long long o = ((unsigned long long)ohi << 32) | olo;
+    return o > v ? o : v;
+}
+// maximum over the wave, wave-uniform result
+__device__ __forceinline__ unsigned long long fps_wave_max(unsigned long long v) {
+    v = fps_dpp_max<0xB1>(v);       // quad_perm [1,0,3,2]
+    v = fps_dpp_max<0x4E>(v);       // quad_perm [2,3,0,1]
+    v = fps_dpp_max<0x141>(v);      // row_half_mirror
+    v = fps_dpp_max<0x140>(v);      // row_mirror: every lane of a row of 16 holds the row's maximum
+    unsigned long long r = 0;
+#pragma unroll
+    for (int row = 0; row < 4; ++row) {
+        const unsigned long long x = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), row * 16) << 32) |
+                                     (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, row * 16);
+        r = x > r ? x : r;
+    }
+    return r;
+}
+// R > 0: register-resident, R points per lane.  R == 0 (FPS_MEM): points and temp stay in memory.
+template <int R>
+__global__ __launch_bounds__(1024) void fps_kernel(const float* __restrict__ pts, float* __restrict__ temp, int32_t* __restrict__ idxs,
+                                                   int n, int m, int logT, int ibits) {
+    __shared__ unsigned long long wave_key[2][16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int T = 1 << logT, nwaves = (int)(blockDim.x >> 6);
+    pts += (int64_t)b * n * 3;
+    temp += (int64_t)b * n;
+    idxs += (int64_t)b * m;
+    // ~(bitrev(t) << ibits): the thread part of the tie order (threads past T, in a wave that T does not fill, own nothing)
+    const bool lane_on = tid < T;
+    const unsigned rev = logT ? (__builtin_bitreverse32((unsigned)tid) >> (32 - logT)) : 0u;
+    const unsigned tie_hi = ~(rev << ibits);
+    constexpr int RR = R > 0 ? R : 1;
+    float px[RR], py[RR], pz[RR], tmin[RR];
+    if (R > 0) {
+#pragma unroll
+        for (int i = 0; i < RR; ++i) {
+            // slots past the end of the cloud repeat point 0: their distance is 0 from the first round on, and a lane's scan keeps
+            // the FIRST maximum, so they never displace a real point
+            const int k = tid + i * T;
+            const int kk = (lane_on && k < n) ? k : 0;
+            px[i] = pts[kk * 3 + 0]; py[i] = pts[kk * 3 + 1]; pz[i] = pts[kk * 3 + 2];
+            tmin[i] = 1e10f;          // the reference's caller fills temp with 1e10 (subsample.py: fill_(1e10))
+        }
+    } else {
+        for (int k = tid; k < n; k += T) if (lane_on) temp[k] = 1e10f;
+    }
+    int old = 0;
+    if (tid == 0) idxs[0] = 0;
+    for (int j = 1; j < m; ++j) {
+        const float x1 = pts[old * 3 + 0], y1 = pts[old * 3 + 1], z1 = pts[old * 3 + 2];      // (wave-uniform address)
+        float best = -1.f;
+        unsigned bi = 0;
+        if (R > 0) {
+#pragma unroll
+            for (int i = 0; i < RR; ++i) {
+                const float d2 = fminf(fps_dist(px[i] - x1, py[i] - y1, pz[i] - z1), tmin[i]);
+                tmin[i] = d2;
+                bi = d2 > best ? (unsigned)i : bi;
+                best = d2 > best ? d2 : best;
+            }
+        } else if (lane_on) {
+            unsigned i = 0;
+            for (int k = tid; k < n; k += T, ++i) {
+                const float d2 = fminf(fps_dist(pts[k * 3 + 0] - x1, pts[k * 3 + 1] - y1, pts[k * 3 + 2] - z1), temp[k]);
+                temp[k] = d2;
+                bi = d2 > best ? i : bi;
+                best = d2 > best ? d2 : best;
+            }
+        }
+        unsigned long long key = lane_on ? (((unsigned long long)__float_as_uint(best) << 32) | (tie_hi - bi)) : 0ull;
+        key = fps_wave_max(key);
+        if (nwaves > 1) {
+            if (lane == 0) wave_key[j & 1][wave] = key;
+            __syncthreads();
+            key = fps_wave_max(lane < nwaves ? wave_key[j & 1][lane] : 0ull);
+        }
+        const unsigned tie = ~(unsigned)key;                              // bitrev(t) << ibits | slot
+        const unsigned t = logT ? (__builtin_bitreverse32(tie >> ibits) >> (32 - logT)) : 0u;
+        old = (int)(((tie & ((1u << ibits) - 1u)) << logT) | t);
+        old = __builtin_amdgcn_readfirstlane(old);
+        if (tid == 0) idxs[j] = old;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- resident KNN
+// k nearest support points of every query, ascending by squared distance, ties by lower index: one wave per query.
+// Each lane scans its strided share keeping a sorted private top-k list is too register-hungry for k = 32; instead the
+// wave selects the k winners one at a time (k rounds of a wave-wide arg-min over the distances held in LDS).
+__global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ support, const float* __restrict__ query,
+                                                  int32_t* __restrict__ idx, int n, int m, int k) {
+    extern __shared__ __attribute__((aligned(16))) char knn_smem[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float* dist = reinterpret_cast<float*>(knn_smem) + (int64_t)wave * n;      // this wave's [n] distances
+    const int b = blockIdx.y;
+    const int q = blockIdx.x * 4 + wave;
+    if (q >= m) return;                                                         // (whole wave)
+    support += (int64_t)b * n * 3;
+    const float qx = query[((int64_t)b * m + q) * 3 + 0], qy = query[((int64_t)b * m + q) * 3 + 1], qz = query[((int64_t)b * m + q) * 3 + 2];
+    for (int i = lane; i < n; i += 64) {
+        const float dx = support[i * 3 + 0] - qx, dy = support[i * 3 + 1] - qy, dz = support[i * 3 + 2] - qz;
+        dist[i] = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+    }
+    __builtin_amdgcn_wave_barrier();
+    int32_t* out = idx + ((int64_t)b * m + q) * k;
+    for (int r = 0; r < k; ++r) {
+        float best = 3.0e38f;
+        int besti = 0x7fffffff;
+        for (int i = lane; i < n; i += 64) {
+            const float d = dist[i];
+            if (d < best) { best = d; besti = i; }                              // first (lowest index) of equal values per lane
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ob = __shfl_xor(best, o, 64);
+            const int oi = __shfl_xor(besti, o, 64);
+            if (ob < best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+        }
+        if (lane == 0) { out[r] = besti; dist[besti] = 3.0e38f; }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------- streaming KNN
 // A workgroup of 4 waves takes 4 x KNN_QPW queries of one cloud and streams the support points through LDS in tiles of
@@ -86,6 +246,24 @@ __global__ __launch_bounds__(256) void knn_stream_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------- grouped rows
+// rows[(b, s, j), 0..2] = pts[b, idx[b, s, j]] - centers[b, s] (relative_xyz), columns 3 .. cols-1 zero: the first MLP layer's
+// GEMM operand (reduction dimension padded to the GEMM's 16-byte granule).
+__global__ __launch_bounds__(PT_THREADS) void group_rel_kernel(const float* __restrict__ pts, const float* __restrict__ centers,
+                                                               const int32_t* __restrict__ idx, float* __restrict__ rows, int B, int n,
+                                                               int m, int k, int cols) {
+    const int64_t total = (int64_t)B * m * k;
+    for (int64_t i = (int64_t)blockIdx.x * PT_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * PT_THREADS) {
+        const int64_t bs = i / k;
+        const int b = (int)(bs / m);
+        const int id = idx[i];
+        const float* p = pts + ((int64_t)b * n + id) * 3;
+        const float* c = centers + bs * 3;
+        float* r = rows + i * cols;
+        r[0] = p[0] - c[0]; r[1] = p[1] - c[1]; r[2] = p[2] - c[2];
+        for (int j = 3; j < cols; ++j) r[j] = 0.f;
+    }
+}
+
 // rows[(b, s, j), :] = [ p[nbr] - p[ctr] (3) | mode part | 0 ... ] with nbr = nbr_idx[b, s, j], ctr = ctr_idx[b, s]:
 //   ME_GROUP_DP       nothing            ME_GROUP_DP_FJ     f[nbr] (C)
 //   ME_GROUP_DP_DF    f[nbr] - f[ctr]    ME_GROUP_DP_FJ_DF  f[nbr] (C) | f[nbr] - f[ctr] (C)
@@ -374,6 +552,28 @@ InterpWs interp_ws(int B, int n, int m) {
 
 }  // namespace
 
+extern "C" int me_fps(const float* points, int32_t* idx, float* temp, int B, int n, int m, void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    ME_CHECK_ARG(points && idx && temp && B > 0 && n > 0 && m > 0 && m <= n, "me_fps: bad args (B=%d n=%d m=%d)", B, n, m);
+    int logT = 0;
+    while ((2 << logT) <= n && logT < 10) ++logT;          // opt_n_threads(n) of the reference launcher: T = 1 << logT
+    const int T = 1 << logT, threads = T < 64 ? 64 : T;
+    const int per_lane = (n + T - 1) / T;                   // points per reference thread
+    int ibits = 1;
+    while ((1 << ibits) < per_lane) ++ibits;
+#define ME_FPS_CASE(RR) hipLaunchKernelGGL(fps_kernel<RR>, dim3((unsigned)B), dim3((unsigned)threads), 0, stream, points, temp, idx, n, m, logT, ibits)
+    if (per_lane <= 1) ME_FPS_CASE(1);
+    else if (per_lane <= 2) ME_FPS_CASE(2);
+    else if (per_lane <= 4) ME_FPS_CASE(4);
+    else if (per_lane <= 8) ME_FPS_CASE(8);
+    else if (per_lane <= 16) ME_FPS_CASE(16);
+    else if (per_lane <= 24) ME_FPS_CASE(24);
+    else ME_FPS_CASE(0);
+#undef ME_FPS_CASE
+    ME_CHECK_LAUNCH("me_fps");
+    return ME_OK;
+}
+
 extern "C" int me_knn_stream(const float* support, const float* query, int32_t* idx, int B, int n, int m, int k, void* stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     ME_CHECK_ARG(support && query && idx && B > 0 && n > 0 && m > 0 && k > 0 && k <= n, "me_knn_stream: bad args");
@@ -389,6 +589,28 @@ extern "C" int me_knn_stream(const float* support, const float* query, int32_t* 
     return ME_OK;
 }
 
+extern "C" int me_knn(const float* support, const float* query, int32_t* idx, int B, int n, int m, int k, void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    ME_CHECK_ARG(support && query && idx && B > 0 && n > 0 && m > 0 && k > 0 && k <= n, "me_knn: bad args");
+    if (n > 10240) return me_knn_stream(support, query, idx, B, n, m, k, stream_);      // beyond the LDS-resident form
+    const size_t lds = (size_t)4 * n * sizeof(float);
+    static OncePerDevice once;
+    if (once.need()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(knn_kernel, dim3((unsigned)((m + 3) / 4), (unsigned)B), dim3(256), lds, stream, support, query, idx, n, m, k);
+    ME_CHECK_LAUNCH("me_knn");
+    return ME_OK;
+}
+
+extern "C" int me_group_relative(const float* points, const float* centers, const int32_t* idx, float* rows, int B, int n, int m,
+                                 int k, int cols, void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    ME_CHECK_ARG(points && centers && idx && rows && B > 0 && n > 0 && m > 0 && k > 0 && cols >= 3, "me_group_relative: bad args");
+    hipLaunchKernelGGL(group_rel_kernel, dim3(grid_blocks((int64_t)B * m * k)), dim3(PT_THREADS), 0, stream, points, centers, idx,
+                       rows, B, n, m, k, cols);
+    ME_CHECK_LAUNCH("me_group_relative");
+    return ME_OK;
+}
+
 extern "C" int me_group_features(const float* points, const void* feats, int feats_dtype, const int32_t* ctr_idx,
                                  const int32_t* nbr_idx, float* rows, int B, int n, int m, int k, int C, int cols, int mode,
                                  void* stream_) {
@@ -400,7 +622,7 @@ extern "C" int me_group_features(const float* points, const void* feats, int fea
     ME_CHECK_ARG(cols % 8 == 0 && cols >= group_width(mode, C), "me_group_features: cols %d (a multiple of 8 >= %d)", cols,
                  group_width(mode, C));
     const int64_t total = (int64_t)B * m * k * cols;
-    hipLaunchKernelGGL(group_features_kernel, dim3(pt_blocks(total)), dim3(PT_THREADS), 0, stream, points, feats, feats_dtype,
+    hipLaunchKernelGGL(group_features_kernel, dim3(grid_blocks(total)), dim3(PT_THREADS), 0, stream, points, feats, feats_dtype,
                        ctr_idx, nbr_idx, rows, n, m, k, C, cols, mode, total);
     ME_CHECK_LAUNCH("me_group_features");
     return ME_OK;
@@ -444,10 +666,10 @@ extern "C" int me_group_features_bwd(const float* drows, const int32_t* ctr_idx,
         rc = invert_lists(ctr_idx, B, m, n, I(w.coff), I(w.ccur), I(w.cent), I(w.csrt), stream);
         if (rc != ME_OK) return rc;
         const int64_t ctot = (int64_t)B * m * C;
-        hipLaunchKernelGGL(group_centre_sum_kernel, dim3(pt_blocks(ctot)), dim3(PT_THREADS), 0, stream, drows, dcs, k, C, cols,
+        hipLaunchKernelGGL(group_centre_sum_kernel, dim3(grid_blocks(ctot)), dim3(PT_THREADS), 0, stream, drows, dcs, k, C, cols,
                            df_col, ctot);
     }
-    hipLaunchKernelGGL(group_features_bwd_kernel, dim3(pt_blocks(total)), dim3(PT_THREADS), 0, stream, drows, dcs, I(w.noff),
+    hipLaunchKernelGGL(group_features_bwd_kernel, dim3(grid_blocks(total)), dim3(PT_THREADS), 0, stream, drows, dcs, I(w.noff),
                        I(w.nsrt), I(w.coff), I(w.csrt), df, df_dtype, C, cols, fj_col, df_col, total);
     ME_CHECK_LAUNCH("me_group_features_bwd");
     return ME_OK;

@@ -301,7 +301,7 @@ GATHER_CASES = [
 
 
 def _gather_kernel(geom, W, x_ptr, cols_ptr):
-    """which kernel me_patchify's launcher takes, from its stated preconditions (csrc/elementwise.hip)"""
+    """which kernel me_patchify's launcher takes, from its stated preconditions (csrc/patchify.hip)"""
     kw, sw = geom[2], geom[5]
     if kw % 4 == 0 and cols_ptr % 16 == 0:
         return "quad aligned" if (W % 4 == 0 and sw % 4 == 0 and x_ptr % 16 == 0) else "quad unaligned"
