@@ -456,6 +456,355 @@ template <int CPR> __device__ __forceinline__ int r16_swz(int r) {
 }
 __device__ __forceinline__ f32x4 mma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
+// -----------------------------------------------------------------------------------------------------
+// The per-wave pieces below (r16_* / st16_* and R16Frags: a wave owns 16 rows) are shared by the six kernels on 16-row waves:
+// attn_fwd_ring16 / attn_bwd_ring16 here and attn_fwd_stream16 / attn_bwd_dq_stream16 / attn_bwd_dkdv_stream16 /
+// attn_bwd_dkdv_stream32 (N > SM_MAXN) further down.  Those differ in what sits in LDS and when, in their loaders and in how a
+// workgroup comes by its items.
+constexpr int ST_KC = 128;                            // streaming kernels: keys (rows) per chunk
+constexpr int ST_RING = 3;                            // ... and LDS ring slots of one {array 0, array 1} chunk each
+
+// a lane's byte offsets into an unpadded, swizzled array for the two fragment reads
+template <int HD> struct R16Frags {
+    typedef RCfg<HD> R;
+    static constexpr int NKS = HD / 32;               // 32-wide d steps of a row-operand product (QK^T)
+    static constexpr int NDT = HD / 16;               // 16-wide d tiles of a transposed-operand product (O^T)
+    int koff[NKS];                                    // row-operand read: row 16 t + l15, chunk 4 ks + g
+    int troff[NDT];                                   // transposing read: rows 32 kk + 16 r + 4 g + (l15 >> 2), 8 bytes at d = 16 dt + 4 (l15 & 3)
+    __device__ __forceinline__ R16Frags(int l15, int g) {
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) koff[ks] = l15 * R::RB + 16 * ((4 * ks + g) ^ r16_swz<R::CPR>(l15));
+        const int rr = 4 * g + (l15 >> 2);
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt)
+            troff[dt] = rr * R::RB + 16 * ((2 * dt + ((l15 & 3) >> 1)) ^ r16_swz<R::CPR>(rr)) + 8 * (l15 & 1);
+    }
+    __device__ __forceinline__ void rowread(const char* arr, int t, bf16x8 (&dst)[NKS]) const {
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) dst[ks] = *reinterpret_cast<const bf16x8*>(arr + 16 * t * R::RB + koff[ks]);
+    }
+    // The same address summed in two ways, which hipcc compiles differently.  As an integer (default) it re-adds per read and keeps no
+    // base live: the backward steps, which sit at the 128-register edge (the pointer form there: 26 spilled registers in
+    // attn_bwd_ring16_kernel<64, 7>).  As a pointer (BASE) it keeps arr + troff[dt] in a register across the steps and folds the rest
+    // into the instruction's offset: the forward's PV pass, which has the room (the integer form there: two more VALU adds per half-step)
+    template <bool BASE = false> __device__ __forceinline__ bf16x8 trread(const char* arr, int kk, int dt) const {
+        union { bf16x4 q4[2]; bf16x8 v; } a;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int off = (32 * kk + 16 * r) * R::RB;
+            const uint32_t p = BASE ? (uint32_t)(uintptr_t)(arr + off + troff[dt]) : (uint32_t)(uintptr_t)arr + off + troff[dt];
+            a.q4[r] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)p);
+        }
+        return a.v;
+    }
+};
+
+// a wave's own rows, fetched raw from global ahead of their use (the chunk address clamped to 0 past hd): chunks of d past hd are zeros
+template <int HD>
+__device__ __forceinline__ void r16_take(const u32x4 (&raw)[HD / 32], int g, int hd, bf16x8 (&dst)[HD / 32]) {
+#pragma unroll
+    for (int ks = 0; ks < HD / 32; ++ks) {
+        const u32x4 v = 32 * ks + 8 * g < hd ? raw[ks] : zero4();
+        dst[ks] = *reinterpret_cast<const bf16x8*>(&v);
+    }
+}
+
+// Forward, pass 1: S^T of NT 16-key tiles, two at a time; the operand chunks of the next pair are in flight while this pair's
+// MFMAs run (software-pipelined by hand: left alone hipcc emits read -> wait -> MFMA one fragment at a time).  `stamp`: the item
+// whose trace stamp 1 is taken behind the first pair (< 0: none)
+template <int HD, int NT>
+__device__ __forceinline__ void r16_st_pass(const R16Frags<HD>& fr, const char* Kb, const bf16x8 (&qf)[HD / 32], f32x4 (&s)[NT], int stamp) {
+    constexpr int NKS = HD / 32;
+    const f32x4 zero4f = {0.f, 0.f, 0.f, 0.f};
+    bf16x8 ka[2][NKS], kb[2][NKS];
+    auto kread = [&](int t, bf16x8 (&dst)[2][NKS]) {
+        fr.rowread(Kb, t, dst[0]);
+        fr.rowread(Kb, t + 1, dst[1]);
+    };
+    auto kmma = [&](int t, const bf16x8 (&src)[2][NKS]) {
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) s[t + tt] = mma16(src[tt][0], qf[0], zero4f);
+#pragma unroll
+        for (int ks = 1; ks < NKS; ++ks)
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) s[t + tt] = mma16(src[tt][ks], qf[ks], s[t + tt]);
+    };
+    (void)stamp;
+    kread(0, ka);
+#pragma unroll
+    for (int t = 0; t < NT; t += 4) {
+        if (t + 2 < NT) kread(t + 2, kb);
+        __builtin_amdgcn_sched_barrier(0);
+        kmma(t, ka);
+        __builtin_amdgcn_sched_barrier(0);
+        if (t == 0 && stamp >= 0) { TRACE_STAMP(stamp, 1); }
+        if (t + 2 < NT) {
+            if (t + 4 < NT) kread(t + 4, ka);
+            __builtin_amdgcn_sched_barrier(0);
+            kmma(t + 2, kb);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+// Forward, pass 2: O^T += V^T P^T over NKK 32-key steps (`fresh`: O^T starts at zero), the d tiles in two halves: the V^T operand of
+// the next half is in flight while this half's MFMAs run (half-steps keep the operand buffers at 2 x NDT / 2 fragments: the ring
+// kernel has to fit 128 registers)
+template <int HD, int NKK>
+__device__ __forceinline__ void r16_pv_pass(const R16Frags<HD>& fr, const char* Vb, const f32x4 (&s)[2 * NKK], f32x4 (&o)[HD / 16], bool fresh) {
+    constexpr int NH = HD / 32;
+    const f32x4 zero4f = {0.f, 0.f, 0.f, 0.f};
+    bf16x8 va[NH], vb[NH];
+    auto vread = [&](int kk, int half, bf16x8 (&dst)[NH]) {
+#pragma unroll
+        for (int i = 0; i < NH; ++i) dst[i] = fr.template trread<true>(Vb, kk, NH * half + i);
+    };
+    vread(0, 0, va);
+#pragma unroll
+    for (int kk = 0; kk < NKK; ++kk) {
+        vread(kk, 1, vb);
+        bf16x8 pb;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { pb[e] = (bf16_t)s[2 * kk][e]; pb[4 + e] = (bf16_t)s[2 * kk + 1][e]; }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NH; ++i) o[i] = mma16(va[i], pb, fresh && kk == 0 ? zero4f : o[i]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (kk + 1 < NKK) vread(kk + 1, 0, va);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NH; ++i) o[NH + i] = mma16(vb[i], pb, fresh && kk == 0 ? zero4f : o[NH + i]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// a softmax probability from its log2-domain argument: v_exp_f32 with the clamp output modifier (hipcc folds the med3 into it)
+__device__ __forceinline__ float r16_p(float arg) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(arg), 0.f, 1.f); }
+
+// four probabilities and their dS / scale (the 32-key dK / dV kernel):  pe = exp2(s * sl - l2),  ds = pe * (dp - d).  The same on
+// PAIRS (measured and removed) -- v_pk_fma_f32 for the argument, v_pk_mul_f32 + v_pk_fma_f32 for dS, 3.5 instead of 5 VALU instructions per score (and, tried with
+// it, the same form in every other backward kernel and v_pk_fma_f32 / v_pk_add_f32 in the forward kernels' exp2 + row sum) -- measured SLOWER everywhere (same box,
+// profiles/r06_attn_bwd_stream32.txt: N = 197 forward 68.7 -> 74.7 us, backward 212.9 -> 222.7; N = 1568 forward 477 -> 504, backward
+// 1 218 -> 1 247): the packed fp32 operations do not issue at the rate of two scalar ones here, and assembling the pairs costs moves.
+__device__ __forceinline__ void r16_pds4(const f32x4& s, const f32x4& dp, float sl, const f32x4& l2, const f32x4& d, f32x4& pe, f32x4& ds) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        pe[e] = r16_p(s[e] * sl - l2[e]);
+        ds[e] = pe[e] * (dp[e] - d[e]);
+    }
+}
+
+// Backward, a wave of 16 queries against 32 keys (tiles 2 kk, 2 kk + 1 of Kb / Vb): S^T and dP^T, dS^T = P^T o (dP^T - delta),
+// dQ^T (+)= K^T dS^T (`first`: dQ^T starts at zero).  lse2 = lse * log2(e), +inf on padded queries -> P = 0.  Valid rows keep their
+// exact lse; a padded key (zero K row, s = 0) evaluates to exp2(-lse2), which overflows for a row whose scores are all very negative
+// -- and it only ever multiplies zeros.  Every P is therefore taken through r16_p(): exp2 with the result clamped to [0, 1] (the output
+// modifier of v_exp_f32, no extra instruction), exact for real entries (P <= 1 by construction of lse) and finite for padded ones
+template <int HD>
+__device__ __forceinline__ void r16_dq_step(const R16Frags<HD>& fr, const char* Kb, const char* Vb, int kk, const bf16x8 (&qf)[HD / 32],
+                                            const bf16x8 (&dof)[HD / 32], float sl, float lse2, float del, f32x4 (&dq)[HD / 16], bool first) {
+    constexpr int NKS = HD / 32, NDT = HD / 16;
+    const f32x4 zero4f = {0.f, 0.f, 0.f, 0.f};
+    bf16x8 ka[2][NKS], va[2][NKS];
+    fr.rowread(Kb, 2 * kk, ka[0]); fr.rowread(Kb, 2 * kk + 1, ka[1]);
+    fr.rowread(Vb, 2 * kk, va[0]); fr.rowread(Vb, 2 * kk + 1, va[1]);
+    f32x4 s[2], dp[2];
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) { s[tt] = mma16(ka[tt][0], qf[0], zero4f); dp[tt] = mma16(va[tt][0], dof[0], zero4f); }
+#pragma unroll
+    for (int ks = 1; ks < NKS; ++ks)
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) { s[tt] = mma16(ka[tt][ks], qf[ks], s[tt]); dp[tt] = mma16(va[tt][ks], dof[ks], dp[tt]); }
+    bf16x8 kt[NDT];
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) kt[dt] = fr.trread(Kb, kk, dt);
+    // keys >= N: their K rows are zeros, so whatever dS holds there adds nothing to dQ -- no mask
+    bf16x8 dsb;
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float pe = r16_p(s[tt][e] * sl - lse2);
+            dsb[4 * tt + e] = (bf16_t)(pe * (dp[tt][e] - del));      // dS^T / scale (scale applied to dQ once)
+        }
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) dq[dt] = mma16(kt[dt], dsb, first ? zero4f : dq[dt]);
+}
+// Backward, a wave of 16 keys (rows kf / vf) against 32 queries (tiles 2 qq, 2 qq + 1 of Qb / Db, their statistics at lsb / deb):
+// S and dP, dV^T (+)= dO^T P, dK^T (+)= Q^T dS.  L2E: lsb holds lse as stored and is multiplied by log2(e) here; otherwise it holds
+// the product already
+template <int HD, bool L2E>
+__device__ __forceinline__ void r16_dkdv_step(const R16Frags<HD>& fr, const char* Qb, const char* Db, const float* lsb, const float* deb,
+                                              int qq, int g, const bf16x8 (&kf)[HD / 32], const bf16x8 (&vf)[HD / 32], float sl,
+                                              f32x4 (&dk)[HD / 16], f32x4 (&dv)[HD / 16], bool first) {
+    constexpr int NKS = HD / 32, NDT = HD / 16;
+    const f32x4 zero4f = {0.f, 0.f, 0.f, 0.f};
+    f32x4 s[2], dp[2];
+    {
+        bf16x8 qa[2][NKS];
+        fr.rowread(Qb, 2 * qq, qa[0]); fr.rowread(Qb, 2 * qq + 1, qa[1]);
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) s[tt] = mma16(qa[tt][0], kf[0], zero4f);
+#pragma unroll
+        for (int ks = 1; ks < NKS; ++ks)
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) s[tt] = mma16(qa[tt][ks], kf[ks], s[tt]);
+    }
+    {
+        bf16x8 da[2][NKS];
+        fr.rowread(Db, 2 * qq, da[0]); fr.rowread(Db, 2 * qq + 1, da[1]);
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) dp[tt] = mma16(da[tt][0], vf[0], zero4f);
+#pragma unroll
+        for (int ks = 1; ks < NKS; ++ks)
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) dp[tt] = mma16(da[tt][ks], vf[ks], dp[tt]);
+    }
+    bf16x8 pb, dsb;
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) {
+        const f32x4 L = *reinterpret_cast<const f32x4*>(lsb + 16 * (2 * qq + tt) + 4 * g);
+        const f32x4 D = *reinterpret_cast<const f32x4*>(deb + 16 * (2 * qq + tt) + 4 * g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float pe = r16_p(s[tt][e] * sl - (L2E ? L[e] * LOG2E : L[e]));
+            pb[4 * tt + e] = (bf16_t)pe;
+            dsb[4 * tt + e] = (bf16_t)(pe * (dp[tt][e] - D[e]));      // dS / scale (scale applied to dK once)
+        }
+    }
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) dv[dt] = mma16(fr.trread(Db, qq, dt), pb, first ? zero4f : dv[dt]);
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) dk[dt] = mma16(fr.trread(Qb, qq, dt), dsb, first ? zero4f : dk[dt]);
+}
+
+// 16 accumulator rows (lane (row l & 15, g = l >> 4) holds d = 16 dt + 4 g + j), times `mul` -> bf16 rows of `grow0`, transposed through the
+// wave's LDS scratch into whole 128-byte row stores.  The stores are BUFFER stores behind a descriptor that ends with the last
+// valid row (rows past it and chunks past hd are dropped by the bounds check, never branched over): the number of memory
+// operations is fixed, so a later wait for loads issued BEFORE these stores can be a counted vmcnt instead of vmcnt(0).
+template <int HD>
+__device__ __forceinline__ void r16_store_rows(char* scr, const f32x4 (&acc)[HD / 16], float mul, bf16_t* __restrict__ grow0,
+                                               int64_t ldg, int rows_valid, int hd, int lane) {
+    typedef Cfg<bf16_t, HD> C;
+    const int l15 = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int dt = 0; dt < HD / 16; ++dt) {
+        bf16x4 v4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v4[e] = (bf16_t)(acc[dt][e] * mul);
+        *reinterpret_cast<bf16x4*>(scr + l15 * C::RROW + (16 * dt + 4 * g) * 2) = v4;
+    }
+    __builtin_amdgcn_wave_barrier();
+    constexpr int RPI = 64 / C::CPR;              // rows per store instruction
+    const int chunk = lane % C::CPR, r0 = lane / C::CPR;
+    const int nrec = rows_valid > 0 ? (int)(((int64_t)(rows_valid - 1) * ldg + hd) * 2) : 0;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(grow0, 0, nrec, 0x00020000);
+#pragma unroll
+    for (int k = 0; k < 16 / RPI; ++k) {
+        const int r = r0 + RPI * k;
+        const u32x4 v = *reinterpret_cast<const u32x4*>(scr + r * C::RROW + chunk * 16);
+        const int off = chunk * 8 < hd ? (int)(r * ldg * 2) + chunk * 16 : 0x7f000000;
+        __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, ME_POL_ATTN_ST);
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+// A loader lane's source addressing for the LDS-DMA of an array with row stride ld: lane l fills LDS bytes [16 l, 16 l + 16) of an
+// instruction's 1 KiB = slot `pos` of row `rg` of the row group, with the chunk that belongs there (the swizzle is applied on the
+// SOURCE side).  voff: the lane's byte offset in piece 0, gstep: bytes from one piece to the next, rec: the descriptor's size --
+// rows >= N and chunks >= hd (voff out of any range) are outside it and arrive as zeros
+template <int HD>
+__device__ __forceinline__ void r16_dma_lane(int lane, int64_t ld, int N, int hd, int& voff, int& gstep, int& rec) {
+    typedef RCfg<HD> R;
+    const int rg = (lane * 16) / R::RB, pos = ((lane * 16) % R::RB) / 16;
+    const int csrc = pos ^ r16_swz<R::CPR>(rg);
+    voff = (csrc * 8 < hd) ? rg * (int)ld * 2 + csrc * 16 : 0x7f000000;
+    gstep = R::RPI * (int)ld * 2;
+    rec = (int)(((int64_t)(N - 1) * ld + hd) * 2);
+}
+
+// The items of a workgroup of the streaming kernels: vid, vid + G, ... with an XCD-major virtual id -- the workgroups of one XCD
+// (blockIdx & 7) take consecutive items = neighbouring row blocks of a head, so a head's streamed side comes out of HBM once
+__device__ __forceinline__ int st16_vid(int G) {
+    return (G & 7) == 0 ? ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
+}
+__device__ __forceinline__ int st16_my_items(int vid, int items, int G) { return vid < items ? (items - vid + G - 1) / G : 0; }
+
+// Loader waves of the streaming kernels: array 0 / 1 of a chunk from (a0, ld0) / (a1, ld1); FL: 128 floats of f0 / f1 per chunk.
+// They keep a three-slot LDS ring of chunks two chunks ahead of the compute waves; chunk j of the workgroup's stream = chunk j % NCH
+// of its (j / NCH)-th item.  NW waves per workgroup, the last NL of them load (the others past the compute waves keep the barrier
+// count): NL = 4 (two waves per array -- an LDS-DMA piece costs its issuer 60-180 clocks, and 16 of them per 128-row chunk is about
+// what the compute waves of a short row block need for the chunk), 2 (one per array) or 1 (one wave fills both arrays -- the 8-wave
+// kernel with seven compute waves).
+template <int HD, bool FL, int NW>
+__device__ __forceinline__ void st16_loader(char* smem, char* fring, int wave, int lane, int NL, int total, int NCH, int vid, int G,
+                                            int nblk, int H, int N, int hd, const bf16_t* a0, int64_t ld0, int64_t hoff0,
+                                            const bf16_t* a1, int64_t ld1, int64_t hoff1, const float* f0, const float* f1) {
+    typedef RCfg<HD> R;
+    constexpr int arr_bytes = ST_KC * R::RB;
+    constexpr int slot_bytes = 2 * arr_bytes;
+    constexpr int NPC = ST_KC / R::RPI;
+    static_assert(2 * NPC + 4 <= 63, "vmcnt range");
+    if (wave < NW - NL) {                             // spare waves: the barrier count only
+        for (int k = 0; k < total; ++k) __builtin_amdgcn_s_barrier();
+        return;
+    }
+    const int lw = wave - (NW - NL);
+    const int which0 = NL == 1 ? 0 : (lw & 1), nwhich = NL == 1 ? 2 : 1;
+    const int part = lw >> 1, nparts = NL == 4 ? 2 : 1;
+    auto fill = [&](int j) {
+        if (j >= total) return;
+        const int it = vid + (j / NCH) * G, c = j % NCH;
+        const int bh = it / nblk;
+        for (int w = 0; w < nwhich; ++w) {
+            const int which = which0 + w;
+            const bf16_t* const arr = which ? a1 : a0;
+            const int64_t ldw = which ? ld1 : ld0, hoff = which ? hoff1 : hoff0;
+            int dma_voff, dma_gstep, rec_bytes;
+            r16_dma_lane<HD>(lane, ldw, N, hd, dma_voff, dma_gstep, rec_bytes);
+            const bf16_t* base = arr + (int64_t)(bh / H) * N * ldw + (bh % H) * hd + hoff;
+            const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base), 0, rec_bytes, 0x00020000);
+            char* dst = smem + (j % ST_RING) * slot_bytes + which * arr_bytes;
+            const int voff = dma_voff + c * NPC * dma_gstep;
+            if (nparts == 1) {
+#pragma unroll
+                for (int i = 0; i < NPC; ++i)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, (lds_dma_t*)(dst + i * 1024), 16, voff + i * dma_gstep, 0, 0, 0);
+            } else {
+#pragma unroll
+                for (int i = 0; i < NPC / 2; ++i) {
+                    const int p = 2 * i + part;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, (lds_dma_t*)(dst + p * 1024), 16, voff + p * dma_gstep, 0, 0, 0);
+                }
+            }
+            if (FL) {
+                // 128 floats of this array's statistics: two dword pieces of 64 (one each when two loaders share the array)
+                const float* const farr = which ? f1 : f0;
+                const __amdgpu_buffer_rsrc_t rf =
+                    __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(farr + (int64_t)bh * N), 0, N * 4, 0x00020000);
+                char* fdst = fring + ((j % ST_RING) * 2 + which) * (ST_KC * 4);
+                const int fvoff = (c * ST_KC + lane) * 4;
+                if (nparts == 1) {
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rf, (lds_dma_t*)fdst, 4, fvoff, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rf, (lds_dma_t*)(fdst + 256), 4, fvoff + 256, 0, 0, 0);
+                } else {
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rf, (lds_dma_t*)(fdst + 256 * part), 4, fvoff + 256 * part, 0, 0, 0);
+                }
+            }
+        }
+    };
+    fill(0);
+    fill(1);
+    for (int k = 0; k < total; ++k) {
+        // chunk k has landed once at most chunk k + 1's pieces (of this loader) are outstanding (in-order retirement)
+        if (k + 1 >= total) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else if (NL == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NPC + (FL ? 4 : 0)) : "memory");
+        else if (NL == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPC + (FL ? 2 : 0)) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPC / 2 + (FL ? 1 : 0)) : "memory");
+        __builtin_amdgcn_s_barrier();                 // chunk k ready; everybody is done with chunk k - 1
+        fill(k + 2);                                  // ... whose slot takes chunk k + 2
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 template <int HD, int NS>
 __global__ __launch_bounds__(R16_THREADS) void attn_fwd_ring16_kernel(const bf16_t* __restrict__ qkv, int64_t ld,
                                                                       bf16_t* __restrict__ out, int64_t ldo,
@@ -484,13 +833,9 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_ring16_kernel(const bf16
             for (int it = blockIdx.x; it < items; it += G) __syncthreads();
             return;
         }
-        // ---- the two loader waves (14: K, 15: V): lane l fills LDS bytes [16 l, 16 l + 16) of an instruction's 1 KiB = slot `pos` of row `rg` of the
-        // row group, with the chunk that belongs there; rows >= N / chunks >= hd are out of the descriptor's range -> zeros
-        const int rg = (lane * 16) / R::RB, pos = ((lane * 16) % R::RB) / 16;
-        const int csrc = pos ^ r16_swz<R::CPR>(rg);
-        const int dma_voff = (csrc * 8 < hd) ? rg * (int)ld * 2 + csrc * 16 : 0x7f000000;
-        const int dma_gstep = R::RPI * (int)ld * 2;
-        const int rec_bytes = (int)(((int64_t)(N - 1) * ld + hd) * 2);
+        // ---- the two loader waves (14: K, 15: V)
+        int dma_voff, dma_gstep, rec_bytes;
+        r16_dma_lane<HD>(lane, ld, N, hd, dma_voff, dma_gstep, rec_bytes);
         // PACED in the steady state (one piece per ~150 clocks and loader): asked for all at once, an item's 56 KiB backs up the
         // CU's vector-memory path and the compute waves' own loads and stores queue behind it
         const int which = wave - 14;                  // 0: K, 1: V
@@ -519,34 +864,16 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_ring16_kernel(const bf16
     const int q = 16 * wave + l15;
     const int qrow = (q < N) ? q : N - 1;
     const float sl = scale * LOG2E;
-    int koff[NKS];                                    // QK^T operand: row 16 t + l15, chunk 4 ks + g
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) koff[ks] = l15 * R::RB + 16 * ((4 * ks + g) ^ r16_swz<R::CPR>(l15));
-    int voff[NDT];                                    // PV operand: rows 32 kk + 16 r + 4 g + (l15 >> 2), 8 bytes at d = 16 dt + 4 (l15 & 3)
-    {
-        const int rr = 4 * g + (l15 >> 2);
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-            voff[dt] = rr * R::RB + 16 * ((2 * dt + ((l15 & 3) >> 1)) ^ r16_swz<R::CPR>(rr)) + 8 * (l15 & 1);
-    }
+    const R16Frags<HD> fr(l15, g);
 
-    bf16x8 qf[NKS], qn[NKS];
+    bf16x8 qf[NKS];
+    u32x4 qn[NKS];
     auto q_issue = [&](int it) {
         const bf16_t* qptr = qkv + (int64_t)(it / H) * N * ld + (it % H) * hd;
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
             const int d = 32 * ks + 8 * g;
-            const u32x4 raw = *reinterpret_cast<const u32x4*>(qptr + (int64_t)qrow * ld + (d < hd ? d : 0));
-            qn[ks] = *reinterpret_cast<const bf16x8*>(&raw);
-        }
-    };
-    auto q_take = [&]() {
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const bool ok = 32 * ks + 8 * g < hd;
-            u32x4 raw = *reinterpret_cast<const u32x4*>(&qn[ks]);
-            raw = ok ? raw : zero4();
-            qf[ks] = *reinterpret_cast<bf16x8*>(&raw);
+            qn[ks] = *reinterpret_cast<const u32x4*>(qptr + (int64_t)qrow * ld + (d < hd ? d : 0));
         }
     };
 
@@ -556,24 +883,7 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_ring16_kernel(const bf16
     auto flush = [&]() {
         const float inv = __builtin_amdgcn_rcpf(l_tot);      // (1 ulp; the result is rounded to bf16)
         const int b = it_out / H, head = it_out % H;
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) {
-            bf16x4 v4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v4[e] = (bf16_t)(o[dt][e] * inv);
-            *reinterpret_cast<bf16x4*>(scr + l15 * C::RROW + (16 * dt + 4 * g) * 2) = v4;
-        }
-        __builtin_amdgcn_wave_barrier();
-        bf16_t* grow0 = out + ((int64_t)b * N + 16 * wave) * ldo + head * hd;
-        constexpr int RPI = 64 / C::CPR;              // rows per store instruction
-        const int chunk = lane % C::CPR, r0 = lane / C::CPR;
-#pragma unroll
-        for (int k = 0; k < 16 / RPI; ++k) {
-            const int r = r0 + RPI * k;
-            const u32x4 v = *reinterpret_cast<const u32x4*>(scr + r * C::RROW + chunk * 16);
-            if (16 * wave + r < N && chunk * 8 < hd) *reinterpret_cast<u32x4*>(grow0 + (int64_t)r * ldo + chunk * 8) = v;
-        }
-        __builtin_amdgcn_wave_barrier();
+        r16_store_rows<HD>(scr, o, inv, out + ((int64_t)b * N + 16 * wave) * ldo + head * hd, ldo, N - 16 * wave, hd, lane);
         if (lse && g == 0 && q < N) lse[((int64_t)b * H + head) * N + q] = (m2 + __builtin_amdgcn_logf(l_tot)) * LN2;
     };
 
@@ -584,43 +894,12 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_ring16_kernel(const bf16
     for (; it < items; it += G) {
         const int nxt = (it + G < items) ? it + G : it;
         TRACE_STAMP(it, 0);
-        q_take();
+        r16_take<HD>(qn, g, hd, qf);
         const char* Kb = smem + cur * 2 * arr_bytes;
         const char* Vb = Kb + arr_bytes;
-        // ---- pass 1: S^T, two 16-key tiles at a time; the operand chunks of the next pair are in flight while this pair's
-        // MFMAs run (software-pipelined by hand: left alone hipcc emits read -> wait -> MFMA one fragment at a time)
+        // ---- pass 1: S^T of the whole row block
         f32x4 s[NT];
-        const f32x4 zero4f = {0.f, 0.f, 0.f, 0.f};
-        bf16x8 ka[2][NKS], kb[2][NKS];
-        auto kread = [&](int t, bf16x8 (&dst)[2][NKS]) {
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) dst[tt][ks] = *reinterpret_cast<const bf16x8*>(Kb + 16 * (t + tt) * R::RB + koff[ks]);
-        };
-        auto kmma = [&](int t, const bf16x8 (&src)[2][NKS]) {
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) s[t + tt] = mma16(src[tt][0], qf[0], zero4f);
-#pragma unroll
-            for (int ks = 1; ks < NKS; ++ks)
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) s[t + tt] = mma16(src[tt][ks], qf[ks], s[t + tt]);
-        };
-        kread(0, ka);
-#pragma unroll
-        for (int t = 0; t < NT; t += 4) {
-            if (t + 2 < NT) kread(t + 2, kb);
-            __builtin_amdgcn_sched_barrier(0);
-            kmma(t, ka);
-            __builtin_amdgcn_sched_barrier(0);
-            if (t == 0) { TRACE_STAMP(it, 1); }
-            if (t + 2 < NT) {
-                if (t + 4 < NT) kread(t + 4, ka);
-                __builtin_amdgcn_sched_barrier(0);
-                kmma(t + 2, kb);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        r16_st_pass<HD, NT>(fr, Kb, qf, s, it);
         TRACE_STAMP(it, 3);
         q_issue(nxt);                                 // (here, not at the head of the item: the memory path is quiet now)
         // ---- softmax over the whole row (registers only); keys >= N sit in the last two tiles
@@ -652,38 +931,8 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_ring16_kernel(const bf16
         ps += __shfl_xor(ps, 16, 64);
         l_tot = ps + __shfl_xor(ps, 32, 64);
         TRACE_STAMP(it, 4);
-        // ---- pass 2: O^T += V^T P^T, 32 keys at a time, the d tiles in two halves: the V^T operand of the next half is in flight
-        // while this half's MFMAs run (half-steps keep the operand buffers at 2 x NDT / 2 fragments: the kernel has to fit 128 registers)
-        constexpr int NH = NDT / 2;
-        bf16x8 va[NH], vb[NH];
-        auto vread = [&](int kk, int half, bf16x8 (&dst)[NH]) {
-#pragma unroll
-            for (int i = 0; i < NH; ++i) {
-                union { bf16x4 q4[2]; bf16x8 v; } a;
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-                    a.q4[r] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                        (lds_bf16x4_t*)((uint32_t)(uintptr_t)Vb + (32 * kk + 16 * r) * R::RB + voff[NH * half + i]));
-                dst[i] = a.v;
-            }
-        };
-        vread(0, 0, va);
-#pragma unroll
-        for (int kk = 0; kk < NS; ++kk) {
-            vread(kk, 1, vb);
-            bf16x8 pb;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { pb[e] = (bf16_t)s[2 * kk][e]; pb[4 + e] = (bf16_t)s[2 * kk + 1][e]; }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < NH; ++i) o[i] = mma16(va[i], pb, kk == 0 ? zero4f : o[i]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (kk + 1 < NS) vread(kk + 1, 0, va);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < NH; ++i) o[NH + i] = mma16(vb[i], pb, kk == 0 ? zero4f : o[NH + i]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        // ---- pass 2: O^T = V^T P^T
+        r16_pv_pass<HD, NS>(fr, Vb, s, o, true);
         it_out = it;
         TRACE_STAMP(it, 5);
         flush();
@@ -807,37 +1056,6 @@ __global__ __launch_bounds__(SM_THREADS) void attn_bwd_small_kernel(const bf16_t
     TRACE_STAMP(trace_slot, 6);
 }
 
-// 16 accumulator rows (lane (row l & 15, g = l >> 4) holds d = 16 dt + 4 g + j) -> bf16 rows of `grow0`, transposed through the
-// wave's LDS scratch into whole 128-byte row stores.  The stores are BUFFER stores behind a descriptor that ends with the last
-// valid row (rows past it and chunks past hd are dropped by the bounds check, never branched over): the number of memory
-// operations is fixed, so a later wait for loads issued BEFORE these stores can be a counted vmcnt instead of vmcnt(0).
-template <int HD>
-__device__ __forceinline__ void r16_store_rows(char* scr, const f32x4 (&acc)[HD / 16], float mul, bf16_t* __restrict__ grow0,
-                                               int64_t ldg, int rows_valid, int hd, int lane) {
-    typedef Cfg<bf16_t, HD> C;
-    const int l15 = lane & 15, g = lane >> 4;
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; ++dt) {
-        bf16x4 v4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v4[e] = (bf16_t)(acc[dt][e] * mul);
-        *reinterpret_cast<bf16x4*>(scr + l15 * C::RROW + (16 * dt + 4 * g) * 2) = v4;
-    }
-    __builtin_amdgcn_wave_barrier();
-    constexpr int RPI = 64 / C::CPR;              // rows per store instruction
-    const int chunk = lane % C::CPR, r0 = lane / C::CPR;
-    const int nrec = rows_valid > 0 ? (int)(((int64_t)(rows_valid - 1) * ldg + hd) * 2) : 0;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(grow0, 0, nrec, 0x00020000);
-#pragma unroll
-    for (int k = 0; k < 16 / RPI; ++k) {
-        const int r = r0 + RPI * k;
-        const u32x4 v = *reinterpret_cast<const u32x4*>(scr + r * C::RROW + chunk * 16);
-        const int off = chunk * 8 < hd ? (int)(r * ldg * 2) + chunk * 16 : 0x7f000000;
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, ME_POL_ATTN_ST);
-    }
-    __builtin_amdgcn_wave_barrier();
-}
-
 // -----------------------------------------------------------------------------------------------------
 // Long sequences (N > SM_MAXN), forward: the ring form with K / V STREAMED.  A workgroup (16 waves: up to 14 compute waves of 16
 // queries + the two loader waves) owns a block of queries of one (batch, head) and walks the keys in chunks of 128; the loaders
@@ -851,8 +1069,6 @@ __device__ __forceinline__ void r16_store_rows(char* scr, const f32x4 (&acc)[HD 
 // wave -- 511 us against 444 at N = 1568: twice the barriers, and the chunk barrier keeps all waves of a SIMD in the same phase;
 // skipping the 64-key groups of the last chunk that lie past N with wave-uniform branches -- slower, 502 against 472 us: the joins
 // cost the straight-line schedule more than the skipped MFMAs save.)
-constexpr int ST_KC = 128;                            // keys per chunk
-constexpr int ST_RING = 3;
 template <int HD>
 __global__ __launch_bounds__(R16_THREADS) void attn_fwd_stream16_kernel(const bf16_t* __restrict__ qkv, int64_t ld,
                                                                         bf16_t* __restrict__ out, int64_t ldo,
@@ -863,9 +1079,8 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_stream16_kernel(const bf
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int arr_bytes = ST_KC * R::RB;          // one array (K or V) of one chunk
     constexpr int slot_bytes = 2 * arr_bytes;
-    constexpr int NPC = ST_KC / R::RPI;               // DMA pieces per array and chunk
     constexpr int NTC = ST_KC / 16;                   // 16-key tiles per chunk
-    constexpr int NKS = HD / 32, NDT = HD / 16, NH = NDT / 2;
+    constexpr int NKS = HD / 32, NDT = HD / 16;
     constexpr int SCR = 16 * C::RROW;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -873,77 +1088,19 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_stream16_kernel(const bf
     const int Cdim = H * hd;
     const int G = (int)gridDim.x;
     const int NCH = (N + ST_KC - 1) / ST_KC;
-    // XCD-major virtual id: the workgroups of one XCD (blockIdx & 7) take consecutive items = neighbouring query blocks of a head
-    const int vid = (G & 7) == 0 ? ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
-    const int my_items = vid < items ? (items - vid + G - 1) / G : 0;      // items vid, vid + G, ...
-    const bool compute = 16 * wave < QB;              // wave-uniform
-
-    if (!compute) {
-        // ---- loader waves: the last two (QB = 224) or four (fewer compute waves) waves; the others only keep the barrier count.
-        // With four, each array of a chunk is split between two loaders -- an LDS-DMA piece costs its issuer 60-180 clocks, and 16 of
-        // them per 128-key chunk is about what the compute waves of a short query block need for the chunk.
-        const int NL = QB <= 12 * 16 ? 4 : 2;
-        if (wave < 16 - NL) {
-            for (int k = 0; k < my_items * NCH; ++k) __builtin_amdgcn_s_barrier();
-            return;
-        }
-        const int lw = wave - (16 - NL);              // loader index
-        const int which = lw & 1;                     // 0: K, 1: V
-        const int part = lw >> 1, nparts = NL >> 1;   // which pieces of the array
-        const int rg = (lane * 16) / R::RB, pos = ((lane * 16) % R::RB) / 16;
-        const int csrc = pos ^ r16_swz<R::CPR>(rg);
-        const int dma_voff = (csrc * 8 < hd) ? rg * (int)ld * 2 + csrc * 16 : 0x7f000000;
-        const int dma_gstep = R::RPI * (int)ld * 2;
-        const int rec_bytes = (int)(((int64_t)(N - 1) * ld + hd) * 2);
-        const int total = my_items * NCH;
-        // chunk j of the workgroup's stream = chunk j % NCH of its (j / NCH)-th item
-        auto fill = [&](int j) {
-            if (j >= total) return;
-            const int it = vid + (j / NCH) * G, c = j % NCH;
-            const int bh = it / nqb;
-            const bf16_t* base = qkv + (int64_t)(bh / H) * N * ld + (bh % H) * hd + (1 + which) * Cdim;
-            const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base), 0, rec_bytes, 0x00020000);
-            char* dst = smem + (j % ST_RING) * slot_bytes + which * arr_bytes;
-            const int voff = dma_voff + c * NPC * dma_gstep;
-            if (nparts == 1) {
-#pragma unroll
-                for (int i = 0; i < NPC; ++i)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, (lds_dma_t*)(dst + i * 1024), 16, voff + i * dma_gstep, 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int i = 0; i < NPC / 2; ++i) {
-                    const int p = 2 * i + part;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, (lds_dma_t*)(dst + p * 1024), 16, voff + p * dma_gstep, 0, 0, 0);
-                }
-            }
-        };
-        fill(0);
-        fill(1);
-        for (int k = 0; k < total; ++k) {
-            // chunk k has landed once at most chunk k + 1's pieces (of this loader) are outstanding (in-order retirement)
-            if (k + 1 >= total) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (nparts == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPC) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPC / 2) : "memory");
-            __builtin_amdgcn_s_barrier();             // chunk k ready; everybody is done with chunk k - 1
-            fill(k + 2);                              // ... whose slot takes chunk k + 2
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int vid = st16_vid(G);
+    const int my_items = st16_my_items(vid, items, G);
+    if (16 * wave >= QB) {
+        // ---- loader waves: the last two (QB = 224) or four (fewer compute waves) waves
+        st16_loader<HD, false, 16>(smem, nullptr, wave, lane, QB <= 12 * 16 ? 4 : 2, my_items * NCH, NCH, vid, G, nqb, H, N, hd, qkv, ld, Cdim, qkv, ld,
+                                   2 * Cdim, nullptr, nullptr);
         return;
     }
 
     // ---- compute waves
     char* scr = smem + ST_RING * slot_bytes + wave * SCR;
     const float sl = scale * LOG2E;
-    int koff[NKS];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) koff[ks] = l15 * R::RB + 16 * ((4 * ks + g) ^ r16_swz<R::CPR>(l15));
-    int voff[NDT];
-    {
-        const int rr = 4 * g + (l15 >> 2);
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-            voff[dt] = rr * R::RB + 16 * ((2 * dt + ((l15 & 3) >> 1)) ^ r16_swz<R::CPR>(rr)) + 8 * (l15 & 1);
-    }
+    const R16Frags<HD> fr(l15, g);
     const f32x4 zero4f = {0.f, 0.f, 0.f, 0.f};
     // the wave's own query rows: item ii + 1's are fetched under item ii's last chunk
     u32x4 qn[NKS];
@@ -966,11 +1123,7 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_stream16_kernel(const bf
         const int q0 = qb * QB + 16 * wave;           // first query of this wave
         const int q = q0 + l15;
         bf16x8 qf[NKS];
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const u32x4 raw = 32 * ks + 8 * g < hd ? qn[ks] : zero4();      // chunks of d past hd are zeros
-            qf[ks] = *reinterpret_cast<const bf16x8*>(&raw);
-        }
+        r16_take<HD>(qn, g, hd, qf);
         f32x4 o[NDT];
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) o[dt] = zero4f;
@@ -981,35 +1134,9 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_stream16_kernel(const bf
             const char* Kb = smem + (j % ST_RING) * slot_bytes;
             const char* Vb = Kb + arr_bytes;
             const int nkeys = N - c * ST_KC;          // valid keys of this chunk (>= 1); wave-uniform
-            // ---- S^T for the chunk's 16-key tiles, two at a time, operands one pair ahead
+            // ---- S^T for the chunk's 16-key tiles
             f32x4 s[NTC];
-            bf16x8 ka[2][NKS], kb[2][NKS];
-            auto kread = [&](int t, bf16x8 (&dst)[2][NKS]) {
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                    for (int ks = 0; ks < NKS; ++ks) dst[tt][ks] = *reinterpret_cast<const bf16x8*>(Kb + 16 * (t + tt) * R::RB + koff[ks]);
-            };
-            auto kmma = [&](int t, const bf16x8 (&src)[2][NKS]) {
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) s[t + tt] = mma16(src[tt][0], qf[0], zero4f);
-#pragma unroll
-                for (int ks = 1; ks < NKS; ++ks)
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) s[t + tt] = mma16(src[tt][ks], qf[ks], s[t + tt]);
-            };
-            kread(0, ka);
-#pragma unroll
-            for (int t = 0; t < NTC; t += 4) {
-                kread(t + 2, kb);
-                __builtin_amdgcn_sched_barrier(0);
-                kmma(t, ka);
-                __builtin_amdgcn_sched_barrier(0);
-                if (t + 4 < NTC) kread(t + 4, ka);
-                __builtin_amdgcn_sched_barrier(0);
-                kmma(t + 2, kb);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            r16_st_pass<HD, NTC>(fr, Kb, qf, s, -1);
             // ---- online softmax
             if (nkeys < ST_KC) {
                 int nk = nkeys - 4 * g;               // (opaque: hipcc would hoist the lane masks out of the loops into SGPRs)
@@ -1041,36 +1168,8 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_stream16_kernel(const bf
             m_run = m_new;
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt) o[dt] *= alpha;
-            // ---- O^T += V^T P^T, 32 keys at a time, d tiles in two halves (operands one half ahead)
-            bf16x8 va[NH], vb[NH];
-            auto vread = [&](int kk, int half, bf16x8 (&dst)[NH]) {
-#pragma unroll
-                for (int i = 0; i < NH; ++i) {
-                    union { bf16x4 q4[2]; bf16x8 v; } a;
-#pragma unroll
-                    for (int r = 0; r < 2; ++r)
-                        a.q4[r] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                            (lds_bf16x4_t*)((uint32_t)(uintptr_t)Vb + (32 * kk + 16 * r) * R::RB + voff[NH * half + i]));
-                    dst[i] = a.v;
-                }
-            };
-            vread(0, 0, va);
-#pragma unroll
-            for (int kk = 0; kk < ST_KC / 32; ++kk) {
-                vread(kk, 1, vb);
-                bf16x8 pb;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { pb[e] = (bf16_t)s[2 * kk][e]; pb[4 + e] = (bf16_t)s[2 * kk + 1][e]; }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < NH; ++i) o[i] = mma16(va[i], pb, o[i]);
-                __builtin_amdgcn_sched_barrier(0);
-                if (kk + 1 < ST_KC / 32) vread(kk + 1, 0, va);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < NH; ++i) o[NH + i] = mma16(vb[i], pb, o[NH + i]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            // ---- O^T += V^T P^T
+            r16_pv_pass<HD, ST_KC / 32>(fr, Vb, s, o, false);
         }
         // ---- finish the item: row sums over the four key groups, normalise, store
         l_run += __shfl_xor(l_run, 16, 64);
@@ -1078,22 +1177,6 @@ __global__ __launch_bounds__(R16_THREADS) void attn_fwd_stream16_kernel(const bf
         const float inv = __builtin_amdgcn_rcpf(l_run);
         r16_store_rows<HD>(scr, o, inv, out + ((int64_t)b * N + q0) * ldo + head * hd, ldo, N - q0, hd, lane);
         if (lse && g == 0 && q < N) lse[((int64_t)b * H + head) * N + q] = (m_run + __builtin_amdgcn_logf(l_run)) * LN2;
-    }
-}
-
-// a softmax probability from its log2-domain argument: v_exp_f32 with the clamp output modifier (hipcc folds the med3 into it)
-__device__ __forceinline__ float r16_p(float arg) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(arg), 0.f, 1.f); }
-
-// four probabilities and their dS / scale (the 32-key dK / dV kernel):  pe = exp2(s * sl - l2),  ds = pe * (dp - d).  The same on
-// PAIRS (measured and removed) -- v_pk_fma_f32 for the argument, v_pk_mul_f32 + v_pk_fma_f32 for dS, 3.5 instead of 5 VALU instructions per score (and, tried with
-// it, the same form in every other backward kernel and v_pk_fma_f32 / v_pk_add_f32 in the forward kernels' exp2 + row sum) -- measured SLOWER everywhere (same box,
-// profiles/r06_attn_bwd_stream32.txt: N = 197 forward 68.7 -> 74.7 us, backward 212.9 -> 222.7; N = 1568 forward 477 -> 504, backward
-// 1 218 -> 1 247): the packed fp32 operations do not issue at the rate of two scalar ones here, and assembling the pairs costs moves.
-__device__ __forceinline__ void r16_pds4(const f32x4& s, const f32x4& dp, float sl, const f32x4& l2, const f32x4& d, f32x4& pe, f32x4& ds) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        pe[e] = r16_p(s[e] * sl - l2[e]);
-        ds[e] = pe[e] * (dp[e] - d[e]);
     }
 }
 
@@ -1176,14 +1259,9 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_ring16_kernel(const bf16
         }
         // ---- loader waves: 14 fills the first array of a region (K, Q), 15 the second (V, dO)
         const int which = wave - 14;
-        const int rg = (lane * 16) / R::RB, pos = ((lane * 16) % R::RB) / 16;
-        const int csrc = pos ^ r16_swz<R::CPR>(rg);
-        const bool cok = csrc * 8 < hd;
-        const int voff_a = cok ? rg * (int)ld * 2 + csrc * 16 : 0x7f000000;              // rows of qkv
-        const int voff_d = cok ? rg * (int)(which ? lddo : ld) * 2 + csrc * 16 : 0x7f000000;      // rows of the QD array of this loader
-        const int gstep_a = R::RPI * (int)ld * 2, gstep_d = R::RPI * (int)(which ? lddo : ld) * 2;
-        const int rec_a = (int)(((int64_t)(N - 1) * ld + hd) * 2);
-        const int rec_d = (int)(((int64_t)(N - 1) * (which ? lddo : ld) + hd) * 2);
+        int voff_a, gstep_a, rec_a, voff_d, gstep_d, rec_d;
+        r16_dma_lane<HD>(lane, ld, N, hd, voff_a, gstep_a, rec_a);                        // rows of qkv
+        r16_dma_lane<HD>(lane, which ? lddo : ld, N, hd, voff_d, gstep_d, rec_d);         // rows of the QD array of this loader
         auto fill = [&](const bf16_t* base, int rec, int voff, int gstep, char* dst, int paced) {
             const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base), 0, rec, 0x00020000);
 #pragma unroll
@@ -1216,16 +1294,7 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_ring16_kernel(const bf16
     const bool row_ok = row < N;
     const int rowc = row_ok ? row : N - 1;
     const float sl = scale * LOG2E;
-    int koff[NKS];                                    // row-operand read: row 16 t + l15, chunk 4 ks + g
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) koff[ks] = l15 * R::RB + 16 * ((4 * ks + g) ^ r16_swz<R::CPR>(l15));
-    int troff[NDT];                                   // transposing read: rows 32 kk + 16 r + 4 g + (l15 >> 2), 8 bytes at d = 16 dt + 4 (l15 & 3)
-    {
-        const int rr = 4 * g + (l15 >> 2);
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-            troff[dt] = rr * R::RB + 16 * ((2 * dt + ((l15 & 3) >> 1)) ^ r16_swz<R::CPR>(rr)) + 8 * (l15 & 1);
-    }
+    const R16Frags<HD> fr(l15, g);
     for (int i = tid; i < NR; i += 64 * ((N + 15) / 16)) { lse_s[i] = INFINITY; del_s[i] = 0.f; }      // rows no wave owns stay this way
 
     // own-row operands of the NEXT item's phase A, in flight across this item's phase B
@@ -1243,18 +1312,6 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_ring16_kernel(const bf16
         else if (arr == 2) on[ks] = *reinterpret_cast<const u32x4*>(out + ((int64_t)b * N + rowc) * ldo + head * hd + dc);
         else lse_n = lse[((int64_t)b * H + head) * N + rowc];
     };
-    auto rowread = [&](const char* arr, int t, bf16x8 (&dst)[NKS]) {
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) dst[ks] = *reinterpret_cast<const bf16x8*>(arr + 16 * t * R::RB + koff[ks]);
-    };
-    auto trread = [&](const char* arr, int kk, int dt) {
-        union { bf16x4 q4[2]; bf16x8 v; } a;
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-            a.q4[r] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)((uint32_t)(uintptr_t)arr + (32 * kk + 16 * r) * R::RB + troff[dt]));
-        return a.v;
-    };
-    const f32x4 zero4f = {0.f, 0.f, 0.f, 0.f};
 
     int it = blockIdx.x;
 #pragma unroll
@@ -1282,11 +1339,7 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_ring16_kernel(const bf16
         }
         del += __shfl_xor(del, 16, 64);
         del += __shfl_xor(del, 32, 64);
-        // +inf on padded queries -> P = 0.  Valid rows keep their exact lse; a padded key (zero K row, s = 0) evaluates to
-        // exp2(-lse2), which overflows for a row whose scores are all very negative -- and it only ever multiplies zeros.  Every P is
-        // therefore taken through r16_p(): exp2 with the result clamped to [0, 1] (the output modifier of v_exp_f32, no extra
-        // instruction), exact for real entries (P <= 1 by construction of lse) and finite for padded ones
-        const float lse2 = row_ok ? lse_n * LOG2E : INFINITY;
+        const float lse2 = row_ok ? lse_n * LOG2E : INFINITY;      // +inf on padded queries -> P = 0 (see r16_dq_step)
         if (g == 0) {
             lse_s[row] = lse2;
             del_s[row] = del;
@@ -1295,39 +1348,11 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_ring16_kernel(const bf16
         TRACE_STAMP(it, 1);
         f32x4 dq[NDT];
 #pragma unroll
-        for (int kk = 0; kk < NS; ++kk) {
-            bf16x8 ka[2][NKS], va[2][NKS];
-            rowread(KVr, 2 * kk, ka[0]); rowread(KVr, 2 * kk + 1, ka[1]);
-            rowread(KVr + arr_bytes, 2 * kk, va[0]); rowread(KVr + arr_bytes, 2 * kk + 1, va[1]);
-            f32x4 s[2], dp[2];
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) { s[tt] = mma16(ka[tt][0], qf[0], zero4f); dp[tt] = mma16(va[tt][0], dof[0], zero4f); }
-#pragma unroll
-            for (int ks = 1; ks < NKS; ++ks)
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) { s[tt] = mma16(ka[tt][ks], qf[ks], s[tt]); dp[tt] = mma16(va[tt][ks], dof[ks], dp[tt]); }
-            bf16x8 kt[NDT];
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) kt[dt] = trread(KVr, kk, dt);
-            // keys >= N: their K rows are zeros, so whatever dS holds there adds nothing to dQ -- no mask
-            bf16x8 dsb;
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float pe = r16_p(s[tt][e] * sl - lse2);
-                    dsb[4 * tt + e] = (bf16_t)(pe * (dp[tt][e] - del));      // dS^T / scale (scale applied to dQ once)
-                }
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) dq[dt] = mma16(kt[dt], dsb, kk == 0 ? zero4f : dq[dt]);
-        }
+        for (int kk = 0; kk < NS; ++kk) r16_dq_step<HD>(fr, KVr, KVr + arr_bytes, kk, qf, dof, sl, lse2, del, dq, kk == 0);
         // this wave's own K / V rows = phase B's register operands (the loaders overwrite the region behind barrier 1)
         bf16x8 kf[NKS], vf[NKS];
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            kf[ks] = *reinterpret_cast<const bf16x8*>(KVr + 16 * wave * R::RB + koff[ks]);
-            vf[ks] = *reinterpret_cast<const bf16x8*>(KVr + arr_bytes + 16 * wave * R::RB + koff[ks]);
-        }
+        fr.rowread(KVr, wave, kf);
+        fr.rowread(KVr + arr_bytes, wave, vf);
         TRACE_STAMP(it, 2);
         if (wave == 0) draw_take(drawn, it);
         __syncthreads();      // barrier 1: KV region dead; {Q, dO} of this item landed; lse_s / del_s complete; next item's id published
@@ -1344,43 +1369,7 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_ring16_kernel(const bf16
         for (int qq = 0; qq < NS; ++qq) {
 #pragma unroll
             for (int i = qq * NPF / NS; i < (qq + 1) * NPF / NS; ++i) prefetch(nxt, i);
-            f32x4 s[2], dp[2];
-            {
-                bf16x8 qa[2][NKS];
-                rowread(QDr, 2 * qq, qa[0]); rowread(QDr, 2 * qq + 1, qa[1]);
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) s[tt] = mma16(qa[tt][0], kf[0], zero4f);
-#pragma unroll
-                for (int ks = 1; ks < NKS; ++ks)
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) s[tt] = mma16(qa[tt][ks], kf[ks], s[tt]);
-            }
-            {
-                bf16x8 da[2][NKS];
-                rowread(QDr + arr_bytes, 2 * qq, da[0]); rowread(QDr + arr_bytes, 2 * qq + 1, da[1]);
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) dp[tt] = mma16(da[tt][0], vf[0], zero4f);
-#pragma unroll
-                for (int ks = 1; ks < NKS; ++ks)
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) dp[tt] = mma16(da[tt][ks], vf[ks], dp[tt]);
-            }
-            bf16x8 pb, dsb;
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) {
-                const f32x4 L = *reinterpret_cast<const f32x4*>(lse_s + 16 * (2 * qq + tt) + 4 * g);
-                const f32x4 D = *reinterpret_cast<const f32x4*>(del_s + 16 * (2 * qq + tt) + 4 * g);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float pe = r16_p(s[tt][e] * sl - L[e]);
-                    pb[4 * tt + e] = (bf16_t)pe;
-                    dsb[4 * tt + e] = (bf16_t)(pe * (dp[tt][e] - D[e]));      // dS / scale (scale applied to dK once)
-                }
-            }
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) dv[dt] = mma16(trread(QDr + arr_bytes, qq, dt), pb, qq == 0 ? zero4f : dv[dt]);
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) dk[dt] = mma16(trread(QDr, qq, dt), dsb, qq == 0 ? zero4f : dk[dt]);
+            r16_dkdv_step<HD, false>(fr, QDr, QDr + arr_bytes, lse_s, del_s, qq, g, kf, vf, sl, dk, dv, qq == 0);
         }
         TRACE_STAMP(it, 5);
         r16_store_rows<HD>(scr, dk, scale, grow0 + Cdim, lddq, N - 16 * wave, hd, lane);
@@ -1407,83 +1396,6 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_ring16_kernel(const bf16
 // Round 6: where a key block fills seven 32-key waves the second phase runs as attn_bwd_dkdv_stream32_kernel (further down; -15 % on that phase).
 constexpr int ST_BWD_MINN = 513;
 
-// loader waves of the streaming backward kernels: array 0 / 1 of a chunk from (a0, ld0) / (a1, ld1); FL: 128 floats of f0 / f1 per chunk.
-// NW waves per workgroup, the last NL of them load (the others past the compute waves keep the barrier count): NL = 4 (two waves per array),
-// 2 (one per array) or 1 (one wave fills both arrays -- the 8-wave kernels with seven compute waves).
-template <int HD, bool FL, int NW>
-__device__ __forceinline__ void st16_bwd_loader(char* smem, char* fring, int wave, int lane, int NL, int total, int NCH, int vid, int G,
-                                                int nblk, int H, int N, int hd, const bf16_t* a0, int64_t ld0, int64_t hoff0,
-                                                const bf16_t* a1, int64_t ld1, int64_t hoff1, const float* f0, const float* f1) {
-    typedef RCfg<HD> R;
-    constexpr int arr_bytes = ST_KC * R::RB;
-    constexpr int slot_bytes = 2 * arr_bytes;
-    constexpr int NPC = ST_KC / R::RPI;
-    static_assert(2 * NPC + 4 <= 63, "vmcnt range");
-    if (wave < NW - NL) {                             // spare waves: the barrier count only
-        for (int k = 0; k < total; ++k) __builtin_amdgcn_s_barrier();
-        return;
-    }
-    const int lw = wave - (NW - NL);
-    const int which0 = NL == 1 ? 0 : (lw & 1), nwhich = NL == 1 ? 2 : 1;
-    const int part = lw >> 1, nparts = NL == 4 ? 2 : 1;
-    const int rg = (lane * 16) / R::RB, pos = ((lane * 16) % R::RB) / 16;
-    const int csrc = pos ^ r16_swz<R::CPR>(rg);
-    auto fill = [&](int j) {
-        if (j >= total) return;
-        const int it = vid + (j / NCH) * G, c = j % NCH;
-        const int bh = it / nblk;
-        for (int w = 0; w < nwhich; ++w) {
-            const int which = which0 + w;
-            const bf16_t* const arr = which ? a1 : a0;
-            const int64_t ldw = which ? ld1 : ld0, hoff = which ? hoff1 : hoff0;
-            const int dma_voff = (csrc * 8 < hd) ? rg * (int)ldw * 2 + csrc * 16 : 0x7f000000;
-            const int dma_gstep = R::RPI * (int)ldw * 2;
-            const int rec_bytes = (int)(((int64_t)(N - 1) * ldw + hd) * 2);
-            const bf16_t* base = arr + (int64_t)(bh / H) * N * ldw + (bh % H) * hd + hoff;
-            const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base), 0, rec_bytes, 0x00020000);
-            char* dst = smem + (j % ST_RING) * slot_bytes + which * arr_bytes;
-            const int voff = dma_voff + c * NPC * dma_gstep;
-            if (nparts == 1) {
-#pragma unroll
-                for (int i = 0; i < NPC; ++i)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, (lds_dma_t*)(dst + i * 1024), 16, voff + i * dma_gstep, 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int i = 0; i < NPC / 2; ++i) {
-                    const int p = 2 * i + part;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, (lds_dma_t*)(dst + p * 1024), 16, voff + p * dma_gstep, 0, 0, 0);
-                }
-            }
-            if (FL) {
-                // 128 floats of this array's statistics: two dword pieces of 64 (one each when two loaders share the array)
-                const float* const farr = which ? f1 : f0;
-                const __amdgpu_buffer_rsrc_t rf =
-                    __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(farr + (int64_t)bh * N), 0, N * 4, 0x00020000);
-                char* fdst = fring + ((j % ST_RING) * 2 + which) * (ST_KC * 4);
-                const int fvoff = (c * ST_KC + lane) * 4;
-                if (nparts == 1) {
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rf, (lds_dma_t*)fdst, 4, fvoff, 0, 0, 0);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rf, (lds_dma_t*)(fdst + 256), 4, fvoff + 256, 0, 0, 0);
-                } else {
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rf, (lds_dma_t*)(fdst + 256 * part), 4, fvoff + 256 * part, 0, 0, 0);
-                }
-            }
-        }
-    };
-    fill(0);
-    fill(1);
-    for (int k = 0; k < total; ++k) {
-        // chunk k has landed once at most chunk k + 1's pieces (of this loader) are outstanding (in-order retirement)
-        if (k + 1 >= total) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (NL == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NPC + (FL ? 4 : 0)) : "memory");
-        else if (NL == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPC + (FL ? 2 : 0)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPC / 2 + (FL ? 1 : 0)) : "memory");
-        __builtin_amdgcn_s_barrier();                 // chunk k ready; everybody is done with chunk k - 1
-        fill(k + 2);                                  // ... whose slot takes chunk k + 2
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
 template <int HD>
 __global__ __launch_bounds__(R16_THREADS) void attn_bwd_dq_stream16_kernel(const bf16_t* __restrict__ qkv, int64_t ld,
                                                                            const bf16_t* __restrict__ out, int64_t ldo,
@@ -1504,36 +1416,16 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_dq_stream16_kernel(const
     const int Cdim = H * hd;
     const int G = (int)gridDim.x;
     const int NCH = (N + ST_KC - 1) / ST_KC;
-    const int vid = (G & 7) == 0 ? ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
-    const int my_items = vid < items ? (items - vid + G - 1) / G : 0;
+    const int vid = st16_vid(G);
+    const int my_items = st16_my_items(vid, items, G);
     if (16 * wave >= QB) {
-        st16_bwd_loader<HD, false, 16>(smem, nullptr, wave, lane, QB <= 12 * 16 ? 4 : 2, my_items * NCH, NCH, vid, G, nqb, H, N, hd, qkv, ld, Cdim, qkv, ld,
+        st16_loader<HD, false, 16>(smem, nullptr, wave, lane, QB <= 12 * 16 ? 4 : 2, my_items * NCH, NCH, vid, G, nqb, H, N, hd, qkv, ld, Cdim, qkv, ld,
                                    2 * Cdim, nullptr, nullptr);
         return;
     }
     char* scr = smem + ST_RING * slot_bytes + wave * SCR;
     const float sl = scale * LOG2E;
-    int koff[NKS];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) koff[ks] = l15 * R::RB + 16 * ((4 * ks + g) ^ r16_swz<R::CPR>(l15));
-    int troff[NDT];
-    {
-        const int rr = 4 * g + (l15 >> 2);
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-            troff[dt] = rr * R::RB + 16 * ((2 * dt + ((l15 & 3) >> 1)) ^ r16_swz<R::CPR>(rr)) + 8 * (l15 & 1);
-    }
-    auto rowread = [&](const char* arr, int t, bf16x8 (&dst)[NKS]) {
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) dst[ks] = *reinterpret_cast<const bf16x8*>(arr + 16 * t * R::RB + koff[ks]);
-    };
-    auto trread = [&](const char* arr, int kk, int dt) {
-        union { bf16x4 q4[2]; bf16x8 v; } a;
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-            a.q4[r] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)((uint32_t)(uintptr_t)arr + (32 * kk + 16 * r) * R::RB + troff[dt]));
-        return a.v;
-    };
+    const R16Frags<HD> fr(l15, g);
     const f32x4 zero4f = {0.f, 0.f, 0.f, 0.f};
     // the wave's own rows (Q, dO, O, lse): the next item's are fetched under this item's last chunk
     u32x4 qn[NKS], don[NKS], on[NKS];
@@ -1585,31 +1477,7 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_dq_stream16_kernel(const
             const char* Kb = smem + (j % ST_RING) * slot_bytes;
             const char* Vb = Kb + arr_bytes;
 #pragma unroll
-            for (int kk = 0; kk < ST_KC / 32; ++kk) {
-                bf16x8 ka[2][NKS], va[2][NKS];
-                rowread(Kb, 2 * kk, ka[0]); rowread(Kb, 2 * kk + 1, ka[1]);
-                rowread(Vb, 2 * kk, va[0]); rowread(Vb, 2 * kk + 1, va[1]);
-                f32x4 s[2], dp[2];
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) { s[tt] = mma16(ka[tt][0], qf[0], zero4f); dp[tt] = mma16(va[tt][0], dof[0], zero4f); }
-#pragma unroll
-                for (int ks = 1; ks < NKS; ++ks)
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) { s[tt] = mma16(ka[tt][ks], qf[ks], s[tt]); dp[tt] = mma16(va[tt][ks], dof[ks], dp[tt]); }
-                bf16x8 kt[NDT];
-#pragma unroll
-                for (int dt = 0; dt < NDT; ++dt) kt[dt] = trread(Kb, kk, dt);
-                bf16x8 dsb;
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float pe = r16_p(s[tt][e] * sl - lse2);
-                        dsb[4 * tt + e] = (bf16_t)(pe * (dp[tt][e] - del));      // dS^T / scale (scale applied to dQ once)
-                    }
-#pragma unroll
-                for (int dt = 0; dt < NDT; ++dt) dq[dt] = mma16(kt[dt], dsb, dq[dt]);
-            }
+            for (int kk = 0; kk < ST_KC / 32; ++kk) r16_dq_step<HD>(fr, Kb, Vb, kk, qf, dof, sl, lse2, del, dq, false);
         };
         for (int c = 0; c + 1 < NCH; ++c, ++j) {
             __syncthreads();                          // chunk j has landed (the loaders waited for it)
@@ -1643,37 +1511,17 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_dkdv_stream16_kernel(con
     const int Cdim = H * hd;
     const int G = (int)gridDim.x;
     const int NCH = (N + ST_KC - 1) / ST_KC;
-    const int vid = (G & 7) == 0 ? ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
-    const int my_items = vid < items ? (items - vid + G - 1) / G : 0;
+    const int vid = st16_vid(G);
+    const int my_items = st16_my_items(vid, items, G);
     char* const fring = smem + ST_RING * slot_bytes;
     if (16 * wave >= KB) {
-        st16_bwd_loader<HD, true, 16>(smem, fring, wave, lane, KB <= 12 * 16 ? 4 : 2, my_items * NCH, NCH, vid, G, nkb, H, N, hd, qkv, ld, 0, dout, lddo, 0, lse,
+        st16_loader<HD, true, 16>(smem, fring, wave, lane, KB <= 12 * 16 ? 4 : 2, my_items * NCH, NCH, vid, G, nkb, H, N, hd, qkv, ld, 0, dout, lddo, 0, lse,
                                   delta);
         return;
     }
     char* scr = fring + FRING + wave * SCR;
     const float sl = scale * LOG2E;
-    int koff[NKS];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) koff[ks] = l15 * R::RB + 16 * ((4 * ks + g) ^ r16_swz<R::CPR>(l15));
-    int troff[NDT];
-    {
-        const int rr = 4 * g + (l15 >> 2);
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-            troff[dt] = rr * R::RB + 16 * ((2 * dt + ((l15 & 3) >> 1)) ^ r16_swz<R::CPR>(rr)) + 8 * (l15 & 1);
-    }
-    auto rowread = [&](const char* arr, int t, bf16x8 (&dst)[NKS]) {
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) dst[ks] = *reinterpret_cast<const bf16x8*>(arr + 16 * t * R::RB + koff[ks]);
-    };
-    auto trread = [&](const char* arr, int kk, int dt) {
-        union { bf16x4 q4[2]; bf16x8 v; } a;
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-            a.q4[r] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)((uint32_t)(uintptr_t)arr + (32 * kk + 16 * r) * R::RB + troff[dt]));
-        return a.v;
-    };
+    const R16Frags<HD> fr(l15, g);
     const f32x4 zero4f = {0.f, 0.f, 0.f, 0.f};
     // the wave's own K / V rows: the next item's are fetched under this item's last chunk
     u32x4 kn[NKS], vn[NKS];
@@ -1696,13 +1544,8 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_dkdv_stream16_kernel(con
         const int b = bh / H, head = bh % H;
         const int k0 = kb * KB + 16 * wave;
         bf16x8 kf[NKS], vf[NKS];
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const bool ok = 32 * ks + 8 * g < hd;
-            const u32x4 kv = ok ? kn[ks] : zero4(), vv = ok ? vn[ks] : zero4();
-            kf[ks] = *reinterpret_cast<const bf16x8*>(&kv);
-            vf[ks] = *reinterpret_cast<const bf16x8*>(&vv);
-        }
+        r16_take<HD>(kn, g, hd, kf);
+        r16_take<HD>(vn, g, hd, vf);
         f32x4 dk[NDT], dv[NDT];
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) { dk[dt] = zero4f; dv[dt] = zero4f; }
@@ -1712,45 +1555,7 @@ __global__ __launch_bounds__(R16_THREADS) void attn_bwd_dkdv_stream16_kernel(con
             const float* lsb = reinterpret_cast<const float*>(fring + (j % ST_RING) * 2 * (ST_KC * 4));
             const float* deb = lsb + ST_KC;
 #pragma unroll
-            for (int qq = 0; qq < ST_KC / 32; ++qq) {
-                f32x4 s[2], dp[2];
-                {
-                    bf16x8 qa[2][NKS];
-                    rowread(Qb, 2 * qq, qa[0]); rowread(Qb, 2 * qq + 1, qa[1]);
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) s[tt] = mma16(qa[tt][0], kf[0], zero4f);
-#pragma unroll
-                    for (int ks = 1; ks < NKS; ++ks)
-#pragma unroll
-                        for (int tt = 0; tt < 2; ++tt) s[tt] = mma16(qa[tt][ks], kf[ks], s[tt]);
-                }
-                {
-                    bf16x8 da[2][NKS];
-                    rowread(Db, 2 * qq, da[0]); rowread(Db, 2 * qq + 1, da[1]);
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) dp[tt] = mma16(da[tt][0], vf[0], zero4f);
-#pragma unroll
-                    for (int ks = 1; ks < NKS; ++ks)
-#pragma unroll
-                        for (int tt = 0; tt < 2; ++tt) dp[tt] = mma16(da[tt][ks], vf[ks], dp[tt]);
-                }
-                bf16x8 pb, dsb;
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) {
-                    const f32x4 L = *reinterpret_cast<const f32x4*>(lsb + 16 * (2 * qq + tt) + 4 * g);
-                    const f32x4 D = *reinterpret_cast<const f32x4*>(deb + 16 * (2 * qq + tt) + 4 * g);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float pe = r16_p(s[tt][e] * sl - L[e] * LOG2E);
-                        pb[4 * tt + e] = (bf16_t)pe;
-                        dsb[4 * tt + e] = (bf16_t)(pe * (dp[tt][e] - D[e]));      // dS / scale (scale applied to dK once)
-                    }
-                }
-#pragma unroll
-                for (int dt = 0; dt < NDT; ++dt) dv[dt] = mma16(trread(Db, qq, dt), pb, dv[dt]);
-#pragma unroll
-                for (int dt = 0; dt < NDT; ++dt) dk[dt] = mma16(trread(Qb, qq, dt), dsb, dk[dt]);
-            }
+            for (int qq = 0; qq < ST_KC / 32; ++qq) r16_dkdv_step<HD, true>(fr, Qb, Db, lsb, deb, qq, g, kf, vf, sl, dk, dv, false);
         };
         for (int c = 0; c + 1 < NCH; ++c, ++j) {
             __syncthreads();
@@ -1799,38 +1604,18 @@ __global__ __launch_bounds__(ST32_THREADS) void attn_bwd_dkdv_stream32_kernel(co
     const int Cdim = H * hd;
     const int G = (int)gridDim.x;
     const int NCH = (N + ST_KC - 1) / ST_KC;
-    const int vid = (G & 7) == 0 ? ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
-    const int my_items = vid < items ? (items - vid + G - 1) / G : 0;
+    const int vid = st16_vid(G);
+    const int my_items = st16_my_items(vid, items, G);
     char* const fring = smem + ST_RING * slot_bytes;
     const int ncw = KB >> 5;
     if (wave >= ncw) {
-        st16_bwd_loader<HD, true, 8>(smem, fring, wave, lane, 8 - ncw >= 4 ? 4 : 8 - ncw >= 2 ? 2 : 1, my_items * NCH, NCH, vid, G, nkb, H, N, hd, qkv,
-                                     ld, 0, dout, lddo, 0, lse, delta);
+        st16_loader<HD, true, 8>(smem, fring, wave, lane, 8 - ncw >= 4 ? 4 : 8 - ncw >= 2 ? 2 : 1, my_items * NCH, NCH, vid, G, nkb, H, N, hd, qkv,
+                                 ld, 0, dout, lddo, 0, lse, delta);
         return;
     }
     char* scr = fring + FRING + wave * SCR;
     const float sl = scale * LOG2E;
-    int koff[NKS];
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) koff[ks] = l15 * R::RB + 16 * ((4 * ks + g) ^ r16_swz<R::CPR>(l15));
-    int troff[NDT];
-    {
-        const int rr = 4 * g + (l15 >> 2);
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-            troff[dt] = rr * R::RB + 16 * ((2 * dt + ((l15 & 3) >> 1)) ^ r16_swz<R::CPR>(rr)) + 8 * (l15 & 1);
-    }
-    auto rowread = [&](const char* arr, int t, bf16x8 (&dst)[NKS]) {
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) dst[ks] = *reinterpret_cast<const bf16x8*>(arr + 16 * t * R::RB + koff[ks]);
-    };
-    auto trread = [&](const char* arr, int kk, int dt) {
-        union { bf16x4 q4[2]; bf16x8 v; } a;
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-            a.q4[r] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)((uint32_t)(uintptr_t)arr + (32 * kk + 16 * r) * R::RB + troff[dt]));
-        return a.v;
-    };
+    const R16Frags<HD> fr(l15, g);
     const f32x4 zero4f = {0.f, 0.f, 0.f, 0.f};
     // the wave's own K / V rows (two 16-key tiles): the next item's are fetched under this item's last chunk
     u32x4 kn[2][NKS], vn[2][NKS];
@@ -1857,14 +1642,10 @@ __global__ __launch_bounds__(ST32_THREADS) void attn_bwd_dkdv_stream32_kernel(co
         const int k0 = kb * KB + 32 * wave;
         bf16x8 kf[2][NKS], vf[2][NKS];
 #pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-                const bool ok = 32 * ks + 8 * g < hd;
-                const u32x4 kv = ok ? kn[r][ks] : zero4(), vv = ok ? vn[r][ks] : zero4();
-                kf[r][ks] = *reinterpret_cast<const bf16x8*>(&kv);
-                vf[r][ks] = *reinterpret_cast<const bf16x8*>(&vv);
-            }
+        for (int r = 0; r < 2; ++r) {
+            r16_take<HD>(kn[r], g, hd, kf[r]);
+            r16_take<HD>(vn[r], g, hd, vf[r]);
+        }
         f32x4 dk[2][NDT], dv[2][NDT];
 #pragma unroll
         for (int r = 0; r < 2; ++r)
@@ -1880,7 +1661,7 @@ __global__ __launch_bounds__(ST32_THREADS) void attn_bwd_dkdv_stream32_kernel(co
             auto sdp = [&](int qq, f32x4 (&s)[2][2], f32x4 (&dp)[2][2]) {      // [query tile of the pair][key tile]
                 {
                     bf16x8 qa[2][NKS];
-                    rowread(Qb, 2 * qq, qa[0]); rowread(Qb, 2 * qq + 1, qa[1]);
+                    fr.rowread(Qb, 2 * qq, qa[0]); fr.rowread(Qb, 2 * qq + 1, qa[1]);
 #pragma unroll
                     for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
@@ -1894,7 +1675,7 @@ __global__ __launch_bounds__(ST32_THREADS) void attn_bwd_dkdv_stream32_kernel(co
                 }
                 {
                     bf16x8 da[2][NKS];
-                    rowread(Db, 2 * qq, da[0]); rowread(Db, 2 * qq + 1, da[1]);
+                    fr.rowread(Db, 2 * qq, da[0]); fr.rowread(Db, 2 * qq + 1, da[1]);
 #pragma unroll
                     for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
@@ -1919,7 +1700,7 @@ __global__ __launch_bounds__(ST32_THREADS) void attn_bwd_dkdv_stream32_kernel(co
                 __builtin_amdgcn_sched_barrier(0);
                 bf16x8 td[NDT], tq[NDT];
 #pragma unroll
-                for (int dt = 0; dt < NDT; ++dt) td[dt] = trread(Db, qq, dt);
+                for (int dt = 0; dt < NDT; ++dt) td[dt] = fr.trread(Db, qq, dt);
                 f32x4 L[2], D[2];
 #pragma unroll
                 for (int tt = 0; tt < 2; ++tt) {
@@ -1941,7 +1722,7 @@ __global__ __launch_bounds__(ST32_THREADS) void attn_bwd_dkdv_stream32_kernel(co
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int dt = 0; dt < NDT; ++dt) tq[dt] = trread(Qb, qq, dt);      // (lands under the dV products)
+                for (int dt = 0; dt < NDT; ++dt) tq[dt] = fr.trread(Qb, qq, dt);      // (lands under the dV products)
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt)

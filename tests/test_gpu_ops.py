@@ -454,12 +454,14 @@ def test_attention_generic_is_the_qkv_kernels(dev, N, hd, dt, p_drop):
         assert torch.equal(dqkv, res["dqkv"])
 
 
-@pytest.mark.parametrize("direction,N,form", [("fwd", 300, MID), ("fwd", 545, CHUNK), ("bwd", 545, CHUNK)])
+@pytest.mark.parametrize("direction,N,form", [("fwd", 300, MID), ("fwd", 545, CHUNK), ("bwd", 545, CHUNK), ("fwd", 130, RING16),
+                                              ("bwd", 130, RING16)])
 def test_attention_route_padded_output_stride(dev, direction, N, form):
     """a row stride with 4 pad columns (the C entry; the Python wrappers pass dense strides): not a multiple of 8, which the streaming
     kernels ask for.  Forward, ld_out = C + 4: at N = 300, head_dim 64 the call stays on the mid kernel, at N = 545 on the chunk kernel
     (3 chunks, the last of 33 rows), where a dense output goes to the streaming one.  Backward, ld_dqkv = 3C + 4 with a dense out:
-    the two chunk kernels.  These are the only calls that launch the chunk kernels at head_dim 64."""
+    the two chunk kernels.  These are the only calls that launch the chunk kernels at head_dim 64.  At N = 130 both directions stay on
+    the ring form, the only special form whose 16-byte output stores then run on rows that are 8-byte but not 16-byte aligned."""
     B, H, hd = 2, 2, 64
     C = H * hd
     scale = hd ** -0.5

@@ -34,7 +34,12 @@ CASES = [(64, 64, "bf16", 0.0, 2, 2), (64, 64, "fp32", 0.0, 2, 2), (65, 64, "bf1
          (65, 24, "bf16", 0.1, 2, 2), (129, 48, "bf16", 0.1, 2, 2), (130, 64, "bf16", 0.5, 2, 2), (257, 72, "bf16", 0.0, 2, 2),
          (70, 96, "bf16", 0.0, 2, 2), (130, 128, "bf16", 0.1, 2, 2),
          # the 32-row kernels: resident at HD = 32, a last chunk of 33 rows (masked two-sub-tile tail), three full chunks (no tail step)
-         (250, 24, "bf16", 0.0, 2, 2), (545, 32, "bf16", 0.0, 1, 2), (768, 24, "bf16", 0.0, 1, 1)]
+         (250, 24, "bf16", 0.0, 2, 2), (545, 32, "bf16", 0.0, 1, 2), (768, 24, "bf16", 0.0, 1, 1),
+         # the 16-row kernels: six ring sub-tiles (N = 161); enough (batch, head) pairs that a workgroup walks more than one item, in the
+         # ring form (N = 197, 100) and the streaming one (N = 300, 600); head_dim below the template width in the ring form (N = 100)
+         # and in the streaming kernels (N = 577, 600); 176-row blocks, which take four loader waves (N = 700)
+         (161, 64, "bf16", 0.0, 2, 2), (197, 64, "bf16", 0.0, 40, 12), (100, 48, "bf16", 0.0, 30, 12), (300, 64, "bf16", 0.0, 40, 12),
+         (577, 40, "bf16", 0.0, 3, 2), (600, 48, "bf16", 0.0, 24, 12), (700, 64, "bf16", 0.0, 9, 4)]
 DT = {"bf16": torch.bfloat16, "fp32": torch.float32}
 # me_attention_qkv_*: (Nq, Nk, causal) -- causal N and two-length pairs on every edge of the tiling (one row, a 64-key tile and + 1, a
 # 128-query block + 1, two blocks).  qkv_cases() gives each shape two head_dims, both layouts and both dropout settings, per dtype
