@@ -835,6 +835,58 @@ int me_upsample2x_rows(const void* y4, int y4_dtype, const float* bias, const vo
                        int B, int h, int w, int C, void* stream);
 int me_upsample2x_rows_bwd(const void* dout, int dout_dtype, void* dy4, int dy4_dtype, int B, int h, int w, int C, void* stream);
 
+/* ------------------------------------------------------------------ audio front end: waveform -> Kaldi log-mel filterbank
+ * What Audio/src/dataloader.py:98-205 does per clip on the CPU -- torchaudio.compliance.kaldi.fbank(htk_compat=True,
+ * use_energy=False, window_type='hanning', dither=0.0, frame_shift=10), mix-up, cut / pad to target_length, the SpecAug bands and
+ * (x - mean) / (2 std) -- for a batch, on the device, in fp32.  All pointers are DEVICE pointers.
+ *   wave [B, n_samples] fp32 (row stride ld_wave); lengths int32 [B] or NULL (every clip has n_samples); a length is clamped to
+ *   [0, n_samples] and samples at or past it are never read.  wave2 / lengths2 / lam (fp32 [B]): the mix-up partner, NULL for none.
+ *   out [B, target_length, n_mel] ME_F32 or ME_BF16: row stride ld_out, clip stride target_length * ld_out.
+ * Per clip b, len = its length:
+ *   1. x = wave[:len] - mean(wave[:len]).  With wave2: a = wave - mean(wave), c = wave2[:len2] - mean(wave2[:len2]) zero-padded or
+ *      cut to len, x = lam a + (1 - lam) c, x -= mean(x).
+ *   2. T = 1 + (len - win) / shift frames (0 when len < win), frame t = x[t shift .. t shift + win).
+ *   3. per frame: subtract its mean; f[i] -= 0.97 f[i - 1] (f[-1] := f[0]); multiply by window [win]; zero-pad to `padded`.
+ *   4. power spectrum |rfft|^2, bins 0 .. padded / 2 - 1 (the Nyquist bin carries no filter weight and is not formed).
+ *   5. energy of filter m = sum over i < mel_range[m][1] of mel_weight[m][i] * power[mel_range[m][0] + i], i ascending.
+ *   6. raw = log(max(energy, 1.1920929e-07)).
+ *   7. rows T .. target_length - 1 hold raw = 0; frames from target_length on are not computed.
+ *   8. raw = 0 where freq_mask[b][0] <= m < freq_mask[b][1] or time_mask[b][0] <= t < time_mask[b][1] (int32 [B, 2], NULL for none).
+ *   9. normalize != 0: out = (raw - norm_mean) / (2 norm_std) for every cell, the padded and masked ones too; else out = raw.
+ * Tables are the caller's (the library keeps no state): window fp32 [win]; twiddle fp32 [padded, 2] = (cos, -sin)(2 pi n / padded);
+ * mel_range int32 [n_mel, 2] = (first bin, count) with first + count <= padded / 2 and count <= mel_ld (values outside are clamped
+ * for the read); mel_weight fp32 [n_mel, mel_ld].
+ * Form: a workgroup owns ME_FBANK_RUN consecutive output rows of one clip and stages their span of samples in LDS once; a wave
+ * transforms one frame at a time as a padded / 2 point complex FFT (radix 4, twiddles from the table) in LDS plus the real-input
+ * split.  The means are sums over 4096-sample chunks (me_fbank_workspace_bytes) added in a fixed order: no float atomics, two
+ * runs are bit-identical.  Geometries: padded = 512 or 256, win <= padded, n_mel <= 256, n_mel * mel_ld <= 8192: ME_ERR_UNSUPPORTED
+ * otherwise.  B = 0 or target_length = 0: ME_OK, nothing is touched.  workspace: 4-byte aligned. */
+#define ME_FBANK_RUN 32
+typedef struct me_fbank_desc {
+    const float* wave;
+    int64_t ld_wave;
+    const int32_t* lengths;
+    const float* wave2;
+    int64_t ld_wave2;
+    const int32_t* lengths2;
+    const float* lam;
+    int32_t B, n_samples, n_samples2;
+    int32_t win, shift, padded, n_mel, mel_ld, target_length;
+    const float* window;
+    const float* twiddle;
+    const int32_t* mel_range;
+    const float* mel_weight;
+    const int32_t* freq_mask;
+    const int32_t* time_mask;
+    int32_t normalize;
+    float norm_mean, norm_std;
+    void* out;
+    int32_t out_dtype;
+    int64_t ld_out;
+} me_fbank_desc;
+size_t me_fbank_workspace_bytes(const me_fbank_desc* d);
+int me_fbank(const me_fbank_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ data-parallel gradient exchange
  * The ONE exchange step of batch-sharded data parallelism: a sum all-reduce per flat gradient bucket over RCCL (xGMI
  * inside a node).  Replaces _allreduce_coalesced (Image/segmentation/mmseg_custom/core/utils/dist_utils.py:14-35:

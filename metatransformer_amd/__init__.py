@@ -19,6 +19,7 @@ from .timeseries import AttentionLayer, Decoder, DecoderLayer, Forecaster, FullA
 from .hyperspectral import HyperSpectralClassifier, HyperSpectralEmbed, neighborhood_tokens  # noqa: F401
 from .video_mae import (PretrainVisionTransformer, PretrainVisionTransformerDecoder, PretrainVisionTransformerEncoder,  # noqa: F401
                         mae_reconstruction_loss)
+from .audio import ASTModel, KaldiFbank, fbank_tables, mel_filterbank, specaug_bands  # noqa: F401
 
 __all__ = ["Block", "Attention", "Mlp", "build_encoder", "set_fp32_mode", "encoder_flops_per_sample", "encoder_forward_inference", "Data2Seq", "PatchEmbed",
            "AcousticPatchEmbed", "VideoPatchEmbed", "DataEmbedding", "MetaEncError", "load_library",
@@ -29,4 +30,5 @@ __all__ = ["Block", "Attention", "Mlp", "build_encoder", "set_fp32_mode", "encod
            "conv3x3_rows", "max_pool3x3s2_rows", "resize_rows_batched", "conv_transpose2x2_rows", "SpatialPriorModule", "ViTAdapter",
            "GraphFeatureTokenizer", "FullAttention", "AttentionLayer", "DecoderLayer", "Decoder", "Forecaster",
            "HyperSpectralEmbed", "HyperSpectralClassifier", "neighborhood_tokens",
-           "PretrainVisionTransformerEncoder", "PretrainVisionTransformerDecoder", "PretrainVisionTransformer", "mae_reconstruction_loss"]
+           "PretrainVisionTransformerEncoder", "PretrainVisionTransformerDecoder", "PretrainVisionTransformer", "mae_reconstruction_loss",
+           "KaldiFbank", "ASTModel", "mel_filterbank", "fbank_tables", "specaug_bands"]

@@ -88,6 +88,16 @@ class HsiDesc(ctypes.Structure):
                 + [(n, c_int32) for n in ("B", "patch", "band_patch")])
 
 
+class FbankDesc(ctypes.Structure):
+    """Mirror of ``struct me_fbank_desc`` (include/metaenc.h)."""
+    _fields_ = ([("wave", c_void_p), ("ld_wave", c_int64), ("lengths", c_void_p), ("wave2", c_void_p), ("ld_wave2", c_int64),
+                 ("lengths2", c_void_p), ("lam", c_void_p)]
+                + [(n, c_int32) for n in ("B", "n_samples", "n_samples2", "win", "shift", "padded", "n_mel", "mel_ld", "target_length")]
+                + [(n, c_void_p) for n in ("window", "twiddle", "mel_range", "mel_weight", "freq_mask", "time_mask")]
+                + [("normalize", c_int32), ("norm_mean", c_float), ("norm_std", c_float), ("out", c_void_p), ("out_dtype", c_int32),
+                   ("ld_out", c_int64)])
+
+
 class AttnQkvDesc(ctypes.Structure):
     """Mirror of ``struct me_attn_qkv_desc`` (include/metaenc.h)."""
     _fields_ = ([("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("ld_q", c_int64), ("ld_k", c_int64), ("ld_v", c_int64),
@@ -254,6 +264,8 @@ SIGNATURES = {
     "me_hsi_embed_wgrad_workspace": (c_size_t, [POINTER(HsiDesc), c_int]),
     "me_hsi_embed_wgrad": (c_int, [POINTER(HsiDesc), c_void_p, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_float, c_void_p, c_size_t, c_void_p]),
+    "me_fbank_workspace_bytes": (c_size_t, [POINTER(FbankDesc)]),
+    "me_fbank": (c_int, [POINTER(FbankDesc), c_void_p, c_size_t, c_void_p]),
     "me_tubelet_gather": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64] + [c_int] * 9 + [c_void_p]),
     "me_take_rows": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p]),
     "me_mae_assemble_fwd": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
