@@ -2110,21 +2110,21 @@ template <int HD> int launch_fwd_small(const AttnCall& c) {
     const int64_t items = (int64_t)c.B * c.H;
     int per_cu = (int)(LDS_PER_CU / smem);
     per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    return attn_launch<attn_fwd_small_kernel<HD>>("me_attention_fwd(small)", dim3(persistent_grid(items, per_cu)), SM_THREADS, smem, lds(SM_MAXN),
+    return launch_kernel<attn_fwd_small_kernel<HD>>("me_attention_fwd(small)", dim3(persistent_grid(items, per_cu)), SM_THREADS, smem, lds(SM_MAXN),
                                                   c.stream, p.qkv, c.ld, p.out, c.ldo, c.lse, c.N, c.H, c.hd, c.scale, (int)items);
 }
 template <int HD> int launch_bwd_small(const AttnCall& c) {
     typedef Cfg<bf16_t, HD> C;
     const auto p = c.as<bf16_t>();
     auto lds = [](int n) { return (size_t)4 * ((n + 31) / 32 * 32) * C::RROW + 2 * SM_MAXN * sizeof(float); };      // {Q, K, V, dO} + lse, delta
-    return attn_launch<attn_bwd_small_kernel<HD>>("me_attention_bwd(small)", dim3(c.H, c.B), SM_THREADS, lds(c.N), lds(SM_MAXN), c.stream, p.qkv, c.ld,
+    return launch_kernel<attn_bwd_small_kernel<HD>>("me_attention_bwd(small)", dim3(c.H, c.B), SM_THREADS, lds(c.N), lds(SM_MAXN), c.stream, p.qkv, c.ld,
                                                   p.out, c.ldo, p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
 }
 template <int HD, int NS> int launch_fwd_ring16(const AttnCall& c) {
     constexpr size_t smem = (size_t)4 * NS * 32 * RCfg<HD>::RB + (R16_THREADS / 64) * 16 * Cfg<bf16_t, HD>::RROW;
     const auto p = c.as<bf16_t>();
     const int64_t items = (int64_t)c.B * c.H;
-    return attn_launch<attn_fwd_ring16_kernel<HD, NS>>("me_attention_fwd(ring16)", dim3(persistent_grid(items)), R16_THREADS, smem, smem, c.stream, p.qkv,
+    return launch_kernel<attn_fwd_ring16_kernel<HD, NS>>("me_attention_fwd(ring16)", dim3(persistent_grid(items)), R16_THREADS, smem, smem, c.stream, p.qkv,
                                                        c.ld, p.out, c.ldo, c.lse, c.N, c.H, c.hd, c.scale, (int)items);
 }
 template <int HD, int NS> int launch_bwd_ring16(const AttnCall& c) {
@@ -2133,7 +2133,7 @@ template <int HD, int NS> int launch_bwd_ring16(const AttnCall& c) {
     unsigned* ctr = me_work_counters(c.stream);      // (null while capturing: static schedule)
     if (ctr) ctr += 1;                                // word 1 of the stream's set (word 0: the resident GEMM, XCD 0)
     const int64_t items = (int64_t)c.B * c.H;
-    return attn_launch<attn_bwd_ring16_kernel<HD, NS>>("me_attention_bwd(ring16)", dim3(persistent_grid(items)), R16_THREADS, smem, smem, c.stream, p.qkv,
+    return launch_kernel<attn_bwd_ring16_kernel<HD, NS>>("me_attention_bwd(ring16)", dim3(persistent_grid(items)), R16_THREADS, smem, smem, c.stream, p.qkv,
                                                        c.ld, p.out, c.ldo, p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale, (int)items,
                                                        ctr);
 }
@@ -2141,7 +2141,7 @@ template <int HD> int launch_fwd_stream16(const AttnCall& c, const AttnRoute& r)
     constexpr size_t smem = (size_t)ST_RING * 2 * ST_KC * RCfg<HD>::RB + (R16_THREADS / 64) * 16 * Cfg<bf16_t, HD>::RROW;
     const auto p = c.as<bf16_t>();
     const int64_t items = (int64_t)c.B * c.H * r.nblk;
-    return attn_launch<attn_fwd_stream16_kernel<HD>>("me_attention_fwd(stream16)", dim3(persistent_grid(items)), R16_THREADS, smem, smem, c.stream, p.qkv, c.ld,
+    return launch_kernel<attn_fwd_stream16_kernel<HD>>("me_attention_fwd(stream16)", dim3(persistent_grid(items)), R16_THREADS, smem, smem, c.stream, p.qkv, c.ld,
                                                      p.out, c.ldo, c.lse, c.N, c.H, c.hd, c.scale, r.rows, r.nblk, (int)items);
 }
 template <int HD> int launch_bwd_stream16(const AttnCall& c, const AttnRoute& r) {
@@ -2152,44 +2152,44 @@ template <int HD> int launch_bwd_stream16(const AttnCall& c, const AttnRoute& r)
     const auto p = c.as<bf16_t>();
     const int64_t items = (int64_t)c.B * c.H * r.nblk;
     const dim3 grid(persistent_grid(items));
-    if (int rc = attn_launch<attn_bwd_dq_stream16_kernel<HD>>("me_attention_bwd(dq stream16)", grid, R16_THREADS, smem1, smem1, c.stream, p.qkv, c.ld, p.out,
+    if (int rc = launch_kernel<attn_bwd_dq_stream16_kernel<HD>>("me_attention_bwd(dq stream16)", grid, R16_THREADS, smem1, smem1, c.stream, p.qkv, c.ld, p.out,
                                                               c.ldo, p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale, r.rows, r.nblk,
                                                               (int)items))
         return rc;
     if (!r.dkdv32)
-        return attn_launch<attn_bwd_dkdv_stream16_kernel<HD>>("me_attention_bwd(dkdv stream16)", grid, R16_THREADS, smem2, smem2, c.stream, p.qkv, c.ld, p.dout,
+        return launch_kernel<attn_bwd_dkdv_stream16_kernel<HD>>("me_attention_bwd(dkdv stream16)", grid, R16_THREADS, smem2, smem2, c.stream, p.qkv, c.ld, p.dout,
                                                               c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale, r.krows, r.nblk, (int)items);
-    return attn_launch<attn_bwd_dkdv_stream32_kernel<HD>>("me_attention_bwd(dkdv stream32)", grid, ST32_THREADS, smem3, smem3, c.stream, p.qkv, c.ld, p.dout,
+    return launch_kernel<attn_bwd_dkdv_stream32_kernel<HD>>("me_attention_bwd(dkdv stream32)", grid, ST32_THREADS, smem3, smem3, c.stream, p.qkv, c.ld, p.dout,
                                                           c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale, r.krows, r.nblk, (int)items);
 }
 template <int HD> int launch_fwd_mid(const AttnCall& c) {
     typedef Cfg<bf16_t, HD> C;
     const auto p = c.as<bf16_t>();
     auto lds = [](int n) { return (size_t)2 * ((n + 31) / 32 * 32) * C::RROW; };      // {K, V}
-    return attn_launch<attn_fwd_mid_kernel<HD, 512, MD_MAXN>>("me_attention_fwd(mid)", dim3(c.H, c.B), 512, lds(c.N), lds(MD_MAXN), c.stream, p.qkv, c.ld,
+    return launch_kernel<attn_fwd_mid_kernel<HD, 512, MD_MAXN>>("me_attention_fwd(mid)", dim3(c.H, c.B), 512, lds(c.N), lds(MD_MAXN), c.stream, p.qkv, c.ld,
                                                               p.out, c.ldo, c.lse, c.N, c.H, c.hd, c.scale);
 }
 template <int HD> int launch_bwd_mid(const AttnCall& c) {
     typedef Cfg<bf16_t, HD> C;
     const auto p = c.as<bf16_t>();
     auto lds = [](int n) { return (size_t)2 * ((n + 31) / 32 * 32) * C::RROW + 2 * MD_MAXN * sizeof(float); };      // {K, V} then {Q, dO} + lse, delta
-    return attn_launch<attn_bwd_mid_kernel<HD, 512, MD_MAXN>>("me_attention_bwd(mid)", dim3(c.H, c.B), 512, lds(c.N), lds(MD_MAXN), c.stream, p.qkv, c.ld,
+    return launch_kernel<attn_bwd_mid_kernel<HD, 512, MD_MAXN>>("me_attention_bwd(mid)", dim3(c.H, c.B), 512, lds(c.N), lds(MD_MAXN), c.stream, p.qkv, c.ld,
                                                               p.out, c.ldo, p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
 }
 template <int HD> int launch_fwd_chunk(const AttnCall& c) {
     const size_t smem = (size_t)2 * CH_ROWS * Cfg<bf16_t, HD>::RROW;
     const auto p = c.as<bf16_t>();
-    return attn_launch<attn_fwd_chunk_kernel<HD>>("me_attention_fwd(chunk)", dim3((c.N + CH_ROWS - 1) / CH_ROWS, c.H, c.B), SM_THREADS, smem, smem, c.stream,
+    return launch_kernel<attn_fwd_chunk_kernel<HD>>("me_attention_fwd(chunk)", dim3((c.N + CH_ROWS - 1) / CH_ROWS, c.H, c.B), SM_THREADS, smem, smem, c.stream,
                                                   p.qkv, c.ld, p.out, c.ldo, c.lse, c.N, c.H, c.hd, c.scale);
 }
 template <int HD> int launch_bwd_chunk(const AttnCall& c) {
     const size_t smem1 = (size_t)2 * CH_ROWS * Cfg<bf16_t, HD>::RROW, smem2 = smem1 + 2 * CH_ROWS * sizeof(float);
     const auto p = c.as<bf16_t>();
     const dim3 grid((c.N + CH_ROWS - 1) / CH_ROWS, c.H, c.B);
-    if (int rc = attn_launch<attn_bwd_dq_chunk_kernel<HD>>("me_attention_bwd(dq chunk)", grid, SM_THREADS, smem1, smem1, c.stream, p.qkv, c.ld, p.out, c.ldo,
+    if (int rc = launch_kernel<attn_bwd_dq_chunk_kernel<HD>>("me_attention_bwd(dq chunk)", grid, SM_THREADS, smem1, smem1, c.stream, p.qkv, c.ld, p.out, c.ldo,
                                                            p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale))
         return rc;
-    return attn_launch<attn_bwd_dkdv_chunk_kernel<HD>>("me_attention_bwd(dkdv chunk)", grid, SM_THREADS, smem2, smem2, c.stream, p.qkv, c.ld, p.dout, c.lddo,
+    return launch_kernel<attn_bwd_dkdv_chunk_kernel<HD>>("me_attention_bwd(dkdv chunk)", grid, SM_THREADS, smem2, smem2, c.stream, p.qkv, c.ld, p.dout, c.lddo,
                                                        c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
 }
 

@@ -55,13 +55,3 @@ int launch_attn_delta(const void* out, int64_t ldo, const void* dout, int64_t ld
 // an ME_BF16X3 Block runs its attention as three bf16 products (attention_x3.hip) at this shape, on the exact-fp32 kernels otherwise
 // (N <= 64: the exact-fp32 one-workgroup-per-head kernels, attention_tiny.hip, are faster and exact)
 inline bool attn_x3_takes(int hd, int N) { return hd == 64 && N > 64; }
-
-// Launch of one kernel instantiation: its dynamic-LDS limit (lds_max: the most any call asks of it) is raised once per device.
-template <auto Kernel, typename... Args>
-int attn_launch(const char* label, dim3 grid, int threads, size_t lds, size_t lds_max, hipStream_t stream, Args... args) {
-    static OncePerDevice once;
-    if (once.need()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-    hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, stream, args...);
-    ME_CHECK_LAUNCH(label);
-    return ME_OK;
-}

@@ -481,7 +481,7 @@ dim3 row_blocks(int N, const me_attn_qkv_desc& d) { return dim3((N + QPB - 1) / 
 template <typename T, int HD> int launch_fwd(const me_attn_qkv_desc& d, hipStream_t stream) {
     typedef Cfg<T, HD> C;
     const size_t smem = C::R_BYTES + (C::T_BYTES > C::R_BYTES ? C::T_BYTES : C::R_BYTES);   // V tile: transposed (fp32) or row-major (bf16)
-    return attn_launch<attn_qkv_fwd_kernel<T, HD>>("attention tiled fwd", row_blocks(d.Nq, d), AT_THREADS, smem, smem, stream, d);
+    return launch_kernel<attn_qkv_fwd_kernel<T, HD>>("attention tiled fwd", row_blocks(d.Nq, d), AT_THREADS, smem, smem, stream, d);
 }
 template <typename T, int HD> int launch_bwd(const me_attn_qkv_desc& d, hipStream_t stream) {
     typedef Cfg<T, HD> C;
@@ -489,7 +489,7 @@ template <typename T, int HD> int launch_bwd(const me_attn_qkv_desc& d, hipStrea
     const size_t smem1 = 2 * C::R_BYTES + 2 * TB + 2 * KVT * sizeof(float);
     const size_t smem2 = 2 * C::R_BYTES + TB;
     auto dkdv = [&](auto DB0, auto NDBO) {
-        return attn_launch<attn_qkv_bwd_dkdv_kernel<T, HD, DB0(), NDBO()>>("attention tiled bwd (dkdv)", row_blocks(d.Nk, d), AT_THREADS, smem1, smem1,
+        return launch_kernel<attn_qkv_bwd_dkdv_kernel<T, HD, DB0(), NDBO()>>("attention tiled bwd (dkdv)", row_blocks(d.Nk, d), AT_THREADS, smem1, smem1,
                                                                            stream, d);
     };
     // fp32 at head_dim > 64: two launches of two d blocks each, no scratch, S and dP formed in both -- against ONE launch of
@@ -502,12 +502,12 @@ template <typename T, int HD> int launch_bwd(const me_attn_qkv_desc& d, hipStrea
     } else {
         if (int rc = dkdv(Int<0>(), Int<C::NDB>())) return rc;
     }
-    return attn_launch<attn_qkv_bwd_dq_kernel<T, HD>>("attention tiled bwd (dq)", row_blocks(d.Nq, d), AT_THREADS, smem2, smem2, stream, d);
+    return launch_kernel<attn_qkv_bwd_dq_kernel<T, HD>>("attention tiled bwd (dq)", row_blocks(d.Nq, d), AT_THREADS, smem2, smem2, stream, d);
 }
 // bf16 delta of me_attention_qkv_bwd: from the tiles (qrows_bwd, which says why)
 template <int HD> int launch_qkv_delta_bf16(const me_attn_qkv_desc& d, hipStream_t stream) {
     constexpr size_t smem = 2 * Cfg<bf16_t, HD>::R_BYTES;
-    return attn_launch<attn_qkv_delta_kernel<bf16_t, HD>>("me_attention_qkv_bwd(delta)", row_blocks(d.Nq, d), AT_THREADS, smem, smem, stream, d);
+    return launch_kernel<attn_qkv_delta_kernel<bf16_t, HD>>("me_attention_qkv_bwd(delta)", row_blocks(d.Nq, d), AT_THREADS, smem, smem, stream, d);
 }
 
 // f(Int<HD>) for the instantiated head width

@@ -320,10 +320,10 @@ template <typename T, int HD, int NMAX, bool BWD> int launch(const AttnCall& c) 
     const auto p = c.as<T>();
     const dim3 grid((unsigned)((int64_t)c.B * c.H));
     if constexpr (BWD)
-        return attn_launch<attn_tiny_bwd_kernel<T, HD, NMAX>>("me_attention_bwd(tiny)", grid, NMAX * 4, C::BWD_LDS, C::BWD_LDS, c.stream, p.qkv, c.ld, p.out, c.ldo,
+        return launch_kernel<attn_tiny_bwd_kernel<T, HD, NMAX>>("me_attention_bwd(tiny)", grid, NMAX * 4, C::BWD_LDS, C::BWD_LDS, c.stream, p.qkv, c.ld, p.out, c.ldo,
                                                               p.dout, c.lddo, c.lse, c.delta, p.dqkv, c.lddq, c.N, c.H, c.hd, c.scale);
     else
-        return attn_launch<attn_tiny_fwd_kernel<T, HD, NMAX>>("me_attention_fwd(tiny)", grid, NMAX * 4, C::FWD_LDS, C::FWD_LDS, c.stream, p.qkv, c.ld, p.out, c.ldo,
+        return launch_kernel<attn_tiny_fwd_kernel<T, HD, NMAX>>("me_attention_fwd(tiny)", grid, NMAX * 4, C::FWD_LDS, C::FWD_LDS, c.stream, p.qkv, c.ld, p.out, c.ldo,
                                                               c.lse, c.N, c.H, c.hd, c.scale);
 }
 // element type, head width (32 / 64) and token capacity (16 / 32 / 64) of the instantiation a call takes

@@ -58,6 +58,15 @@ struct OncePerDevice {
         return true;
     }
 };
+// Launch of one kernel instantiation: its dynamic-LDS limit (lds_max: the most any call asks of it) is raised once per device.
+template <auto Kernel, typename... Args>
+int launch_kernel(const char* label, dim3 grid, int threads, size_t lds, size_t lds_max, hipStream_t stream, Args... args) {
+    static OncePerDevice once;
+    if (once.need()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+    hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, stream, args...);
+    ME_CHECK_LAUNCH(label);
+    return ME_OK;
+}
 
 // CUs of the current device (the resident / persistent kernel forms launch one workgroup, or a few, per CU); asked once per translation unit
 static inline int device_cus() {

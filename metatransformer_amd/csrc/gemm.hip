@@ -144,11 +144,7 @@ __global__ __launch_bounds__(NT) void gemm_g128_kernel(const GemmParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
 
-    // XCD-aware bijective remap: block b runs on XCD b % 8; give every XCD a contiguous range of tiles so
-    // that the blocks sharing an activation row-panel hit the same L2.
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int wgid = xcd_major_wgid(blockIdx.x, gridDim.x);      // (the blocks that share an activation row panel hit the same L2)
     const int tm = wgid / p.tiles_n, tn = wgid % p.tiles_n;
     const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
 
@@ -220,15 +216,8 @@ __global__ __launch_bounds__(NT) void gemm_g128_kernel(const GemmParams p) {
 template <typename T, bool TN>
 int launch_g128(const GemmParams& p, hipStream_t stream) {
     const size_t lds = 4 * TILE_BYTES;   // 64 KiB
-    static OncePerDevice once;
-    if (once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g128_kernel<T, TN>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
     const int64_t nblk = (int64_t)p.tiles_m * p.tiles_n;
-    hipLaunchKernelGGL((gemm_g128_kernel<T, TN>), dim3((unsigned)nblk), dim3(NT), lds, stream, p);
-    ME_CHECK_LAUNCH("me_gemm(g128)");
-    return ME_OK;
+    return launch_kernel<gemm_g128_kernel<T, TN>>("me_gemm(g128)", dim3((unsigned)nblk), NT, lds, lds, stream, p);
 }
 
 // fold the partial column sums of A (fixed order: deterministic).  The LAST workgroups of the grid take 32 columns each,

@@ -41,9 +41,7 @@ __global__ __launch_bounds__((BM == 64 ? 256 : BM * 2)) __attribute__((amdgpu_wa
     const int wr = wave >> 2, wc = wave & 3;                        // wave row (BM = 256 only) / column group
     const int l31 = lane & 31, h = lane >> 5;
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int wgid = xcd_major_wgid(blockIdx.x, gridDim.x);
     const int tm = wgid / p.tiles_n, tn = wgid % p.tiles_n;
     const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
 
@@ -345,15 +343,8 @@ template <int BM, int BN, bool TN, int EPI>
 int launch2e(const GemmParams& p, hipStream_t stream) {
     typedef G2<BM, BN> G;
     const size_t lds = G::NSTAGE * G::STAGE;
-    static OncePerDevice once;
-    if (once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g2_kernel<BM, BN, TN, EPI>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
     dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)(p.split_k > 1 ? p.split_k : 1));
-    hipLaunchKernelGGL((gemm_g2_kernel<BM, BN, TN, EPI>), grid, dim3(G::NTH), lds, stream, p);
-    ME_CHECK_LAUNCH("me_gemm(g2)");
-    return ME_OK;
+    return launch_kernel<gemm_g2_kernel<BM, BN, TN, EPI>>("me_gemm(g2)", grid, G::NTH, lds, lds, stream, p);
 }
 
 template <int BM, int BN, bool TN>

@@ -85,11 +85,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         kt1 = kt0 + p.g3_ktp < nkt ? kt0 + p.g3_ktp : nkt;
     }
     s.wrap_kt = WRAP ? p.a_wrap_kt : 0;
-    g3_issue<0, WRAP>(s, src, 0, kt0); g3_issue<1, WRAP>(s, src, 0, kt0); g3_issue<2, WRAP>(s, src, 0, kt0); g3_issue<3, WRAP>(s, src, 0, kt0);
-    g3_issue<0, WRAP>(s, src, 1, kt0 + 1); g3_issue<1, WRAP>(s, src, 1, kt0 + 1); g3_issue<2, WRAP>(s, src, 1, kt0 + 1);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();
+    g3_prime<WRAP>(s, src, kt0, wr);
 
     // past the end of the K-range the source is a null descriptor (see g3_phase)
     const G3Src null = g3_null_src(p);
@@ -99,8 +95,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     g3_ktile<0, false, 0, false, 0, WRAP>(s, src, kt1 - 1, null, 0);
     g3_ktile<1, false, 0, false, 0, WRAP>(s, null, 0, null, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (wr == 0) __builtin_amdgcn_s_barrier();
+    g3_drain(wr);
     if (part >= 0) {
         // a part of a split tile: raw partial sums; the fold that follows the launch applies the real epilogue
         const int64_t row0 = (int64_t)(F / p.tiles_n) * G3_BM;
@@ -775,9 +770,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 // ---- wgrad: one (output tile, K-range) per workgroup; raw fp32 partial sums into slab blockIdx.y ... the deterministic
-// fold (splitk_reduce_kernel, gemm.hip) sums the slabs and applies the epilogue.  Work ids are split-major (id = split *
-// tiles + tile): the workgroups an XCD runs together read the SAME rows of dY and X at the same time, so every operand
-// row comes out of HBM once and is shared through that XCD's L2.
+// fold (splitk_reduce_kernel, gemm.hip) sums the slabs and applies the epilogue.  The plain form of the walk in gemm3_core.h
+// (g3_tn_part, g3_tn_walk).
 // The fold stays a separate launch: inside this kernel it measured 211 us per wgrad launch against 176 us for kernel + fold (round
 // 4) -- there the slab write-through, the wait for the tile row and the read-back are exposed one after the other on every CU.
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_g3tn_kernel(const GemmParams p) {
@@ -785,65 +779,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2;
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    const int tiles = p.tiles_m * p.tiles_n;
-    const int split = __builtin_amdgcn_readfirstlane(wgid / tiles);
-    const int tile = wgid - split * tiles;
-    const int tm = __builtin_amdgcn_readfirstlane(tile / p.tiles_n), tn = tile - tm * p.tiles_n;
-    const int64_t m0 = (int64_t)tm * G3_BM, n0 = (int64_t)tn * G3_BN;
+    const G3TnPart w = g3_tn_part(p, xcd_major_wgid(blockIdx.x, gridDim.x));
 
     G3State s;
     g3_init_lane_tn(s, p, smem, wave, lane);
     g3_zero(s);
-    const G3Src src = g3_make_src_tn(p, tm, tn);
-    const int kt0 = split * p.ksteps_per_split, kt1 = kt0 + p.ksteps_per_split;       // (an even count; tiles past K read zeros)
-
-    g3_issue<0>(s, src, 0, kt0); g3_issue<1>(s, src, 0, kt0); g3_issue<2>(s, src, 0, kt0); g3_issue<3>(s, src, 0, kt0);
-    g3_issue<0>(s, src, 1, kt0 + 1); g3_issue<1>(s, src, 1, kt0 + 1); g3_issue<2>(s, src, 1, kt0 + 1);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();
-    const G3Src null = g3_null_src(p);
-    // bias gradient: the N-tiles of one (M-tile, split) stage the same A rows -- they share the column sums pair by pair of
-    // K-tiles, round-robin (cs_turn = pairs until this workgroup's next turn)
-    const bool do_cs = p.colsum_ws != nullptr;
-    s.cs[0] = s.cs[1] = 0.f;
-    int cs_turn = do_cs ? tn : -1;
-    auto my_turn = [&]() {
-        if (!do_cs) return false;
-        const bool mine = cs_turn == 0;
-        cs_turn = mine ? p.tiles_n - 1 : cs_turn - 1;
-        return mine;
-    };
-    for (int kt = kt0; kt < kt1 - 2; kt += 2) {
-        const bool c = my_turn();
-        g3_ktile<0, true>(s, src, kt + 1, src, kt + 2, c);
-        g3_ktile<1, true>(s, src, kt + 2, src, kt + 3, c);
-    }
-    {
-        const bool c = my_turn();
-        g3_ktile<0, true>(s, src, kt1 - 1, null, 0, c);
-        g3_ktile<1, true>(s, null, 0, null, 0, c);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (wr == 0) __builtin_amdgcn_s_barrier();
-    if (do_cs) {
-        // lanes l, l+16, l+32, l+48 hold the four k-groups of column l & 15: fold, then one row of partial sums per
-        // (split, N-tile): [split * tiles_n + tn][M]
-        float c0 = s.cs[0], c1 = s.cs[1];
-        c0 += __shfl_xor(c0, 16, 64); c0 += __shfl_xor(c0, 32, 64);
-        c1 += __shfl_xor(c1, 16, 64); c1 += __shfl_xor(c1, 32, 64);
-        if (lane < 16) {
-            float* row = p.colsum_ws + ((int64_t)split * p.tiles_n + tn) * p.M;
-            const int wcol = wave & 3;
-            const int64_t ma = m0 + wr * 128 + wcol * 16 + lane, mb = ma + 64;
-            if (ma < p.M) row[ma] = c0;
-            if (mb < p.M) row[mb] = c1;
-        }
-    }
-    g3_epilogue<5>(p, s, m0, n0, lane, reinterpret_cast<float*>(p.C) + (int64_t)split * p.slab_stride, 0);
+    G3Turn turn = g3_tn_colsum_begin(s, p, w.tn);
+    g3_tn_walk(s, p, g3_make_src_tn(p, w.tm, w.tn), w.kt0, w.kt1, wr, turn);
+    g3_tn_store_colsum(p, s, (int64_t)w.split * p.tiles_n + w.tn, w.m0, lane);      // [split * tiles_n + tn][M]
+    g3_epilogue<5>(p, s, w.m0, w.n0, lane, reinterpret_cast<float*>(p.C) + (int64_t)w.split * p.slab_stride, 0);
 }
 
 
@@ -864,9 +808,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2;
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);       // neighbours in the id list share an XCD
+    const int wgid = xcd_major_wgid(blockIdx.x, gridDim.x);
     const int T = p.tiles_m * p.tiles_n, S = p.sk_levels, L1 = p.sk_l1, E = p.sk_wgs - S * T, Ul = p.sk_upt - S * L1;
     const int64_t TUl = (int64_t)T * Ul;
     const bool regular = wgid < S * T;
@@ -879,8 +821,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     G3State s;
     g3_init_lane_tn(s, p, smem, wave, lane);
-    const G3Src null = g3_null_src(p);
-    const bool do_cs = p.colsum_ws != nullptr;
     while (u0 < u1) {
         int tile, kt0, kt1, part, cs_row;
         int64_t ue;
@@ -900,50 +840,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int tm = __builtin_amdgcn_readfirstlane(tile / p.tiles_n), tn = tile - tm * p.tiles_n;
         cs_row = regular ? part * p.tiles_n + tn : S * p.tiles_n + (part - S) * p.tiles_n + tn;
         const int64_t m0 = (int64_t)tm * G3_BM, n0 = (int64_t)tn * G3_BN;
-        const G3Src src = g3_make_src_tn(p, tm, tn);
         g3_zero(s);
-        g3_issue<0>(s, src, 0, kt0); g3_issue<1>(s, src, 0, kt0); g3_issue<2>(s, src, 0, kt0); g3_issue<3>(s, src, 0, kt0);
-        g3_issue<0>(s, src, 1, kt0 + 1); g3_issue<1>(s, src, 1, kt0 + 1); g3_issue<2>(s, src, 1, kt0 + 1);
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (wr == 1) __builtin_amdgcn_s_barrier();
-        // column sums: the N-tiles of a tile row stage the same dY rows and share them pair by pair, round-robin -- inside a level all N-tiles walk
-        // the same K range; in the leftover the segments of different N-tiles are ragged, so the turn is tied to the ABSOLUTE pair index (pair k
-        // belongs to N-tile k % tiles_n: whichever of that tile's segments covers it takes it).  (A first version let the tn = 0 segments sum
-        // every pair: those workgroups became the launch's tail, +33 % -- profiles/r06_contention.txt.)
-        const bool cs_any = do_cs;
-        s.cs[0] = s.cs[1] = 0.f;
-        int cs_turn = regular ? tn : (tn + p.tiles_n - ((kt0 >> 1) % p.tiles_n)) % p.tiles_n;
-        auto my_turn = [&]() {
-            if (!cs_any) return false;
-            const bool mine = cs_turn == 0;
-            cs_turn = mine ? p.tiles_n - 1 : cs_turn - 1;
-            return mine;
-        };
-        for (int kt = kt0; kt < kt1 - 2; kt += 2) {
-            const bool c = my_turn();
-            g3_ktile<0, true>(s, src, kt + 1, src, kt + 2, c);
-            g3_ktile<1, true>(s, src, kt + 2, src, kt + 3, c);
-        }
-        {
-            const bool c = my_turn();
-            g3_ktile<0, true>(s, src, kt1 - 1, null, 0, c);
-            g3_ktile<1, true>(s, null, 0, null, 0, c);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (wr == 0) __builtin_amdgcn_s_barrier();          // (both wave rows are past their last fragment read: the next segment may refill the LDS)
-        if (cs_any) {
-            float c0 = s.cs[0], c1 = s.cs[1];
-            c0 += __shfl_xor(c0, 16, 64); c0 += __shfl_xor(c0, 32, 64);
-            c1 += __shfl_xor(c1, 16, 64); c1 += __shfl_xor(c1, 32, 64);
-            if (lane < 16) {
-                float* row = p.colsum_ws + (int64_t)cs_row * p.M;
-                const int wcol = wave & 3;
-                const int64_t ma = m0 + wr * 128 + wcol * 16 + lane, mb = ma + 64;
-                if (ma < p.M) row[ma] = c0;
-                if (mb < p.M) row[mb] = c1;
-            }
-        }
+        // column sums: inside a level all N-tiles of a tile row walk the same K range; the leftover segments of different N-tiles are ragged
+        // (G3Turn: the turn follows the absolute pair index)
+        G3Turn turn = g3_tn_colsum_begin(s, p, regular ? tn : (tn + p.tiles_n - ((kt0 >> 1) % p.tiles_n)) % p.tiles_n);
+        g3_tn_walk(s, p, g3_make_src_tn(p, tm, tn), kt0, kt1, wr, turn);      // (drained: the next segment may refill the LDS)
+        g3_tn_store_colsum(p, s, cs_row, m0, lane);
         g3_epilogue<5>(p, s, m0, n0, g3_lane_now(), reinterpret_cast<float*>(p.C) + (int64_t)part * p.slab_stride, 0);
         u0 = ue;
     }
@@ -999,9 +901,6 @@ template <int EPI, int PRE> int launch3r(const GemmParams& q0, int G, hipStream_
     // 60); not the x-row-operand kernel (fc2 dgrad, the same 2 364 tiles: 243 -> 251 us sustained with them, measured and removed)
     constexpr bool HI = EPI == 0 || EPI == 2 || EPI == 1;
     constexpr int LDS_BYTES = G3_LDS + 64 + (PRE == 5 ? 4096 : PRE == 4 ? 8192 : 0);      // operand buffers + the ticket word (+ PRE 5: two buffers of 256 LayerNorm row pairs; PRE 4: 256 rows x 4 wave columns of partial pairs)
-    static OncePerDevice once;
-    if (once.need())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g3r_kernel<EPI, PRE, HI>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     GemmParams q = q0;
     // Tile quantisation: T tiles on G resident workgroups take ceil(T / G) rounds, and the encoder's N = 768 outputs are 591 tiles =
     // 2.31 rounds (N = 3072: 9.23).  When at most half the CUs would work in the last round, its tiles run as two 128-row items
@@ -1014,9 +913,7 @@ template <int EPI, int PRE> int launch3r(const GemmParams& q0, int G, hipStream_
     }
     // claimed items need >= 2 K-tile pairs per item (see the kernel)
     q.g3_tickets = q.K >= 4 * G3_BK ? g3r_tickets(stream) : nullptr;
-    hipLaunchKernelGGL((gemm_g3r_kernel<EPI, PRE, HI>), dim3((unsigned)G), dim3(512), LDS_BYTES, stream, q);
-    ME_CHECK_LAUNCH("me_gemm(g3 resident)");
-    return ME_OK;
+    return launch_kernel<gemm_g3r_kernel<EPI, PRE, HI>>("me_gemm(g3 resident)", dim3((unsigned)G), 512, LDS_BYTES, LDS_BYTES, stream, q);
 }
 
 int launch3r_any(int epi, int pre, const GemmParams& q, int G, hipStream_t stream) {
@@ -1033,12 +930,7 @@ int launch3r_any(int epi, int pre, const GemmParams& q, int G, hipStream_t strea
 
 // one tile (or one K-part of a split tail tile) per workgroup
 template <int EPI, bool WRAP> int launch3t(const GemmParams& q, int nwg, hipStream_t stream) {
-    static OncePerDevice once;
-    if (once.need())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g3_kernel<EPI, WRAP>), hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
-    hipLaunchKernelGGL((gemm_g3_kernel<EPI, WRAP>), dim3((unsigned)nwg), dim3(512), G3_LDS, stream, q);
-    ME_CHECK_LAUNCH(WRAP ? "me_gemm(g3, wrapped A)" : "me_gemm(g3)");
-    return ME_OK;
+    return launch_kernel<gemm_g3_kernel<EPI, WRAP>>(WRAP ? "me_gemm(g3, wrapped A)" : "me_gemm(g3)", dim3((unsigned)nwg), 512, G3_LDS, G3_LDS, stream, q);
 }
 
 template <int EPI> int launch3e(const GemmParams& q, const G3Form& f, hipStream_t stream) {
@@ -1056,22 +948,12 @@ unsigned* me_work_counters(hipStream_t stream) { return g3r_tickets(stream); }
 
 // TN: p.split_k slabs of p.ksteps_per_split K-tiles (of 64) each into p.C = [split_k][M][N] fp32
 int launch_g3_tn(const GemmParams& p, hipStream_t stream) {
-    static OncePerDevice once;
-    if (once.need())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g3tn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
     const int nwg = p.tiles_m * p.tiles_n * p.split_k;
-    hipLaunchKernelGGL(gemm_g3tn_kernel, dim3((unsigned)nwg), dim3(512), G3_LDS, stream, p);
-    ME_CHECK_LAUNCH("me_gemm(g3 tn)");
-    return ME_OK;
+    return launch_kernel<gemm_g3tn_kernel>("me_gemm(g3 tn)", dim3((unsigned)nwg), 512, G3_LDS, G3_LDS, stream, p);
 }
 
 int launch_g3_tn_sk(const GemmParams& p, hipStream_t stream) {
-    static OncePerDevice once;
-    if (once.need())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g3tn_sk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
-    hipLaunchKernelGGL(gemm_g3tn_sk_kernel, dim3((unsigned)p.sk_wgs), dim3(512), G3_LDS, stream, p);
-    ME_CHECK_LAUNCH("me_gemm(g3 tn, balanced partition)");
-    return ME_OK;
+    return launch_kernel<gemm_g3tn_sk_kernel>("me_gemm(g3 tn, balanced partition)", dim3((unsigned)p.sk_wgs), 512, G3_LDS, G3_LDS, stream, p);
 }
 
 bool g3_tn_supported(const GemmParams& p) {

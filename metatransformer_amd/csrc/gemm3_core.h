@@ -398,6 +398,107 @@ __device__ __forceinline__ void g3_zero(G3State& s) {
         for (int j = 0; j < 4; ++j) s.acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
+// ---- the two ends of a K-loop that starts on empty LDS (every kernel but the resident one, whose stream runs through its epilogues).
+// stage(k): a kernel's hook ahead of the issues of K-tile k -- the gathering wgrad kernel (patch_embed.hip) refreshes its lane offsets there.
+struct G3NoStage { __device__ __forceinline__ void operator()(int) const {} };
+// Prime the stream with K-tiles k0, k0 + 1 of `src`: SEVEN half-tiles, all of K-tile k0 into buffer 0 and B-X, A-X, B-Y of k0 + 1 into
+// buffer 1 -- the stream depth the phases keep up (phase 0 of the first g3_ktile issues the eighth, A-Y of k0 + 1).  vmcnt(6): this
+// wave's share of K-tile k0 has landed, the three younger half-tiles (two instructions each) stay in flight -- the same count as the wait
+// in phase 3, which is tied to that depth.  The first barrier publishes K-tile k0; the second puts wave row 1 one barrier behind wave row 0.
+template <bool WRAP = false, typename Stage = G3NoStage>
+__device__ __forceinline__ void g3_prime(G3State& s, const G3Src& src, int k0, int wr, Stage stage = {}) {
+    stage(k0);
+    g3_issue<0, WRAP>(s, src, 0, k0); g3_issue<1, WRAP>(s, src, 0, k0); g3_issue<2, WRAP>(s, src, 0, k0); g3_issue<3, WRAP>(s, src, 0, k0);
+    stage(k0 + 1);
+    g3_issue<0, WRAP>(s, src, 1, k0 + 1); g3_issue<1, WRAP>(s, src, 1, k0 + 1); g3_issue<2, WRAP>(s, src, 1, k0 + 1);
+    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (wr == 1) __builtin_amdgcn_s_barrier();
+}
+// Behind the last K-tile: the trailing null DMAs must land before the LDS is released or refilled, and wave row 0 waits for wave row 1 to
+// catch up -- both rows are then past their last fragment read.
+__device__ __forceinline__ void g3_drain(int wr) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (wr == 0) __builtin_amdgcn_s_barrier();
+}
+
+// ---- split-K wgrad: what one workgroup does for one (tile, K-range) part, shared by the TN kernels (gemm3.hip, patch_embed.hip).  The
+// three-plane kernel (gemm3_x3.hip) stands on g3_prime / g3_drain only and holds its OWN copy of the id decode, the turn and the
+// column-sum store (on the shared ones it measured 0.5 % slower at both of its launch shapes: profiles/g3_wgrad_one_walk.txt, D) -- a
+// change to the turn or the store has to be made there as well.
+// Bias gradient: the N-tiles of one (M-tile, K-range) stage the same A rows, so they share the column sums (g3_phase, cs_on) pair by pair of
+// K-tiles, round-robin: `turn` = pairs until this workgroup's next turn, of n = tiles_n.  A workgroup whose K-range starts at the same pair as
+// its tile row's others starts at turn = tn.  Where the ranges of a tile row's N-tiles are ragged (the leftover segments of
+// gemm_g3tn_sk_kernel) the turn is tied to the ABSOLUTE pair index instead: pair k belongs to N-tile k % tiles_n, whichever of that tile's
+// segments covers it takes it.  (A first version let the tn = 0 segments sum every pair: those workgroups became the launch's tail, +33 % --
+// profiles/r06_contention.txt.)
+struct G3Turn {
+    int turn, n;
+    bool on;                    // column sums asked for at all (GemmParams::colsum_ws)
+    __device__ __forceinline__ bool next() {
+        if (!on) return false;
+        const bool mine = turn == 0;
+        turn = mine ? n - 1 : turn - 1;
+        return mine;
+    }
+};
+__device__ __forceinline__ G3Turn g3_tn_colsum_begin(G3State& s, const GemmParams& p, int first_turn) {
+    s.cs[0] = s.cs[1] = 0.f;
+    return G3Turn{first_turn, p.tiles_n, p.colsum_ws != nullptr};
+}
+// ... and their end: lanes l, l + 16, l + 32, l + 48 hold the four k-groups of column l & 15 -- fold them, then one row of partial sums per
+// part, p.colsum_ws[row][M] (columns m0 + ..: m-tiles wc and 4 + wc of this wave row, see g3_phase)
+__device__ __forceinline__ void g3_tn_store_colsum(const GemmParams& p, const G3State& s, int64_t row, int64_t m0, int lane) {
+    if (!p.colsum_ws) return;
+    float c0 = s.cs[0], c1 = s.cs[1];
+    c0 += __shfl_xor(c0, 16, 64); c0 += __shfl_xor(c0, 32, 64);
+    c1 += __shfl_xor(c1, 16, 64); c1 += __shfl_xor(c1, 32, 64);
+    if (lane < 16) {
+        float* dst = p.colsum_ws + row * p.M;
+        const int64_t ma = m0 + (s.wave >> 2) * 128 + (s.wave & 3) * 16 + lane, mb = ma + 64;
+        if (ma < p.M) dst[ma] = c0;
+        if (mb < p.M) dst[mb] = c1;
+    }
+}
+// The uniform (tile, split) grid: work ids are split-major (id = split * tiles + tile; the caller passes its xcd_major_wgid), so the workgroups
+// an XCD runs together read the SAME rows of both operands at the same time -- every operand row comes out of HBM once and is shared
+// through that XCD's L2.  Part `split` covers K-tiles [kt0, kt1) and writes slab `split` and column-sum row split * tiles_n + tn.
+struct G3TnPart {
+    int split, tm, tn, kt0, kt1;
+    int64_t m0, n0;
+};
+__device__ __forceinline__ G3TnPart g3_tn_part(const GemmParams& p, int wgid) {
+    G3TnPart w;
+    const int tiles = p.tiles_m * p.tiles_n;
+    w.split = __builtin_amdgcn_readfirstlane(wgid / tiles);
+    const int tile = wgid - w.split * tiles;
+    w.tm = __builtin_amdgcn_readfirstlane(tile / p.tiles_n);
+    w.tn = tile - w.tm * p.tiles_n;
+    w.m0 = (int64_t)w.tm * G3_BM;
+    w.n0 = (int64_t)w.tn * G3_BN;
+    w.kt0 = w.split * p.ksteps_per_split;
+    w.kt1 = w.kt0 + p.ksteps_per_split;
+    return w;
+}
+// K-tiles [kt0, kt1) (an even count >= 2; tiles past K read zeros) of `src` into the accumulators: prime, pairs of K-tiles, drain.  Past the
+// end of the range the source is a null descriptor (see g3_phase), so the last pair issues like every other.
+template <typename Stage = G3NoStage>
+__device__ __forceinline__ void g3_tn_walk(G3State& s, const GemmParams& p, const G3Src& src, int kt0, int kt1, int wr, G3Turn& turn, Stage stage = {}) {
+    g3_prime(s, src, kt0, wr, stage);
+    const G3Src null = g3_null_src(p);
+    for (int kt = kt0; kt < kt1 - 2; kt += 2) {
+        const bool c = turn.next();
+        stage(kt + 2);
+        g3_ktile<0, true>(s, src, kt + 1, src, kt + 2, c);
+        stage(kt + 3);
+        g3_ktile<1, true>(s, src, kt + 2, src, kt + 3, c);
+    }
+    const bool c = turn.next();
+    g3_ktile<0, true>(s, src, kt1 - 1, null, 0, c);
+    g3_ktile<1, true>(s, null, 0, null, 0, c);
+    g3_drain(wr);
+}
+
 // ---- epilogue without LDS.  Two neighbouring 16 x 16 accumulator tiles (n-tiles 2q, 2q+1) are re-dealt inside the wave
 // with v_permlane16_swap (rows of 16 lanes: odd rows of the first operand <-> even rows of the second), after which lane
 // (r = l & 15, g = l >> 4) holds EIGHT consecutive output columns of row r: n-tile 2q + (g & 1), columns 8 (g >> 1) ..

@@ -27,9 +27,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2;
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int wgid = xcd_major_wgid(blockIdx.x, gridDim.x);
     const int tiles = p.tiles_m * p.tiles_n;
     const int split = __builtin_amdgcn_readfirstlane(wgid / tiles);
     const int tile = wgid - split * tiles;
@@ -44,13 +42,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const G3Src null = g3_null_src(p);
     G3Src cur = x3_seg_src(p, m0, n0, 0);
 
-    g3_issue<0>(s, cur, 0, kt0); g3_issue<1>(s, cur, 0, kt0); g3_issue<2>(s, cur, 0, kt0); g3_issue<3>(s, cur, 0, kt0);
-    g3_issue<0>(s, cur, 1, kt0 + 1); g3_issue<1>(s, cur, 1, kt0 + 1); g3_issue<2>(s, cur, 1, kt0 + 1);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();
-    // bias gradient: the N-tiles of one (M-tile, split) stage the same dOut rows -- they share the column sums pair by pair of K-tiles,
-    // round-robin; segment 2 stages the hi plane of dOut a second time and is left out
+    g3_prime(s, cur, kt0, wr);
+    // bias gradient: the round-robin turn of G3Turn (gemm3_core.h); segment 2 stages the hi plane of dOut a second time and is left out
     const bool do_cs = p.colsum_ws != nullptr;
     s.cs[0] = s.cs[1] = 0.f;
     int cs_turn = do_cs ? tn : -1;
@@ -73,9 +66,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             cur = nxt;
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (wr == 0) __builtin_amdgcn_s_barrier();
-    if (do_cs) {
+    g3_drain(wr);
+    if (do_cs) {      // (g3_tn_store_colsum, written out: see the note on this kernel in gemm3_core.h)
         float c0 = s.cs[0], c1 = s.cs[1];
         c0 += __shfl_xor(c0, 16, 64); c0 += __shfl_xor(c0, 32, 64);
         c1 += __shfl_xor(c1, 16, 64); c1 += __shfl_xor(c1, 32, 64);
@@ -91,13 +83,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 int launch_g3tn_x3(const GemmParams& p, hipStream_t stream, const void*) {
-    static OncePerDevice once;
-    if (once.need())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_g3tn_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
     const int nwg = p.tiles_m * p.tiles_n * p.split_k;
-    hipLaunchKernelGGL(gemm_g3tn_x3_kernel, dim3((unsigned)nwg), dim3(512), G3_LDS, stream, p);
-    ME_CHECK_LAUNCH("me_gemm(g3 tn, three planes)");
-    return ME_OK;
+    return launch_kernel<gemm_g3tn_x3_kernel>("me_gemm(g3 tn, three planes)", dim3((unsigned)nwg), 512, G3_LDS, G3_LDS, stream, p);
 }
 
 }  // namespace

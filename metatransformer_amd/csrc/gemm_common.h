@@ -36,6 +36,14 @@ struct GemmParams {
                                             // [N / 64][M] pairs (mean, M2) over 64-column groups, or null
 };
 
+// XCD-major workgroup id of block `bid` in a one-dimensional grid of `nwg`.  The hardware deals blocks out round-robin: block b runs on
+// XCD b % 8.  This bijection hands every XCD a CONTIGUOUS range of ids (the first nwg % 8 XCDs one more than the others), so that
+// neighbours in the id list -- the tiles of one row panel, or the workgroups of one split-K level that stream the same operand rows --
+// run on the same XCD and share those rows through its L2.
+__device__ __forceinline__ int xcd_major_wgid(int bid, int nwg) {
+    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
 
 // ---- a split-K weight gradient on W workgroups, W not a multiple of the T tiles (GemmParams::sk_*): S = W / T whole split levels of L1 pairs
 // per tile, then the LEFTOVER Ul = U - S L1 pairs of every tile as a tile-major list of T Ul units that the E = W - S T extra workgroups share

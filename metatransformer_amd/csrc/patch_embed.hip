@@ -113,12 +113,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     advance();
     G3Src nxt = g.planes > 1 ? pe_plane_src(p, g, c, dt, 1, n0) : null;
 
-    g3_issue<0>(s, cur, 0, 0); g3_issue<1>(s, cur, 0, 0); g3_issue<2>(s, cur, 0, 0); g3_issue<3>(s, cur, 0, 0);
-    g3_issue<0>(s, cur, 1, 1); g3_issue<1>(s, cur, 1, 1); g3_issue<2>(s, cur, 1, 1);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();
-
+    g3_prime(s, cur, 0, wr);
     for (int pl = 0; pl < g.planes; ++pl) {
         g3_ktile<0>(s, cur, 1, cur, 2);
         g3_ktile<1>(s, cur, 2, cur, 3);
@@ -128,18 +123,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         advance();
         nxt = pl + 2 < g.planes ? pe_plane_src(p, g, c, dt, pl + 2, n0) : null;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (wr == 0) __builtin_amdgcn_s_barrier();
+    g3_drain(wr);
     g3_epilogue<EPI>(p, s, m0, n0, lane);
 }
 
 template <int EPI> int launch_pe(const GemmParams& p, const PeGeom& g, hipStream_t stream) {
-    static OncePerDevice once;
-    if (once.need())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_embed_g3_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
-    hipLaunchKernelGGL((patch_embed_g3_kernel<EPI>), dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(512), G3_LDS, stream, p, g);
-    ME_CHECK_LAUNCH("me_patch_embed");
-    return ME_OK;
+    return launch_kernel<patch_embed_g3_kernel<EPI>>("me_patch_embed", dim3((unsigned)(p.tiles_m * p.tiles_n)), 512, G3_LDS, G3_LDS, stream, p, g);
 }
 
 // ---- weight gradient dW[Cout, Kp] = dY[tokens, Cout]^T . patches[tokens, Kp]: the split-K wgrad kernel (gemm_g3tn_kernel, gemm3.hip) with
@@ -161,19 +150,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2;
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    const int tiles = p.tiles_m * p.tiles_n;
-    const int split = __builtin_amdgcn_readfirstlane(wgid / tiles);
-    const int tile = wgid - split * tiles;
-    const int tm = __builtin_amdgcn_readfirstlane(tile / p.tiles_n), tn = tile - tm * p.tiles_n;
-    const int64_t m0 = (int64_t)tm * G3_BM, n0 = (int64_t)tn * G3_BN;
+    const G3TnPart w = g3_tn_part(p, xcd_major_wgid(blockIdx.x, gridDim.x));
 
     G3State s;
     g3_init_lane_tn(s, p, smem, wave, lane);
     g3_zero(s);
-    G3Src src = g3_make_src_tn(p, tm, tn);
+    G3Src src = g3_make_src_tn(p, w.tm, w.tn);
     src.b = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.B), 0, (int)g.x_bytes, 0x00020000);
     s.kstep_b = 0;
     // feature part of the lane's two B-X / B-Y chunks (same k-row t and slot as g3_init_lane_tn) and the k-rows themselves
@@ -186,7 +168,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         trow[i] = (uint32_t)t;
 #pragma unroll
         for (int y = 0; y < 2; ++y) {
-            const int f = (int)n0 + b_col + 32 * y;                  // < Kp: Kp is a multiple of 256
+            const int f = (int)w.n0 + b_col + 32 * y;                 // < Kp: Kp is a multiple of 256
             const int pl = f >> 8, in = f & 255;
             const int c_ = pl / g.kt, dt = pl - c_ * g.kt;
             feat[i][y] = (uint32_t)((((int64_t)c_ * g.T + dt) * g.plane_bytes) + ((in / g.kw) * g.W + (in % g.kw)) * 2);
@@ -201,63 +183,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             s.src[2][i] = o + feat[i][1];
         }
     };
-    const int kt0 = split * p.ksteps_per_split, kt1 = kt0 + p.ksteps_per_split;       // (an even count; tiles past K read zeros)
-
-    set_b(kt0);
-    g3_issue<0>(s, src, 0, kt0); g3_issue<1>(s, src, 0, kt0); g3_issue<2>(s, src, 0, kt0); g3_issue<3>(s, src, 0, kt0);
-    set_b(kt0 + 1);
-    g3_issue<0>(s, src, 1, kt0 + 1); g3_issue<1>(s, src, 1, kt0 + 1); g3_issue<2>(s, src, 1, kt0 + 1);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();
-    const G3Src null = g3_null_src(p);
-    // bias gradient: the N-tiles of one (M-tile, split) stage the same dY rows -- they share the column sums pair by pair of K-tiles
-    const bool do_cs = p.colsum_ws != nullptr;
-    s.cs[0] = s.cs[1] = 0.f;
-    int cs_turn = do_cs ? tn : -1;
-    auto my_turn = [&]() {
-        if (!do_cs) return false;
-        const bool mine = cs_turn == 0;
-        cs_turn = mine ? p.tiles_n - 1 : cs_turn - 1;
-        return mine;
-    };
-    for (int kt = kt0; kt < kt1 - 2; kt += 2) {
-        const bool c = my_turn();
-        set_b(kt + 2);
-        g3_ktile<0, true>(s, src, kt + 1, src, kt + 2, c);
-        set_b(kt + 3);
-        g3_ktile<1, true>(s, src, kt + 2, src, kt + 3, c);
-    }
-    {
-        const bool c = my_turn();
-        g3_ktile<0, true>(s, src, kt1 - 1, null, 0, c);
-        g3_ktile<1, true>(s, null, 0, null, 0, c);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (wr == 0) __builtin_amdgcn_s_barrier();
-    if (do_cs) {
-        float c0 = s.cs[0], c1 = s.cs[1];
-        c0 += __shfl_xor(c0, 16, 64); c0 += __shfl_xor(c0, 32, 64);
-        c1 += __shfl_xor(c1, 16, 64); c1 += __shfl_xor(c1, 32, 64);
-        if (lane < 16) {
-            float* row = p.colsum_ws + ((int64_t)split * p.tiles_n + tn) * p.M;
-            const int wcol = wave & 3;
-            const int64_t ma = m0 + wr * 128 + wcol * 16 + lane, mb = ma + 64;
-            if (ma < p.M) row[ma] = c0;
-            if (mb < p.M) row[mb] = c1;
-        }
-    }
-    g3_epilogue<5>(p, s, m0, n0, lane, reinterpret_cast<float*>(p.C) + (int64_t)split * p.slab_stride, 0);
+    // the plain walk (gemm_g3tn_kernel) with set_b as its stage hook
+    G3Turn turn = g3_tn_colsum_begin(s, p, w.tn);
+    g3_tn_walk(s, p, src, w.kt0, w.kt1, wr, turn, set_b);
+    g3_tn_store_colsum(p, s, (int64_t)w.split * p.tiles_n + w.tn, w.m0, lane);
+    g3_epilogue<5>(p, s, w.m0, w.n0, lane, reinterpret_cast<float*>(p.C) + (int64_t)w.split * p.slab_stride, 0);
 }
 
 int launch_pe_wgrad(const GemmParams& p, hipStream_t stream, const void* ctx) {
-    static OncePerDevice once;
-    if (once.need())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_embed_wgrad_g3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS);
     const int nwg = p.tiles_m * p.tiles_n * p.split_k;
-    hipLaunchKernelGGL(patch_embed_wgrad_g3_kernel, dim3((unsigned)nwg), dim3(512), G3_LDS, stream, p, *reinterpret_cast<const PeGeom*>(ctx));
-    ME_CHECK_LAUNCH("me_patch_embed_wgrad");
-    return ME_OK;
+    return launch_kernel<patch_embed_wgrad_g3_kernel>("me_patch_embed_wgrad", dim3((unsigned)nwg), 512, G3_LDS, G3_LDS, stream, p,
+                                                      *reinterpret_cast<const PeGeom*>(ctx));
 }
 
 struct PeShape {

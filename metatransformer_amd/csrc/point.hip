@@ -594,11 +594,7 @@ extern "C" int me_knn(const float* support, const float* query, int32_t* idx, in
     ME_CHECK_ARG(support && query && idx && B > 0 && n > 0 && m > 0 && k > 0 && k <= n, "me_knn: bad args");
     if (n > 10240) return me_knn_stream(support, query, idx, B, n, m, k, stream_);      // beyond the LDS-resident form
     const size_t lds = (size_t)4 * n * sizeof(float);
-    static OncePerDevice once;
-    if (once.need()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(knn_kernel, dim3((unsigned)((m + 3) / 4), (unsigned)B), dim3(256), lds, stream, support, query, idx, n, m, k);
-    ME_CHECK_LAUNCH("me_knn");
-    return ME_OK;
+    return launch_kernel<knn_kernel>("me_knn", dim3((unsigned)((m + 3) / 4), (unsigned)B), 256, lds, 160 * 1024, stream, support, query, idx, n, m, k);
 }
 
 extern "C" int me_group_relative(const float* points, const float* centers, const int32_t* idx, float* rows, int B, int n, int m,

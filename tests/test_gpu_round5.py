@@ -576,6 +576,12 @@ def test_patch_embed_wgrad_gathers_inside_the_kernel(dev, case):
     dw_ref = dy.double().t() @ cols.double()
     check_close(dw, dw_ref, 2e-5, "fused patch-embed wgrad")
     check_close(db, dy.double().sum(0), 2e-5, "bias gradient on the wgrad launch")
+    if (shape, geom) == ((2, 3, 4, 64, 64), (2, 16, 16, 2, 16, 16)):
+        # the gathering kernel is the plain split-K walk (g3_tn_walk) with gathered B rows: same descriptor, same plan, same K order, same
+        # fold -- the bits of the plain kernel on the gathered matrix (six planes = six N-tiles: the column-sum turn rotates)
+        c2, _ = ops.patchify(xd, *geom, dt)
+        dw2, db2 = ops.gemm(dy.to(dev), c2.reshape(B * one, -1), op=_capi.ME_GEMM_TN, out_dtype=torch.float32, want_colsum_a=True)
+        assert torch.equal(dw, dw2) and torch.equal(db, db2)
     dwb, _ = ops.patch_embed_wgrad(xd, geom, dy.to(dev), dt, False)
     check_close(dwb.float(), dw_ref, TOL_BF16_OP, "fused wgrad, bf16 out")
 
