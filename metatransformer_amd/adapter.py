@@ -33,7 +33,8 @@ from . import _capi, ops
 from ._capi import MetaEncError, check, dtype_code, ptr, stream_ptr
 from .data2seq import PatchEmbed
 from .encoder import Block
-from .heads import _LayerNormFn, linear
+from .heads import _LayerNormFn
+from .linear import linear
 
 MAX_LEVELS = 8          # me_ms_deform_attn_*: levels per call
 MAX_HEAD_DIM = 128      # ... channels per head (a multiple of 4)
@@ -486,79 +487,7 @@ class _Conv3x3UnfoldFn(torch.autograd.Function):
         return dx, None, None, None, None
 
 
-CONV_K_CHUNK = 128      # fp32 contractions longer than this run as several me_gemm calls accumulating into the output
-
-
-def _gemm_nt_chunked(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    """fp32 [M, N] = a [M, K] b [N, K]^T (+ bias) on me_gemm NT.  The exact-fp32 kernel adds all K products of an output into
-    one accumulator, so its rounding error grows like sqrt(K); a 3x3 convolution has K = 9 Cin up to 2304.  fp32 operands are
-    therefore contracted CONV_K_CHUNK columns at a time, each call adding its partial sum to the output (beta = 1): the long
-    chain becomes K / 128 short ones plus K / 128 additions of partial sums.  bf16 operands (whose own rounding is 2^-9) take
-    one call."""
-    lib = _capi.load()
-    M, K = a.shape
-    N = b.shape[0]
-    out = torch.empty(M, N, dtype=torch.float32, device=a.device)
-    step = CONV_K_CHUNK if a.dtype == torch.float32 else K
-    es = a.element_size()
-    bias = bias.detach().float().contiguous() if bias is not None else None
-    for k0 in range(0, K, step):
-        d = _capi.GemmDesc()
-        d.op, d.ab_dtype = _capi.ME_GEMM_NT, dtype_code(a.dtype)
-        d.M, d.N, d.K = M, N, min(step, K - k0)
-        d.A, d.lda = ptr(a) + k0 * es, K
-        d.B, d.ldb = ptr(b) + k0 * es, K
-        d.C, d.ldc, d.c_dtype = ptr(out), N, _capi.ME_F32
-        d.alpha, d.beta = 1.0, 0.0 if k0 == 0 else 1.0
-        if bias is not None and k0 == 0:
-            d.bias = ptr(bias)
-        ws = None
-        need = lib.me_gemm_workspace_bytes(ctypes.byref(d))
-        if need:
-            ws = torch.empty(need, dtype=torch.uint8, device=a.device)
-            d.workspace, d.workspace_bytes = ptr(ws), need
-        check(lib.me_gemm(ctypes.byref(d), stream_ptr()), "me_gemm (conv3x3_rows)")
-    return out
-
-
-class _ConvLinearFn(torch.autograd.Function):
-    """heads._LinearFn with its two NT products chunked along K (_gemm_nt_chunked): y = x W^T + b for the unfolded rows"""
-
-    @staticmethod
-    def forward(ctx, x, w, b):
-        cdt = x.dtype
-        N, K = w.shape
-        Np = (N + 7) // 8 * 8
-        wc = w.detach().to(cdt)
-        bc = b.detach().float() if b is not None else None
-        if Np != N:
-            wc = torch.cat([wc, wc.new_zeros(Np - N, K)])
-            bc = torch.cat([bc, bc.new_zeros(Np - N)]) if bc is not None else None
-        wc = wc.contiguous()
-        y = _gemm_nt_chunked(x, wc, bc)
-        ctx.save_for_backward(x, wc)
-        ctx.meta = (N, Np, b is not None, w.dtype)
-        return y if Np == N else y[:, :N].contiguous()
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        x, wc = ctx.saved_tensors
-        N, Np, has_b, wdt = ctx.meta
-        d2 = dy.to(x.dtype)
-        if Np != N:
-            d2 = torch.cat([d2, d2.new_zeros(d2.shape[0], Np - N)], dim=1)
-        d2 = d2.contiguous()
-        dx = _gemm_nt_chunked(d2, ops.transpose_cast(wc, wc.dtype), None).to(x.dtype) if ctx.needs_input_grad[0] else None
-        M = d2.shape[0]
-        if M % 8 == 0:
-            dw = ops.gemm(d2, x, op=_capi.ME_GEMM_TN, out_dtype=torch.float32)
-        else:       # the TN kernel wants 16-byte rows of the reduction-major operands: pad the batch with zero rows
-            pad = 8 - M % 8
-            dw = ops.gemm(torch.cat([d2, d2.new_zeros(pad, Np)]), torch.cat([x, x.new_zeros(pad, x.shape[1])]),
-                          op=_capi.ME_GEMM_TN, out_dtype=torch.float32)
-        db = ops.colsum(d2)[:N].to(wdt) if has_b else None
-        return dx, dw[:N].to(wdt), db
+CONV_K_CHUNK = 128      # fp32 contractions longer than this run as several me_gemm calls accumulating into the output (linear's k_chunk)
 
 
 def conv3x3_rows(x: torch.Tensor, weight: torch.Tensor, B: int, H: int, W: int, stride: int = 1,
@@ -577,8 +506,7 @@ def conv3x3_rows(x: torch.Tensor, weight: torch.Tensor, B: int, H: int, W: int, 
     _require_one_gpu("conv3x3_rows", x=x, weight=weight, bias=bias)
     Cout, Cin = weight.shape[:2]
     cols = _Conv3x3UnfoldFn.apply(x, int(B), int(H), int(W), int(stride))
-    w2 = F.pad(weight.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin), (0, cols.shape[1] - 9 * Cin))
-    return _ConvLinearFn.apply(cols, w2, bias)
+    return linear(cols, weight.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin), bias, k_chunk=CONV_K_CHUNK)
 
 
 class _MaxPoolFn(torch.autograd.Function):

@@ -33,7 +33,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _capi, ops
-from ._capi import ME_GEMM_TN, MetaEncError, check, dtype_code, ptr, stream_ptr
+from ._capi import MetaEncError, check, dtype_code, ptr, stream_ptr
+from .linear import linear, pad_to, wgrad
 
 
 def _boundary_dtypes(weight: torch.Tensor):
@@ -359,8 +360,7 @@ class _TSEmbedFn(torch.autograd.Function):
         ncols = (3 * cin + 3) // 4 * 4
         xu = torch.empty((B * L, ncols), dtype=torch.float32, device=xf.device)
         check(lib.me_timeseries_unfold(ptr(xf), ptr(xu), B, L, cin, ncols, stream_ptr()), "me_timeseries_unfold")
-        dw = ops.gemm(dy2, xu, op=_capi.ME_GEMM_TN, out_dtype=torch.float32)          # [C, ncols]
-        dw = dw[:, :3 * cin].reshape(C, cin, 3).to(wdt)
+        dw = wgrad(dy2, xu)[0][:, :3 * cin].reshape(C, cin, 3).to(wdt)                 # [C, ncols] -> the Conv1d's [C, cin, 3]
         return (None, dw, None, None, None, None, None, None)
 
 
@@ -373,8 +373,8 @@ class _TimeFeatFn(torch.autograd.Function):
     def forward(ctx, feats, weight, emb):
         C, d_inp = weight.shape
         cdt = emb.dtype
-        fc = F.pad(feats, (0, 8 - d_inp)).to(cdt).contiguous()
-        wc = F.pad(weight.detach().float(), (0, 8 - d_inp)).to(cdt).contiguous()
+        fc = pad_to(feats, 1).to(cdt).contiguous()
+        wc = pad_to(weight.detach().float(), 1).to(cdt).contiguous()
         y = ops.gemm(fc, wc, residual=emb.reshape(-1, C).contiguous(), out_dtype=cdt)
         ctx.save_for_backward(fc)
         ctx.meta = (d_inp, weight.dtype, emb.shape)
@@ -386,12 +386,7 @@ class _TimeFeatFn(torch.autograd.Function):
         d_inp, wdt, eshape = ctx.meta
         dw = None
         if ctx.needs_input_grad[1]:
-            d = ops.cast(dy.reshape(-1, eshape[-1]).contiguous(), fc.dtype)
-            M = d.shape[0]
-            if M % 8:      # the TN kernel wants the row count a multiple of 8: zero rows pad it
-                d = torch.cat([d, d.new_zeros(8 - M % 8, d.shape[1])])
-                fc = torch.cat([fc, fc.new_zeros(8 - M % 8, 8)])
-            dw = ops.gemm(d, fc, op=ME_GEMM_TN, out_dtype=torch.float32)[:, :d_inp].to(wdt)
+            dw = wgrad(ops.cast(dy.reshape(-1, eshape[-1]).contiguous(), fc.dtype), fc)[0][:, :d_inp].to(wdt)
         return None, dw, dy if ctx.needs_input_grad[2] else None
 
 
@@ -407,25 +402,6 @@ class _DropoutFn(torch.autograd.Function):
     def backward(ctx, dy):
         rows_per_sample, p, seed = ctx.meta
         return ops.dropout_add(dy.contiguous(), None, rows_per_sample, p, 0.0, seed), None, None, None
-
-
-class _NodeIdProjFn(torch.autograd.Function):
-    """Z [rows, 2C] = P [rows, K] W^T on me_gemm, the dtype policy of heads.linear (fp32 rows -> the exact fp32 MFMA, bf16 rows ->
-    bf16 MFMA, fp32 result either way).  The identifiers carry no gradient: backward is the one TN GEMM dW = dZ^T P.  rows is a
-    multiple of 8 (the caller pads with zero rows), K a multiple of 8."""
-
-    @staticmethod
-    def forward(ctx, p, w):
-        wc = w.detach().to(p.dtype).contiguous()
-        ctx.save_for_backward(p)
-        ctx.wdt = w.dtype
-        return ops.gemm(p, wc, out_dtype=torch.float32)
-
-    @staticmethod
-    def backward(ctx, dz):
-        (p,) = ctx.saved_tensors
-        dw = ops.gemm(dz.to(p.dtype).contiguous(), p, op=ME_GEMM_TN, out_dtype=torch.float32)      # [2C, K]
-        return None, dw.to(ctx.wdt)
 
 
 def _graph_desc(node_data, edge_data, edge_index, offsets, atom, edge, graph_token, null_token, order, Z, perturb, dims):
@@ -663,10 +639,10 @@ class GraphFeatureTokenizer(nn.Module):
             P[:Sn, at:at + D] = p
             ws.append(w.view(C, 2, D).permute(1, 0, 2).reshape(2 * C, D))          # [W_a ; W_b]
             at += D
-        if Kp != K:
-            ws.append(ws[0].new_zeros(2 * C, Kp - K))
         W = ws[0] if len(ws) == 1 else torch.cat(ws, dim=1)
-        return _NodeIdProjFn.apply(P, W)
+        # the dtype policy of heads.linear (fp32 rows -> the exact fp32 MFMA, bf16 rows -> bf16 MFMA, fp32 result either way); the identifiers
+        # carry no gradient, so backward is the one TN GEMM dW = dZ^T P
+        return linear(P, W, None, compute_dtype=cdt)
 
     def forward(self, batched_data, perturb=None, node_ids=None):
         node_num, edge_num = self._check(batched_data, perturb, node_ids)

@@ -26,6 +26,7 @@ import torch.nn as nn
 from . import _capi, ops
 from ._capi import MetaEncError, check, dtype_code, ptr, stream_ptr
 from .encoder import Block, convert_video_state_dict
+from .linear import linear      # noqa: F401  (heads.linear: the name its call sites and the documents use)
 
 _POOL = {"mean": _capi.ME_POOL_MEAN, "avg": _capi.ME_POOL_MEAN, "max": _capi.ME_POOL_MAX, "cls": _capi.ME_POOL_FIRST,
          "first": _capi.ME_POOL_FIRST}
@@ -65,59 +66,6 @@ def pool_tokens(x: torch.Tensor, mode: str = "mean") -> torch.Tensor:
     if mode not in _POOL:
         raise MetaEncError(f"pool_tokens: mode {mode!r} (mean / max / cls)")
     return _PoolFn.apply(x, _POOL[mode])
-
-
-class _LinearFn(torch.autograd.Function):
-    """y = x W^T + b on me_gemm (exact fp32 MFMA or bf16 MFMA by the input dtype); N padded to a multiple of 8 internally
-    (class counts such as 174 are not)."""
-
-    @staticmethod
-    def forward(ctx, x, w, b):
-        x2 = x.reshape(-1, x.shape[-1]).contiguous()
-        cdt = torch.bfloat16 if x2.dtype in (torch.bfloat16, torch.float16) else torch.float32
-        xc = x2 if x2.dtype == cdt else ops.cast(x2, cdt)
-        N, K = w.shape
-        Np = (N + 7) // 8 * 8
-        wc = w.detach().to(cdt)
-        bc = b.detach().float() if b is not None else None
-        if Np != N:
-            wc = torch.cat([wc, wc.new_zeros(Np - N, K)])
-            bc = torch.cat([bc, bc.new_zeros(Np - N)]) if bc is not None else None
-        y = ops.gemm(xc, wc.contiguous(), bias=bc, out_dtype=torch.float32)
-        ctx.save_for_backward(xc, wc)
-        ctx.meta = (N, Np, x.shape, b is not None, w.dtype, x.dtype)
-        # never a VIEW of a tensor made in here: the reference's ClsHead puts nn.ReLU(inplace=True) straight behind its Linear
-        # (cls_base.py:112-118 with norm_args=None), and autograd refuses in-place writes to a custom Function's view output
-        return y if Np == N else y[:, :N].contiguous()
-
-    @staticmethod
-    def backward(ctx, dy):
-        xc, wc = ctx.saved_tensors
-        N, Np, xshape, has_b, wdt, xdt = ctx.meta
-        d2 = dy.to(xc.dtype)
-        if Np != N:
-            d2 = torch.cat([d2, d2.new_zeros(d2.shape[0], Np - N)], dim=1)
-        d2 = d2.contiguous()
-        dx = ops.gemm(d2, ops.transpose_cast(wc, wc.dtype), out_dtype=torch.float32).reshape(xshape).to(xdt)
-        M = d2.shape[0]
-        if M % 8 == 0:
-            dw = ops.gemm(d2, xc, op=_capi.ME_GEMM_TN, out_dtype=torch.float32)          # [Np, K]
-        else:       # the TN kernel wants 16-byte rows of the reduction-major operands: pad the batch with zero rows
-            pad = 8 - M % 8
-            dw = ops.gemm(torch.cat([d2, d2.new_zeros(pad, Np)]), torch.cat([xc, xc.new_zeros(pad, xc.shape[1])]),
-                          op=_capi.ME_GEMM_TN, out_dtype=torch.float32)
-        db = ops.colsum(d2)[:N].to(wdt) if has_b else None
-        return dx, dw[:N].to(wdt), db
-
-
-def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    """F.linear on the HIP GEMM (fp32 result)."""
-    if not x.is_cuda:
-        raise MetaEncError("heads.linear: CUDA tensors only (no CPU fallback)")
-    if x.shape[-1] % 8 != 0:
-        raise MetaEncError(f"heads.linear: in_features {x.shape[-1]} must be a multiple of 8")
-    y = _LinearFn.apply(x, weight, bias)                        # [rows, out_features]
-    return y if x.dim() == 2 else y.reshape(*x.shape[:-1], weight.shape[0])
 
 
 class _LayerNormFn(torch.autograd.Function):
@@ -326,11 +274,7 @@ class PointPatchEmbed(nn.Module):
     def _mlp(self, seq: nn.Sequential, f: torch.Tensor) -> torch.Tensor:
         for blk in seq:
             conv = blk[0]
-            w = conv.weight.reshape(conv.out_channels, conv.in_channels)
-            K = f.shape[1]
-            if w.shape[1] != K:                                   # the xyz layer: reduction padded 3 -> 8
-                w = torch.cat([w, w.new_zeros(w.shape[0], K - w.shape[1])], dim=1)
-            f = linear(f, w, conv.bias)
+            f = linear(f, _w2d(conv), conv.bias)                  # (the xyz layer: 3 weight columns on rows padded to 8)
             if len(blk) > 1:
                 bn = blk[1]
                 f = torch.nn.functional.batch_norm(f, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.training, bn.momentum, bn.eps)
@@ -537,11 +481,6 @@ class P3Embed(nn.Module):
         self.out_channels = channels[-1]
 
     @staticmethod
-    def _weight(conv: nn.Conv2d, K: int) -> torch.Tensor:
-        w = conv.weight.reshape(conv.out_channels, conv.in_channels)
-        return w if K == w.shape[1] else torch.cat([w, w.new_zeros(w.shape[0], K - w.shape[1])], dim=1)
-
-    @staticmethod
     def _norm_act(blk: nn.Sequential, f: torch.Tensor) -> torch.Tensor:
         if len(blk) == 1:
             return f
@@ -561,7 +500,7 @@ class P3Embed(nn.Module):
         f = group_features(cur_p, cur_f, idx, nbr, self.feature_type)                 # [B*S*k, cols]
         conv1, conv2 = convs
         for blk in conv1:
-            f = self._norm_act(blk, linear(f, self._weight(blk[0], f.shape[1]), blk[0].bias))
+            f = self._norm_act(blk, linear(f, _w2d(blk[0]), blk[0].bias))
         C1 = f.shape[1]
         pooled = pool_tokens(f.reshape(B * S, k, C1), self.reduction)                 # [B*S, C1]
         first = conv2[0]
@@ -570,7 +509,7 @@ class P3Embed(nn.Module):
         g = linear(f, w[:, C1:].contiguous(), None).reshape(B * S, k, -1) + linear(pooled, w[:, :C1].contiguous(), first[0].bias).unsqueeze(1)
         f = self._norm_act(first, g.reshape(B * S * k, -1))
         for blk in list(conv2)[1:]:
-            f = self._norm_act(blk, linear(f, self._weight(blk[0], f.shape[1]), blk[0].bias))
+            f = self._norm_act(blk, linear(f, _w2d(blk[0]), blk[0].bias))
         out = pool_tokens(f.reshape(B * S, k, f.shape[1]), self.reduction).reshape(B, S, -1)
         return center_p, out
 
@@ -739,17 +678,14 @@ def _convblock1d(cin, cout, norm_args=None, act_args=None, order="conv-norm-act"
     return nn.Sequential(*mods)
 
 
-def _w2d(conv: nn.Conv1d) -> torch.Tensor:
+def _w2d(conv) -> torch.Tensor:
+    """the [out, in] matrix of a k = 1 convolution (Conv1d / Conv2d)"""
     return conv.weight.reshape(conv.out_channels, conv.in_channels)
 
 
 def _lin(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x [rows, K] W^T (+ b) on the exact-fp32 GEMM, the reduction zero-padded to a multiple of 8 where it is not one"""
-    K = x.shape[1]
-    if K % 8:
-        x = torch.nn.functional.pad(x, (0, 8 - K % 8))
-        w = torch.nn.functional.pad(w, (0, 8 - K % 8))
-    return linear(x.float(), w.contiguous(), b)
+    """x [rows, K] W^T (+ b) on the exact-fp32 GEMM"""
+    return linear(x.float(), w, b)
 
 
 def _post(blk: nn.Sequential, f: torch.Tensor) -> torch.Tensor:

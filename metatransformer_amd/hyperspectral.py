@@ -24,11 +24,11 @@ from typing import Optional
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import _capi, ops
 from ._capi import MetaEncError, check, dtype_code, ptr, stream_ptr
 from .data2seq import _DropoutFn, _boundary_dtypes
+from .linear import linear, pad_to as _pad_to      # (neighborhood_tokens has a `pad_to` argument)
 from .weight_cache import _WeightCache
 
 # which route HyperSpectralEmbed.forward(cube, points) takes (DESIGN.md 7g has the timings behind the default):
@@ -147,10 +147,9 @@ class _HsiEmbedFn(torch.autograd.Function):
         if gemm_forward:
             # token rows by me_gemm on the gathered, K-padded tensor: bias, pos[j + 1] (residual, row j of every pixel) and the
             # one-row offset behind the cls token are its epilogue; row 0 of every pixel is parameter-sized glue
-            Kp = (K + 7) // 8 * 8
             x = neighborhood_tokens(cube, pts, patch, band_patch, out_dtype=wc.dtype, pad_to=8)
-            wp = F.pad(wc, (0, Kp - K)) if Kp != K else wc
-            ops.gemm(x.reshape(B * bands, Kp), wp, out=out.view(B * (bands + 1), C), bias=b32, residual=p32[1:], res_row_mod=bands,
+            wp = _pad_to(wc, 1)
+            ops.gemm(x.reshape(B * bands, wp.shape[1]), wp, out=out.view(B * (bands + 1), C), bias=b32, residual=p32[1:], res_row_mod=bands,
                      out_group=(bands, bands + 1, 1))
             out[:, 0] = (c32 + p32[0]).to(kdt)
         else:
@@ -181,38 +180,6 @@ class _HsiEmbedFn(torch.autograd.Function):
         dcls = g.get("dcls")
         return (None, None, cast(g.get("dw"), wdt), cast(g.get("dbias"), bdt), None if dcls is None else dcls.reshape(cshape).to(cdt), dpos,
                 None, None, None, None, None)
-
-
-class _GatheredLinearFn(torch.autograd.Function):
-    """x [M, K] W^T + b on me_gemm for any K: x and W are zero-padded to a multiple of 8 columns (the GEMM's K granule).  Backward:
-    dW = dY^T x (TN GEMM), db = colsum(dY); the gathered tokens are data."""
-
-    @staticmethod
-    def forward(ctx, x2, weight, bias, cdt):
-        K = weight.shape[1]
-        Kp = (K + 7) // 8 * 8
-        xc = F.pad(x2.detach(), (0, Kp - x2.shape[1])).to(cdt).contiguous() if x2.shape[1] != Kp or x2.dtype != cdt else x2.detach().contiguous()
-        wc = F.pad(weight.detach(), (0, Kp - K)).to(cdt).contiguous()
-        y = ops.gemm(xc, wc, bias=ops._f32(bias.detach()).contiguous(), out_dtype=torch.float32)
-        ctx.save_for_backward(xc)
-        ctx.meta = (K, weight.dtype, bias.dtype)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        (xc,) = ctx.saved_tensors
-        K, wdt, bdt = ctx.meta
-        d2 = dy.to(xc.dtype).contiguous()
-        M = d2.shape[0]
-        if M % 8:
-            d2 = torch.cat([d2, d2.new_zeros(8 - M % 8, d2.shape[1])])
-            xc = torch.cat([xc, xc.new_zeros(8 - M % 8, xc.shape[1])])
-        dw = db = None
-        if ctx.needs_input_grad[1]:
-            dw = ops.gemm(d2, xc, op=_capi.ME_GEMM_TN, out_dtype=torch.float32)[:, :K].to(wdt)
-        if ctx.needs_input_grad[2]:
-            db = ops.colsum(d2).to(bdt)
-        return None, dw, db, None
 
 
 class _HsiTokenizer(nn.Module):
@@ -259,7 +226,8 @@ class _HsiTokenizer(nn.Module):
             if x.requires_grad:
                 raise MetaEncError(f"{who}: gradient w.r.t. the gathered tokens is not implemented (they are data); detach the input")
             B, n = x.shape[:2]
-            y = _GatheredLinearFn.apply(x.reshape(B * n, x.shape[2]), w, self.patch_to_embedding.bias, cdt).reshape(B, n, C)
+            # (x and W zero-padded to 8 columns inside; the gathered tokens are data: no dgrad)
+            y = linear(x.reshape(B * n, x.shape[2]), w, self.patch_to_embedding.bias, compute_dtype=cdt).reshape(B, n, C)
             # cls row and position rows: parameter-sized glue with autograd's own backward (x += pos_embedding[:, :n + 1])
             y = torch.cat([self.cls_token.float().expand(B, 1, C), y], dim=1) + self.pos_embedding[:, :n + 1].float()
             y = y.to(odt)
@@ -314,7 +282,7 @@ class HyperSpectralClassifier(_HsiTokenizer):
         self.mlp_head = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, num_classes))
 
     def forward(self, x: torch.Tensor, points: Optional[torch.Tensor] = None) -> torch.Tensor:
-        from .heads import _LayerNormFn, linear, pool_tokens
+        from .heads import _LayerNormFn, pool_tokens
         t = self.transformer(self._tokens(x, points))
         ln, fc = self.mlp_head[0], self.mlp_head[1]
         f = _LayerNormFn.apply(pool_tokens(t, "cls"), ln.weight, ln.bias, ln.eps)

@@ -34,9 +34,10 @@ import torch
 import torch.nn as nn
 
 from . import heads, ops
-from ._capi import ME_ACT_GELU, ME_GEMM_AUX_IS_FACTOR, ME_GEMM_SAVE_GELU_GRAD, ME_GEMM_TN, MetaEncError
+from ._capi import ME_ACT_GELU, ME_GEMM_AUX_IS_FACTOR, ME_GEMM_SAVE_GELU_GRAD, MetaEncError
 from .data2seq import DataEmbedding
 from .encoder import Block
+from .linear import linear, wgrad
 
 # per-site seed offsets inside one decoder layer (DecoderLayer.forward, Transformer_EncDec.py:98-116)
 SEED_SELF_ATTN_DROP = 1       # FullAttention.dropout of the self-attention: on the probabilities, inside the kernel
@@ -65,18 +66,6 @@ def _compute_dtype(x: torch.Tensor) -> torch.dtype:
     if x.dtype in (torch.bfloat16, torch.float16):
         return torch.bfloat16
     raise MetaEncError(f"unsupported input dtype {x.dtype}")
-
-
-def _wgrad(d: torch.Tensor, xc: torch.Tensor, need_b: bool):
-    """(dW [N, K] fp32 = d^T xc, column sums of d or None); the TN kernel wants the row count a multiple of 8: zero rows pad it"""
-    M = d.shape[0]
-    if M % 8:
-        pad = 8 - M % 8
-        d = torch.cat([d, d.new_zeros(pad, d.shape[1])])
-        xc = torch.cat([xc, xc.new_zeros(pad, xc.shape[1])])
-    if need_b:
-        return ops.gemm(d, xc, op=ME_GEMM_TN, out_dtype=torch.float32, want_colsum_a=True)
-    return ops.gemm(d, xc, op=ME_GEMM_TN, out_dtype=torch.float32), None
 
 
 def _masked_grad(dy2: torch.Tensor, rows: int, p: float, seed: int, cdt: torch.dtype) -> torch.Tensor:
@@ -114,7 +103,7 @@ class _LinFn(torch.autograd.Function):
             dx = ops.gemm(d, ops.transpose_cast(wc, cdt), out_dtype=xdt if xdt in (torch.float32, torch.bfloat16) else torch.float32)
             dx = dx.reshape(xshape).to(xdt)
         if ng[1] or (has_b and ng[2]):
-            dw, db = _wgrad(d, xc, has_b and ng[2])
+            dw, db = wgrad(d, xc, bias=has_b and ng[2], fused_bias=True)
             dw = dw.to(wdt) if ng[1] else None
             db = db.to(wdt) if db is not None else None
         dres = dy.reshape(rshape) if has_res and ng[3] else None
@@ -150,8 +139,8 @@ class _MlpFn(torch.autograd.Function):
         dh = ops.gemm(d, ops.transpose_cast(w2c, cdt), aux=gp, flags=ME_GEMM_AUX_IS_FACTOR)      # (d W2) * gelu'
         if p > 0:
             dh = ops.dropout_add(dh, None, rows, p, 0.0, seed_hidden)
-        dw2, db2 = _wgrad(d, a, True)
-        dw1, db1 = _wgrad(dh, xc, True)
+        dw2, db2 = wgrad(d, a, bias=True, fused_bias=True)
+        dw1, db1 = wgrad(dh, xc, bias=True, fused_bias=True)
         dx = ops.gemm(dh, ops.transpose_cast(w1c, cdt), residual=dy2, out_dtype=torch.float32)
         return dx.reshape(xshape), dw1.to(wdt), db1.to(wdt), dw2.to(wdt), db2.to(wdt), None, None, None, None, None
 
@@ -339,7 +328,7 @@ class Decoder(nn.Module):
         if self.norm is not None:
             x = _layer_norm(self.norm, x.float()).reshape(x.shape)
         if self.projection is not None:
-            x = heads.linear(x.to(cdt), self.projection.weight, self.projection.bias)      # (fp32 result; N padded to a multiple of 8 inside)
+            x = linear(x.to(cdt), self.projection.weight, self.projection.bias)      # (fp32 result; N padded to a multiple of 8 inside)
         return x
 
 

@@ -23,13 +23,12 @@ from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import _capi, ops
-from ._capi import ME_GEMM_TN, MetaEncError, check, dtype_code, ptr, stream_ptr
+from ._capi import MetaEncError, check, dtype_code, ptr, stream_ptr
 from .data2seq import VideoPatchEmbed, _boundary_dtypes, video_sinusoid_table
 from .encoder import Block
-from .heads import linear
+from .linear import linear, pad_to, wgrad
 
 IMAGENET_DEFAULT_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_DEFAULT_STD = (0.229, 0.224, 0.225)
@@ -248,10 +247,7 @@ class _VisibleEmbedFn(torch.autograd.Function):
         K = weight[0].numel()
         M = B * Nvis
         xg = tubelet_gather(video, vis_idx, tubelet, out_dtype=cdt, pad_cols_to=8, pad_rows_to=8)       # zero rows / columns pad to the GEMM granules
-        Kp = xg.shape[1]
-        wc = ops.cast(weight.detach().reshape(C, K).contiguous(), cdt)
-        if Kp != K:
-            wc = F.pad(wc, (0, Kp - K))
+        wc = pad_to(ops.cast(weight.detach().reshape(C, K).contiguous(), cdt), 1)
         pos_rows = take_rows(ops._f32(pos.detach()).reshape(-1, C), vis_idx, out_dtype=torch.float32).view(M, C)
         kdt = torch.bfloat16 if odt == torch.float16 else odt
         b32 = None if bias is None else ops._f32(bias.detach()).contiguous()
@@ -269,15 +265,15 @@ class _VisibleEmbedFn(torch.autograd.Function):
         d2 = dy.reshape(M, C).contiguous()
         if d2.dtype == torch.float16:
             d2 = ops.cast(d2, torch.bfloat16)
-        d2 = ops.cast(d2, xg.dtype)
-        if xg.shape[0] != M:
-            d2 = torch.cat([d2, d2.new_zeros(xg.shape[0] - M, C)])
+        d2 = pad_to(ops.cast(d2, xg.dtype), 0)      # (xg came from the gather with its rows padded already)
+        need_b = bdt is not None and ctx.needs_input_grad[3]
         dw = db = None
         if ctx.needs_input_grad[2]:
-            dw = ops.gemm(d2, xg, op=ME_GEMM_TN, out_dtype=torch.float32)[:, :K].reshape(wshape).to(wdt)
-        if bdt is not None and ctx.needs_input_grad[3]:
-            db = ops.colsum(d2).to(bdt)
-        return None, None, dw, db, None, None, None, None
+            dw, db = wgrad(d2, xg, bias=need_b)
+            dw = dw[:, :K].reshape(wshape).to(wdt)
+        elif need_b:
+            db = ops.colsum(d2)
+        return None, None, dw, db.to(bdt) if need_b else None, None, None, None, None
 
 
 class _AssembleFn(torch.autograd.Function):

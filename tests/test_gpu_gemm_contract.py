@@ -209,7 +209,7 @@ def test_gemm_contract(dev, case):
 
 
 def test_gemm_k_window_of_wider_operands(dev):
-    """adapter._gemm_nt_chunked: fp32 A / B are K windows of wider matrices (lda = ldb = K_total, pointer offset k0), accumulated with
+    """linear._gemm_nt_chunked: fp32 A / B are K windows of wider matrices (lda = ldb = K_total, pointer offset k0), accumulated with
     beta = 1 window by window.  Here every column OUTSIDE the current window is NaN while its call runs."""
     lib = _capi.load()
     M, N, Kt, step = 130, 132, 328, 128

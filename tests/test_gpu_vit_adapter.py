@@ -5,7 +5,7 @@ max |got - f64| / max |f64| <= min(max(4 x ref_err, OP_FLOOR), TOL_F32), ref_err
 evaluated in float32 on the CPU.  OP_FLOOR = 2^-22 = four float32 roundings (2^-24 each, relative to the tensor's largest
 magnitude): a pure selection or permutation has ref_err 0 and must then be exact up to the few additions the backward makes.
 Index outputs are compared with torch.equal.
-conv3x3_rows contracts fp32 operands 128 columns at a time (adapter._gemm_nt_chunked): as one me_gemm call the K = 576 forward
+conv3x3_rows contracts fp32 operands 128 columns at a time (linear._gemm_nt_chunked): as one me_gemm call the K = 576 forward
 measured 4.07 x ref_err, outside this bound.
 
 Fixture cases (tests/golden/vit_adapter.npz, tools/make_vit_adapter_golden.py): max |got - f64| / max |f64| <=
