@@ -31,7 +31,7 @@ from . import _capi, ops
 from ._capi import MetaEncError, check, dtype_code, ptr, stream_ptr
 from .data2seq import AcousticPatchEmbed, _PatchEmbedFn, _boundary_dtypes
 
-FRAMES_PER_WORKGROUP = 32          # ME_FBANK_RUN (include/metaenc.h): output rows one workgroup of me_fbank owns
+FRAMES_PER_WORKGROUP = _capi.ME_FBANK_RUN      # output rows one workgroup of me_fbank owns
 LOW_FREQ = 20.0                    # Kaldi's default low edge of the mel filters
 
 

@@ -1,5 +1,5 @@
-"""CPU: the drop-in boundary -- the C-ABI library loads and exports every symbol include/metaenc.h declares, the
-ctypes mirror of the descriptor struct matches the C layout, the product package never touches oracle/, and the
+"""CPU: the drop-in boundary -- the C-ABI library loads and exports every symbol include/metaenc.h declares; what the ctypes binding
+derives from the header (struct layouts, prototypes, constants) is what gcc sees in it; the product package never touches oracle/, and the
 host-side module mirrors the reference's plugin interface (names, shapes, error behaviour)."""
 import ctypes
 import os
@@ -14,7 +14,7 @@ import torch.nn as nn
 from conftest import ROOT
 
 import metatransformer_amd as M
-from metatransformer_amd import _capi, build as me_build
+from metatransformer_amd import _capi, _header, build as me_build
 from oracle import block_oracle as bo
 
 HEADER = os.path.join(ROOT, "include", "metaenc.h")
@@ -42,26 +42,142 @@ def test_header_symbols_all_bound_and_exported(lib):
     assert lib.me_build_arch() == b"gfx950"
 
 
-@pytest.mark.parametrize("cname,pyname", [("me_gemm_desc", "GemmDesc"), ("me_block_desc", "BlockDesc"),
-                                          ("me_block_grads", "BlockGrads"), ("me_gemm_profile_rec", "GemmProfileRec"),
-                                          ("me_adamw_segment", "AdamwSegment"), ("me_adamw_ctl", "AdamwCtl"),
-                                          ("me_patch_embed_desc", "PatchEmbedDesc")])
-def test_struct_layouts_match_c(cname, pyname):
-    """every struct that crosses the C ABI: size and field offsets of the ctypes mirror == what gcc lays out from the header"""
-    cls = getattr(_capi, pyname)
-    fields = [n for n, _ in cls._fields_]
-    code = ('#include <stdio.h>\n#include <stddef.h>\n#include "metaenc.h"\nint main(void){ printf("size %zu\\n", sizeof('
-            + cname + '));\n' + "".join(f'printf("{f} %zu\\n", offsetof({cname}, {f}));\n' for f in fields) + "return 0; }\n")
+def run_c(code, run=True):
+    """compile `code` (which includes metaenc.h) with gcc -Werror; run=True: -> {first word: second word} of the lines it prints"""
     with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(code)
-        exe = os.path.join(d, "t")
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe], check=True)
-        out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split("\n")
-    got = dict(l.split() for l in out if l)
+        src, exe = os.path.join(d, "t.c"), os.path.join(d, "t")
+        open(src, "w").write('#include <stdio.h>\n#include <stddef.h>\n#include "metaenc.h"\n' + code)
+        gcc = ["gcc", "-Werror", "-I", os.path.join(ROOT, "include"), src]
+        res = subprocess.run(gcc + (["-o", exe] if run else ["-fsyntax-only"]), capture_output=True, text=True)
+        assert res.returncode == 0, res.stderr
+        if run:
+            return dict(l.split() for l in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split("\n") if l)
+
+
+def header_text():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
+def test_every_struct_body_of_the_header_is_mirrored():
+    assert set(re.findall(r"typedef\s+struct\s+(me_\w+)\s*\{", header_text())) == set(_capi.STRUCTS) == set(_header.read()[1])
+    for cname, cls in _capi.STRUCTS.items():
+        assert getattr(_capi, cls.__name__) is cls and cls.__name__ == "".join(w.capitalize() for w in cname[3:].split("_"))
+    assert {"GemmDesc", "AttnQkvDesc", "TcBatch", "GemmProfileRec"} <= {c.__name__ for c in _capi.STRUCTS.values()}
+
+
+@pytest.mark.parametrize("cname,pyname", [(c, cls.__name__) for c, cls in _capi.STRUCTS.items()])
+def test_struct_layouts_match_c(cname, pyname):
+    """every struct that crosses the C ABI: size and field offsets of the ctypes class == what gcc lays out from the header; of an
+    array of nested structs the members of elements 0 and 1"""
+    cls = getattr(_capi, pyname)
+    want = {}
+    for name, ft in cls._fields_:
+        want[name] = getattr(cls, name).offset
+        if hasattr(ft, "_length_"):
+            assert ft._length_ >= 2
+            for i in (0, 1):
+                for sub, _ in ft._type_._fields_:
+                    want[f"{name}[{i}].{sub}"] = want[name] + i * ctypes.sizeof(ft._type_) + getattr(ft._type_, sub).offset
+    assert [n for n, _ in cls._fields_] == [n for n, _ in _header.read()[1][cname]]
+    got = run_c(f'int main(void){{ printf("size %zu\\n", sizeof({cname}));\n'
+                + "".join(f'printf("{f} %zu\\n", offsetof({cname}, {f}));\n' for f in want) + "return 0; }\n")
     assert int(got.pop("size")) == ctypes.sizeof(cls)
-    for name in fields:
-        assert int(got[name]) == getattr(cls, name).offset, name
+    assert {k: int(v) for k, v in got.items()} == want
+
+
+def test_parsed_prototypes_redeclare_without_conflict():
+    """the compiler checks the reader: every function re-declared from the PARSED types behind the header's own declaration -- a type
+    read wrongly, an argument lost or added is a conflicting redeclaration, a compile error"""
+    protos = _header.read()[2]
+    assert sorted(protos) == header_functions() and len(protos) >= 107
+    run_c("".join(f"{ret} {name}({', '.join(f'{t} a{i}' for i, (t, _) in enumerate(args)) or 'void'});\n"
+                  for name, (ret, args) in protos.items()), run=False)
+    with pytest.raises(AssertionError, match="conflicting types"):          # (the check does fail on a wrong type)
+        run_c("int me_cast(const void* a0, int a1, void* a2, int a3, int a4, void* a5);\n", run=False)
+
+
+def test_c_types_map_to_ctypes():
+    """the C-to-ctypes table, pinned by argument lists written out by hand"""
+    from ctypes import POINTER, c_char_p, c_float as F, c_int as I, c_int64 as L, c_size_t, c_uint64, c_void_p as P
+    S = _capi.SIGNATURES
+    assert S["me_mae_loss"] == (I, [P, I] + [I] * 8 + [P, P, P, P, I, P, I, L, I, P, P, P, P, L, P, L, P])
+    assert S["me_attention_bwd"] == (I, [P, L, P, L, P, L, P, P, P, L, I, I, I, I, F, I, F, c_uint64, P])
+    assert S["me_dropout_add"] == (I, [P, I, P, I, P, I, L, I, L, F, F, c_uint64, P, P])
+    assert S["me_device_info"] == (I, [I, P, P, P, c_char_p, I])
+    assert S["me_block_fwd"] == (I, [POINTER(_capi.BlockDesc), P, P, P, P, c_size_t, P])
+    assert S["me_block_bwd"][1][5] is POINTER(_capi.BlockGrads) and S["me_gemm_profile_read"][1] == [POINTER(_capi.GemmProfileRec), I]
+    assert S["me_last_error"] == (c_char_p, []) and S["me_block_saved_bytes"] == (c_size_t, [POINTER(_capi.BlockDesc)])
+    # the AdamW control block and segment table live in device memory: addresses, like every other device pointer
+    assert S["me_adamw_prepare"][1][0] is P and S["me_adamw_step_segments"][1][5] is P and S["me_adamw_step_segments"][1][11] is P
+    assert [t for _, t in _capi.AttnQkvDesc._fields_][:4] == [P, P, P, L] and dict(_capi.AttnQkvDesc._fields_)["seed"] is c_uint64
+    assert dict(_capi.GemmDesc._fields_)["alpha"] is F and dict(_capi.GemmDesc._fields_)["op"] is ctypes.c_int32
+
+
+def test_constants_equal_what_the_compiler_sees():
+    consts = _header.read()[0]
+    names = set(re.findall(r"\b(ME_[A-Z0-9_]+)\s*=", header_text())) | set(re.findall(r"#define\s+(ME_\w+)[ \t]+\S", header_text()))
+    assert set(consts) == names and len(names) >= 47
+    got = run_c("int main(void){\n" + "".join(f'printf("{n} %lld\\n", (long long){n});\n' for n in consts) + "return 0; }\n")
+    assert {k: int(v) for k, v in got.items()} == consts == {n: getattr(_capi, n) for n in consts}
+    # values that callers and stored records rely on
+    pinned = dict(ME_ABI_VERSION=1, ME_F32=0, ME_BF16=1, ME_F16=2, ME_GROUP_DP=0, ME_GROUP_DP_FJ=1, ME_GROUP_DP_DF=2, ME_GROUP_DP_FJ_DF=3,
+                  ME_GRAPH_BWD_INDEX=1, ME_GRAPH_BWD_GATHER=2, ME_ERR_UNSUPPORTED=-2)
+    assert {n: consts[n] for n in pinned} == pinned
+    from metatransformer_amd import audio
+    assert audio.FRAMES_PER_WORKGROUP == consts["ME_FBANK_RUN"]
+
+
+@pytest.mark.parametrize("text,word", [
+    ("int me_x(int a, double b);", "double"),                                        # a scalar outside the table
+    ("int me_x(int a, int);", "argument 'int'"),                                               # an argument without a name
+    ("typedef struct me_s { int32_t a; long b; } me_s;", "long"),
+    ("typedef struct me_s { int32_t a[4]; } me_s;", "a[4]"),                          # arrays only of nested structs
+    ("typedef struct me_s { struct { struct { int a; } x[2]; } y[2]; } me_s;", "nested"),
+    ("typedef struct me_s { struct { int a; } x[ME_NOWHERE]; } me_s;", "ME_NOWHERE"),
+    ("typedef struct me_s { int a; } me_t;", "me_s"),
+    ("enum { ME_A = 0, ME_B };", "ME_B"),
+    ("enum { ME_A = 1 << 2 };", "ME_A"),
+    ("#define ME_Z 1.5\n", "ME_Z"),
+    ("union me_u { int a; float b; };", "me_u"),
+    ("int me_x(int a)", "me_x"),                                                     # no semicolon
+    ("int me_x(int (*cb)(int));", "me_x"),
+])
+def test_reader_raises_on_what_it_does_not_understand(text, word):
+    with pytest.raises(_header.HeaderError, match=re.escape(word)):
+        _header.parse("int me_ok(void);\n" + text)
+
+
+def test_reader_reads_the_forms_the_header_uses():
+    c, s, p = _header.parse("""#ifndef X_H
+        #define X_H
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        #define ME_N 3   /* three */
+        enum { ME_A = 0, ME_B = -2 /* , ME_C = 5 */ };
+        typedef struct me_opaque me_opaque;
+        typedef struct me_s { const void *p, *q; int64_t M, N; float* f; struct { void* src; int64_t rows, cols; } item[ME_N]; size_t n; } me_s;
+        const char* me_name(void);
+        size_t me_f(const me_s* d, me_opaque** h, const float* const* tables, uint64_t seed /* seed */, void* stream);
+        #ifdef __cplusplus
+        }
+        #endif
+        #endif""")
+    assert c == dict(ME_N=3, ME_A=0, ME_B=-2)
+    assert s == {"me_s": [("p", "const void*"), ("q", "const void*"), ("M", "int64_t"), ("N", "int64_t"), ("f", "float*"),
+                          ("item", ([("src", "void*"), ("rows", "int64_t"), ("cols", "int64_t")], 3)), ("n", "size_t")]}
+    assert p == {"me_name": ("const char*", []),
+                 "me_f": ("size_t", [("const me_s*", "d"), ("me_opaque**", "h"), ("const float* const*", "tables"), ("uint64_t", "seed"),
+                                     ("void*", "stream")])}
+
+
+def test_missing_header_fails_loudly(monkeypatch):
+    import importlib.util
+    monkeypatch.setattr(_header, "HEADER_PATH", "/nonexistent/include/metaenc.h")
+    spec = importlib.util.spec_from_file_location("metatransformer_amd._capi_without_header", _capi.__file__)
+    with pytest.raises(RuntimeError, match="looked for at /nonexistent/include/metaenc.h") as e:
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
+    assert type(e.value).__name__ == "MetaEncError"
 
 
 def test_patch_embed_fuses_the_reference_geometries(lib):

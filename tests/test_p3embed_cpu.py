@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from metatransformer_amd import MetaEncError, P3Embed, _capi
+from metatransformer_amd import MetaEncError, P3Embed
 
 RECIPES = ["scanobjectnn", "shapenetpart", "s3dis", "scannet"]
 
@@ -63,9 +63,3 @@ def test_unsupported_options_raise(kw, word):
     base.update(kw)
     with pytest.raises(MetaEncError, match=word):
         P3Embed(**base)
-
-
-def test_entry_points_declared():
-    for name in ("me_knn_stream", "me_group_features", "me_group_features_bwd", "me_group_features_bwd_workspace"):
-        assert name in _capi.SIGNATURES
-    assert (_capi.ME_GROUP_DP, _capi.ME_GROUP_DP_FJ, _capi.ME_GROUP_DP_DF, _capi.ME_GROUP_DP_FJ_DF) == (0, 1, 2, 3)
